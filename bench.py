@@ -16,10 +16,19 @@ N > 1: data-parallel, weak scaling: every rank takes its own 32-sample shard of 
        batch.  IDQN_DP_MODE=allreduce all-reduces the 80.9 MB gradient arena instead.
        `value` counts 32-sample gradient steps: N per global step (units all ranks processed / time).
 
+A plain run sets up, warms up, times exactly --steps steps in one region, writes the outputs if --dump-outputs is given and
+prints the line (metric, value, unit, higher_is_better, dtype, ms_per_step and the configuration).  Everything else is --full:
+
 roofline: the dominant kernel (the fused Dense_0 update, HBM-bound) timed with hipEvents on its own stream inside
 the timed regions, on every 4th step (PROFILE_EVERY: the bracket keeps the launch from overlapping its neighbours and
 costs a bracketed step 4.5 - 5 us); cpu_baseline: the oracle's torch-CPU fp32 restatement of the same step, timed on this
-box's host cores on a bounded sample (rank 0, N = 1 only) -- a reported baseline, not the target.
+box's host cores on a bounded sample (rank 0, N = 1 only) -- a reported baseline, not the target.  --full also repeats short
+regions until ~1500 steps are timed (the median region is reported) and adds step_roofline, the per-launch kernel table, the
+sampling leg, the K-sweep fit and, for data-parallel runs, the single-GPU step of the same ranks.
+
+--dump-outputs DIR: after the timed steps, what learn_on_batch hands its caller after the last one (per-head losses, parameters,
+Adam moments and count) as DIR/<name>.npy (dump_outputs).  Inputs and initial parameters are seeded, so two builds can be
+compared output for output.
 """
 import argparse
 import json
@@ -71,6 +80,32 @@ def step_work(K, B, A):
     f_bwd = 2 * f_fwd - 2 * 3612672
     P = 8 * 8 * 4 * 32 + 32 + 4 * 4 * 32 * 64 + 64 + 3 * 3 * 64 * 64 + 64 + 7744 * 512 + 512 + 512 * A + A
     return K * B * (2 * f_fwd + f_bwd), K * 7 * 4 * P + 2 * B * 28224 + 9 * B
+
+
+WARMUP_MIN_STEPS = 200  # a plain run's warm-up floor (main(): the first ~150 steps of a process are slower)
+DUMP_SAMPLE = 1 << 21  # positions kept of each [K, P] arena by --dump-outputs (8 MB in f32; the headline arenas are 20.2 M floats)
+
+
+def dump_outputs(out_dir, agent):
+    """learn_on_batch's results after the last timed step (idqn.py:96-109: params, optimizer_state, losses) as float32 .npy files:
+    losses [K], adam_count [K], and of each parameter / moment arena the same seeded sample of DUMP_SAMPLE flat positions (sorted),
+    the whole arena when it is smaller.  24 MB at the headline size."""
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    n = agent._online.numel()
+    idx = None
+    if n > DUMP_SAMPLE:
+        idx = torch.from_numpy(np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))).cuda()
+
+    def take(arena):
+        flat = arena.reshape(-1)
+        return (flat if idx is None else flat[idx]).float().cpu().numpy()
+
+    outs = {"losses": agent._losses.float().cpu().numpy(), "adam_count": agent._count.float().cpu().numpy(),
+            "params": take(agent._online), "adam_mu": take(agent._mu), "adam_nu": take(agent._nu)}
+    for name, a in outs.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a, np.float32))
 
 
 def heads_fit(A, heads=(1, 2, 3, 5), steps=200, warmup=30):
@@ -345,7 +380,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=500)
-    ap.add_argument("--warmup", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=50,
+                    help="warm-up steps before the timed steps (a plain run runs at least WARMUP_MIN_STEPS = 200: timing.warmup_steps_run)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: CPU baseline, roofline + PMC traffic, step roofline, per-launch "
+                         "kernel table, sampling leg, K-sweep fit, the data-parallel runs' single-GPU step, and short timed regions "
+                         "repeated until ~1500 steps are timed (median region reported)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (losses, parameters, Adam state) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-side-legs", action="store_true",
                     help="profiling runs (rocprofv3 --pmc / --kernel-trace): nothing but the warm-up and the timed steps of THIS "
@@ -357,7 +399,9 @@ def main():
     ap.add_argument("--force-dp", action="store_true",
                     help="rehearse the data-parallel path (RCCL all-reduce + two-phase step) even with one rank")
     ap.add_argument("--actions", type=int, default=N_ACTIONS, help="action count A (SURVEY 8d: 6, repeat with 18)")
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps steps each; the median is reported")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps steps each; the median is reported (default: 1 on a plain run; 5 with --full "
+                         "or another mode, the headline path with --full repeating short regions until ~1500 steps are timed)")
     ap.add_argument("--emulate-ranks", type=int, default=0,
                     help="ONE GPU: the compute side of rank 0 of an N-rank factored data-parallel step (the fused Dense_0 update "
                          "runs over N sample blocks: this rank's factors N times), no collective; a regression guard for the "
@@ -382,6 +426,11 @@ def main():
                     help="iiqn: BASELINE config 3 (i-IQN heads, 32 quantile fractions; a labelled extension -- the reference "
                          "has no quantile code), one GPU, its own JSON line")
     args = ap.parse_args()
+    plain_regions = args.repeats if args.repeats is not None else 1
+    if args.repeats is None:
+        args.repeats = 5
+    if args.dump_outputs and (args.heads_per_gpu or args.algo != "idqn" or args.emulate_ranks or args.learner or "," in args.heads):
+        ap.error("--dump-outputs writes the outputs of the i-DQN step (the headline path and its --batch / --heads / data-parallel variants)")
 
     if (args.gpus > 1 or args.heads_per_gpu) and "WORLD_SIZE" not in os.environ:
         # No launcher around us: start the N ranks as fresh child processes (one per GPU, RCCL) and relay rank 0's
@@ -464,7 +513,7 @@ def main():
     dp = world > 1 or args.force_dp
     # The CPU leg FIRST (the reference path is timed before the GPU runs), rank 0 of a single-GPU run only.
     cpu = None
-    if rank == 0 and not dp and not args.no_cpu_baseline:
+    if rank == 0 and not dp and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(n_actions=A, heads=K, batch=B)
         cpu["jax"] = jax_cpu_probe(n_actions=A) if headline else {"status": "probed on the headline configuration only"}
     agent = iDQN(0, OBS, A, K, FEATURES, "cnn", 6.25e-5, 0.99, 1, 1, 10**9, 10**9, adam_eps=1.5e-4)
@@ -493,7 +542,7 @@ def main():
     # data-parallel runs: the SAME rank's plain single-GPU step (no collective, no factor exchange) timed first, so that the line
     # can say what N ranks cost relative to one -- t(1) / t(N) at fixed per-rank work -- instead of leaving it to a second run
     single_ms = None
-    if dp:
+    if dp and args.full:
         for _ in range(20):
             agent._learn(batches[0])
         t1s = []
@@ -508,7 +557,14 @@ def main():
         dist.all_reduce(t1, op=dist.ReduceOp.MAX)
         single_ms = float(t1.item()) * 1e3
 
-    for _ in range(args.warmup):
+    # a plain run's one region must not open on a cold chip: the step still speeds up over the first ~150 steps of a process
+    # (--full's 20-step regions read 0.283, 0.273, 0.269, 0.266, 0.263 ms before settling at 0.260), so it warms up for at least
+    # WARMUP_MIN_STEPS steps -- a count, not a time, so that --dump-outputs sees the same steps on every run
+    n_warmup = args.warmup if args.full else max(args.warmup, WARMUP_MIN_STEPS)
+    import gc
+
+    gc.collect()  # before the warm-up: a collection between it and the timed steps idles the chip, and the first region opens cold
+    for _ in range(n_warmup):
         step()
 
     # `repeats` timed regions of EXACTLY `steps` steps each, barrier + synchronize on both sides, max over ranks;
@@ -516,10 +572,11 @@ def main():
     # ~1500 steps have been timed: the first regions after the CPU leg still see the clocks ramp (the round-4 driver line read
     # 0.2946, 0.2854, 0.2816, 0.2789, 0.2763 ms over its five) and a single host hiccup is a whole region; the median over more
     # regions is the steady-state figure SURVEY 8d defines the metric on.  Every region is listed under timing.ms_per_step_all.
-    import gc
-
-    gc.collect()
-    n_regions = max(1, args.repeats, min(75, -(-1500 // max(1, args.steps)))) | 1  # odd: the median is a region that was run
+    if args.full:
+        n_regions = max(1, args.repeats, min(75, -(-1500 // max(1, args.steps)))) | 1  # odd: the median is a region that was run
+    else:  # a plain run times exactly --steps steps (unless --repeats asks for more regions)
+        n_regions = max(1, plain_regions)
+    profile_flag = _hip.F_PROFILE if args.full else 0
     regions = []
     for _ in range(n_regions):
         barrier()
@@ -528,7 +585,7 @@ def main():
             # the dominant kernel is bracketed with hipEvents on every PROFILE_EVERY-th step of the region only: a bracketed
             # launch cannot overlap its neighbours' launch / tail phases, which costs the step 4.5 - 5 us (measured: the fifth
             # 500-step region of the earlier all-steps scheme ran past the 2048-event buffer and was that much faster)
-            step(_hip.F_PROFILE if i % PROFILE_EVERY == 0 else 0)
+            step(profile_flag if i % PROFILE_EVERY == 0 else 0)
         barrier()
         elapsed = time.perf_counter() - t0
         if dp:
@@ -537,6 +594,8 @@ def main():
             elapsed = float(tmax.item())
         regions.append(elapsed)
     elapsed = float(np.median(regions))
+    if args.dump_outputs and rank == 0:  # before anything else steps the agent
+        dump_outputs(args.dump_outputs, agent)
 
     import ctypes as C
 
@@ -544,7 +603,7 @@ def main():
     _hip.check(_hip.lib().idqn_profile_read(agent._handle, C.byref(mean_ms), C.byref(n_l), name), "idqn_profile_read")
     # per-launch table: a short extra run (outside the timed regions) with one hipEvent behind every launch
     kernels = []
-    if not dp and not args.no_side_legs:
+    if not dp and args.full and not args.no_side_legs:
         for _ in range(60):
             step(_hip.F_PROFILE_ALL)
         torch.cuda.synchronize()
@@ -613,7 +672,7 @@ def main():
                        "heads": K, "batch_per_gpu": B, "global_batch": global_batch, "actions": A,
                        "parallelism": f"dp{world}" if dp else "single",
                        "conv_arithmetic": os.environ.get("IDQN_CONV", "bf16x3") + " (f32-accurate products)"},
-            "timing": {"regions": n_regions, "steps_per_region": args.steps, "reported": "median region",
+            "timing": {"regions": n_regions, "steps_per_region": args.steps, "reported": "median region", "warmup_steps_run": n_warmup,
                        "ms_per_step_all": [r / args.steps * 1e3 for r in regions]},
             "roofline": {"bound": "hbm", "kernel": name.value.decode() + ("<fused Adam>" if fused else "<grad only>"),
                          "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -633,6 +692,9 @@ def main():
             "kernels": kernels,
             "final_losses": [float(x) for x in losses],
         }
+        if not args.full:  # the dominant kernel was not bracketed and no per-launch run was made: those figures are --full's
+            for key in ("roofline", "step_roofline", "kernels"):
+                del out[key]
         if dp:
             out["rccl"] = rccl_report(dp_mode, world, agent, args.dp_streams or os.environ.get("IDQN_DP_STREAMS", "side"))
             # `value` counts every rank's 32-sample step (weak scaling: N ranks = N x the samples per global step), so it grows
@@ -646,7 +708,7 @@ def main():
                 "scaling_efficiency": (single_ms / ms_step) if single_ms else None,  # t(1) / t(N) at fixed per-rank work
                 "what": "weak scaling: per-rank batch fixed at %d, global batch %d; efficiency 1.0 = the N-rank step costs what the "
                         "single-GPU step costs" % (B, global_batch)}
-        if headline and not dp and not args.no_side_legs:
+        if headline and not dp and args.full and not args.no_side_legs:
             try:
                 out["sampling"] = sampling_leg()
             except Exception as e:  # noqa: BLE001 -- the headline line must not depend on this leg

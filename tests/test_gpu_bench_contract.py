@@ -1,11 +1,13 @@
-"""The bench line the driver parses (task contract): one JSON object on stdout with the metric, the timing fields, `roofline` (the
-dominant kernel priced against HBM, measured with hipEvents inside the timed regions) and, unless switched off, `cpu_baseline`.
+"""The bench line the driver parses (task contract): one JSON object on stdout with the metric and the timing fields; a plain run
+times exactly --steps steps and can dump the last step's outputs, `--full` adds `roofline` (the dominant kernel priced against HBM,
+measured with hipEvents inside the timed regions) and, unless switched off, `cpu_baseline`.
 Run here with a handful of steps: the figures are meaningless, the structure and the arithmetic between the fields are checked."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -21,7 +23,7 @@ def _bench(*args):
 
 
 def test_default_line_has_the_contract_fields_and_consistent_arithmetic():
-    d = _bench("--gpus", "1", "--steps", "8", "--warmup", "2", "--repeats", "3", "--no-cpu-baseline")
+    d = _bench("--gpus", "1", "--steps", "8", "--warmup", "2", "--repeats", "3", "--no-cpu-baseline", "--full")
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
                 "dtype", "data", "config", "roofline"):
         assert key in d, key
@@ -52,10 +54,29 @@ def test_default_line_has_the_contract_fields_and_consistent_arithmetic():
     assert "traffic" in d["step_roofline"]
 
 
+def test_plain_line_times_exactly_the_steps_and_dumps_the_last_step(tmp_path):
+    """A plain run: one region of exactly --steps steps, the headline fields, none of --full's legs; --dump-outputs writes the
+    last step's losses, parameters and Adam state as float32 .npy files, 64 MB at most, the losses those of the line."""
+    d = _bench("--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", str(tmp_path / "out"))
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in d, key
+    assert d["steps"] == 7 and d["timing"]["regions"] == 1 and len(d["timing"]["ms_per_step_all"]) == 1
+    assert abs(d["value"] - 1e3 / d["ms_per_step"]) <= 1e-6 * d["value"]
+    for key in ("roofline", "step_roofline", "kernels", "sampling", "heads_fit", "cpu_baseline"):
+        assert key not in d, key
+    files = {f: np.load(tmp_path / "out" / f) for f in os.listdir(tmp_path / "out")}
+    assert set(files) == {"losses.npy", "adam_count.npy", "params.npy", "adam_mu.npy", "adam_nu.npy"}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in files.values())
+    assert sum(os.path.getsize(tmp_path / "out" / f) for f in files) <= 64 << 20
+    assert np.array_equal(files["losses.npy"], np.asarray(d["final_losses"], np.float32))
+    assert d["timing"]["warmup_steps_run"] >= 2 and (files["adam_count.npy"] == d["timing"]["warmup_steps_run"] + 7).all()  # nothing else
+    assert files["params.npy"].shape == files["adam_mu.npy"].shape == files["adam_nu.npy"].shape == (1 << 21,)
+
+
 @pytest.mark.parametrize("flags,K,B", [(("--batch", "256"), 5, 256), (("--heads", "64"), 64, 32)])
 def test_config_4_and_5_single_device_lines(flags, K, B):
     """BASELINE configs 4 (B = 256 per step) and 5 (K = 64) as kept single-device bench lines with their floors."""
-    d = _bench(*flags, "--steps", "6", "--warmup", "2", "--repeats", "1", "--no-cpu-baseline")
+    d = _bench(*flags, "--steps", "6", "--warmup", "2", "--repeats", "1", "--no-cpu-baseline", "--full")
     assert d["config"]["heads"] == K and d["config"]["batch_per_gpu"] == B and f"K={K} batch={B}" in d["metric"]
     nb = B // 32
     # (from three sample blocks on the data gradient is its own launch: the update kernel reads a3 and dh of every block, writes no dL/da3)
@@ -66,7 +87,7 @@ def test_config_4_and_5_single_device_lines(flags, K, B):
 
 
 def test_cpu_baseline_object():
-    d = _bench("--steps", "4", "--warmup", "1", "--repeats", "1")
+    d = _bench("--steps", "4", "--warmup", "1", "--repeats", "1", "--full")
     c = d["cpu_baseline"]
     for key in ("value", "unit", "cores", "kind", "sample"):
         assert key in c, key
@@ -77,7 +98,7 @@ def test_cpu_baseline_object():
 def test_data_parallel_line_separates_rank_steps_from_global_steps():
     """The N > 1 line (rehearsed with one rank over RCCL): `value` counts rank-steps, so the line also carries the global step rate,
     the per-rank step time and t(1) / t(N) measured in the same run -- and RCCL's own log excerpt."""
-    d = _bench("--gpus", "1", "--force-dp", "--steps", "8", "--warmup", "2", "--repeats", "3")
+    d = _bench("--gpus", "1", "--force-dp", "--steps", "8", "--warmup", "2", "--repeats", "3", "--full")
     assert d["n_gpus"] == 1 and d["scaling"] == "weak" and d["config"]["parallelism"] == "dp1"
     p = d["data_parallel"]
     assert abs(p["per_rank_ms_per_step"] - d["ms_per_step"]) <= 1e-9

@@ -6,21 +6,21 @@ mkdir -p gpurun_out/final && cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_R
 O=gpurun_out/final
 PART=${PART:-all}   # a: headline set + PMC, b: other configurations, c: rehearsals / switches / loops (one gpurun call each: 1100 s limit)
 if [ $PART = all ] || [ $PART = a ]; then
-timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_steps20.json 2> $O/bench_steps20.err; echo "bench steps20 rc=$?"
-timeout -k 10 300 python bench.py --actions 18 --no-cpu-baseline > $O/bench_a18.json 2> $O/bench_a18.err; echo "bench a18 rc=$?"
+timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_steps20.json 2> $O/bench_steps20.err; echo "bench steps20 rc=$?"
+timeout -k 10 300 python bench.py --full --actions 18 --no-cpu-baseline > $O/bench_a18.json 2> $O/bench_a18.err; echo "bench a18 rc=$?"
 rm -rf $O/prof; timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python bench.py --steps 100 --warmup 20 --repeats 1 --no-cpu-baseline --no-side-legs > $O/prof.log 2>&1
 cp $O/prof/*/*_kernel_stats.csv $O/kernel_stats.csv && echo "kernel stats ok"; rm -rf $O/prof
 bash tools/gpu_pmc.sh > $O/pmc.log 2>&1; tail -5 $O/pmc.log
 fi
 if [ $PART = all ] || [ $PART = b ]; then
-timeout -k 10 300 python bench.py --batch 256 --steps 200 --warmup 20 --repeats 3 > $O/bench_b256.json 2> $O/bench_b256.err; echo "b256 rc=$?"
-timeout -k 10 300 python bench.py --heads 64 --steps 60 --warmup 10 --repeats 3 > $O/bench_k64.json 2> $O/bench_k64.err; echo "k64 rc=$?"
+timeout -k 10 300 python bench.py --full --batch 256 --steps 200 --warmup 20 --repeats 3 > $O/bench_b256.json 2> $O/bench_b256.err; echo "b256 rc=$?"
+timeout -k 10 300 python bench.py --full --heads 64 --steps 60 --warmup 10 --repeats 3 > $O/bench_k64.json 2> $O/bench_k64.err; echo "k64 rc=$?"
 fi
 if [ $PART = all ] || [ $PART = c ]; then
-for st in inline side; do timeout -k 10 300 python bench.py --gpus 1 --force-dp --dp-streams $st > $O/bench_dp1_native_$st.json 2> $O/dp1_native_$st.err; echo "dp native $st rc=$?"; done
-IDQN_DP_MODE=factored timeout -k 10 300 python bench.py --gpus 1 --force-dp > $O/bench_dp1_python.json 2> $O/dp1_python.err; echo "dp python factored rc=$?"
-IDQN_DP_MODE=allreduce timeout -k 10 300 python bench.py --gpus 1 --force-dp > $O/bench_dp1_allreduce.json 2> $O/dp1_allreduce.err; echo "dp allreduce rc=$?"
+for st in inline side; do timeout -k 10 300 python bench.py --full --gpus 1 --force-dp --dp-streams $st > $O/bench_dp1_native_$st.json 2> $O/dp1_native_$st.err; echo "dp native $st rc=$?"; done
+IDQN_DP_MODE=factored timeout -k 10 300 python bench.py --full --gpus 1 --force-dp > $O/bench_dp1_python.json 2> $O/dp1_python.err; echo "dp python factored rc=$?"
+IDQN_DP_MODE=allreduce timeout -k 10 300 python bench.py --full --gpus 1 --force-dp > $O/bench_dp1_allreduce.json 2> $O/dp1_allreduce.err; echo "dp allreduce rc=$?"
 timeout -k 10 300 python bench.py --gpus 1 --heads-per-gpu 8 --steps 300 --warmup 30 > $O/bench_hp8.json 2> $O/hp8.err; echo "hp rc=$?"
 for n in 1 2 4 8; do timeout -k 10 200 python bench.py --emulate-ranks $n --steps 200 --repeats 3 > $O/bench_emulate$n.json 2> $O/emulate$n.err; echo "emulate $n rc=$?"; done
 fi
@@ -32,11 +32,11 @@ fi
 if [ $PART = all ] || [ $PART = c ]; then
 # the shipped library's second ways of issuing the same arithmetic, each against the default on THIS box
 for sw in IDQN_NONE=1 IDQN_STEP_GRAPH=1 IDQN_CONV=f32 IDQN_NONE=2; do
-  env $sw timeout -k 10 200 python bench.py --no-cpu-baseline --no-side-legs --steps 300 --repeats 3 > $O/bench_$sw.json 2> $O/bench_$sw.err; echo "$sw rc=$?"
+  env $sw timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-side-legs --steps 300 --repeats 3 > $O/bench_$sw.json 2> $O/bench_$sw.err; echo "$sw rc=$?"
 done
 for sw in IDQN_NONE=1 IDQN_CONV_PP=0; do
-  env $sw timeout -k 10 200 python bench.py --batch 256 --no-cpu-baseline --no-side-legs --steps 100 --repeats 3 > $O/bench_b256_$sw.json 2> $O/bench_b256_$sw.err; echo "b256 $sw rc=$?"
-  env $sw timeout -k 10 200 python bench.py --heads 64 --no-cpu-baseline --no-side-legs --steps 60 --repeats 3 > $O/bench_k64_$sw.json 2> $O/bench_k64_$sw.err; echo "k64 $sw rc=$?"
+  env $sw timeout -k 10 200 python bench.py --full --batch 256 --no-cpu-baseline --no-side-legs --steps 100 --repeats 3 > $O/bench_b256_$sw.json 2> $O/bench_b256_$sw.err; echo "b256 $sw rc=$?"
+  env $sw timeout -k 10 200 python bench.py --full --heads 64 --no-cpu-baseline --no-side-legs --steps 60 --repeats 3 > $O/bench_k64_$sw.json 2> $O/bench_k64_$sw.err; echo "k64 $sw rc=$?"
 done
 timeout -k 10 400 python bench.py --learner --steps 200 > $O/bench_learner.json 2> $O/bench_learner.err; echo "learner rc=$?"
 timeout -k 10 300 python tools/bench_loop.py > $O/loop_all.log 2>&1; grep -E "us per|env steps" $O/loop_all.log > $O/loop.txt
