@@ -130,6 +130,7 @@ struct StageArgs {
     PackJob job[8];
 };
 struct StageSlots { int32_t slot[256]; };  // the sampled element slots of a replay-sourced step, as kernel arguments
+struct StageSlotsDev { const int32_t* slot; };  // ... or read by the staging launch from device memory (int32 [B])
 
 // exact three-way bf16 split of two f32 values, round-to-nearest-even at every level (a plain cast: v_cvt_pk_bf16_f32,
 // which keeps a NaN a NaN).  Returns the pair packed (v0 in the low half) per plane.
@@ -212,7 +213,9 @@ int convp_launch_wgrad(const CWgradArgs& a, int NPX, int MT, int CT, int n_items
 bool convp_pair_built(int NPA, int CT, int NQ, int NT, int WNPX, int WCT, int WNTW, int WPG);
 int convp_launch_pair(const CFwdArgs& f, int NPA, int CT, int NQ, int NT, int n_f, size_t f_stage, int ring, size_t f_lds,
                       const CWgradArgs& w, int WNPX, int MT, int WCT, int n_w, size_t w_lds, hipStream_t q, long long* prof);
-int convp_launch_stage(const StageArgs& a, int n_blocks, hipStream_t q, const StageSlots* slots = nullptr);
+// replay-sourced (a.frames set): the slots come from `slots` (kernel arguments) or, when it is null, from `slots_dev`
+int convp_launch_stage(const StageArgs& a, int n_blocks, hipStream_t q, const StageSlots* slots = nullptr,
+                       const int32_t* slots_dev = nullptr);
 int convp_fwd_max_nt(int CT);
 // persistent form for launches with several items per CU (convp_pp.hip): n_wg workgroups walk n_items items
 bool convp_pp_built(int NPA, int CT, int NQ, int NT);

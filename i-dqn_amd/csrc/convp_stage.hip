@@ -135,8 +135,10 @@ __global__ __launch_bounds__(256) void k_stage(StageArgs a, SL sl) {
 
 }  // namespace
 
-int convp_launch_stage(const StageArgs& a, int n_blocks, hipStream_t q, const StageSlots* slots) {
+int convp_launch_stage(const StageArgs& a, int n_blocks, hipStream_t q, const StageSlots* slots, const int32_t* slots_dev) {
     if (a.frames && slots) hipLaunchKernelGGL((k_stage<true, StageSlots>), dim3((unsigned)n_blocks), dim3(256), 0, q, a, *slots);
+    else if (a.frames && slots_dev)  // (the same kernel: sl.slot[bg] is a load from the caller's array instead of the argument block)
+        hipLaunchKernelGGL((k_stage<true, StageSlotsDev>), dim3((unsigned)n_blocks), dim3(256), 0, q, a, StageSlotsDev{slots_dev});
     else hipLaunchKernelGGL((k_stage<false, NoSlots>), dim3((unsigned)n_blocks), dim3(256), 0, q, a, NoSlots{{0}});
     IDQN_HIP_CHECK(hipGetLastError());
     return IDQN_OK;

@@ -10,7 +10,8 @@
 // Every rank then runs the identical fused update over the gathered global batch: replicas stay bit-identical.
 // idqn_dp_step enqueues the whole schedule from C -- forward, head, Dense_0 data gradient | all-gather | conv backward |
 // all-reduce | fused Dense_0 update | Adam on the other leaves -- with the collectives on the caller's stream or on a side
-// stream of the library's own (hipEvents, no host synchronisation).  slimdqn/networks/parallel.py keeps the same schedule in
+// stream of the library's own (hipEvents, no host synchronisation).  idqn_dp_learn_on_replay runs the same schedule with the
+// shard staged from the rank's frame ring (idqn_learn_on_replay's split step) and, prioritized, gathers every shard's |TD| too.  slimdqn/networks/parallel.py keeps the same schedule in
 // Python over torch.distributed: it is the oracle of the tests (gloo on CPU, two ranks on one card) for this function.
 //
 // RCCL is resolved at run time (dlopen of librccl.so.1: in a process that imported torch this is the RCCL torch itself
@@ -172,22 +173,21 @@ extern "C" int idqn_dp_info(idqn_dp_t dp, int32_t* rank, int32_t* world, int64_t
     return IDQN_OK;
 }
 
-extern "C" int idqn_dp_step(idqn_dp_t dp, const void* state_dev, const void* next_state_dev, const int32_t* action_dev,
-                            const float* reward_dev, const uint8_t* terminal_dev, int32_t batch, int32_t global_batch,
-                            uint32_t flags, void* stream) {
-    IDQN_REQUIRE(dp, "idqn_dp_step: null handle");
-    IDQN_REQUIRE(!(flags & ~(IDQN_F_PROFILE | IDQN_F_PROFILE_ALL)), "idqn_dp_step: only the profile flags are supported");
-    IDQN_REQUIRE(global_batch == batch * dp->world, "idqn_dp_step: global batch %d is not %d ranks x %d samples (equal shards)",
-                 global_batch, dp->world, batch);
+// The factored schedule after `forward` has enqueued the step up to the Dense_0 weight gradient (IDQN_F_STOP_BEFORE_DENSE0_WGRAD).
+// td_all_dev (may be null): the shard's |TD| [K][batch] of the handle's prioritized-replay output is all-gathered into it as
+// [world][K][batch], on the collectives' stream next to the factors (the TD kernel ran before the stop point), and the compute
+// stream waits for it before the fused update: whatever the caller enqueues after the step sees the gathered errors.
+template <typename Fwd>
+static int dp_schedule(idqn_dp_t dp, Fwd&& forward, int32_t batch, float* td_all_dev, void* stream) {
     idqn_handle_t h = dp->h;
     hipStream_t q = (hipStream_t)stream;
     const bool side = dp->side != nullptr;
     hipStream_t qc = side ? dp->side : q;  // the collectives' stream
     int rc;
+    IdqnDpView v;
+    if ((rc = idqn_internal_dp_view(h, &v))) return rc;
     // forward of the 2K nets, head, TD / loss, Dense_0 data gradient (the conv backward needs it first)
-    if ((rc = idqn_learn_on_batch(h, state_dev, next_state_dev, action_dev, reward_dev, terminal_dev, batch, global_batch,
-                                  IDQN_F_STOP_BEFORE_DENSE0_WGRAD | flags, stream)))
-        return rc;
+    if ((rc = forward())) return rc;
     float* factors = nullptr;
     int64_t n_dh = 0, n_a3 = 0;
     if ((rc = idqn_dense0_factors(h, &factors, &n_dh, &n_a3))) return rc;
@@ -197,14 +197,13 @@ extern "C" int idqn_dp_step(idqn_dp_t dp, const void* state_dev, const void* nex
         IDQN_HIP_CHECK(hipMalloc((void**)&dp->gathered, (size_t)n * dp->world * 4));
         dp->gathered_cap = n * dp->world;
     }
-    IdqnDpView v;
-    if ((rc = idqn_internal_dp_view(h, &v))) return rc;
     // all-gather of [dL/dh | a3]: ONE collective for both factors, under the conv backward when it has a stream of its own
     if (side) {
         IDQN_HIP_CHECK(hipEventRecord(dp->ev_fwd, q));
         IDQN_HIP_CHECK(hipStreamWaitEvent(qc, dp->ev_fwd, 0));
     }
     IDQN_NCCL_CHECK(g_rccl.AllGather(factors, dp->gathered, (size_t)n, ncclFloat, dp->comm, qc));
+    if (td_all_dev) IDQN_NCCL_CHECK(g_rccl.AllGather(v.td_abs, td_all_dev, (size_t)v.K * batch, ncclFloat, dp->comm, qc));
     if (side) IDQN_HIP_CHECK(hipEventRecord(dp->ev_gather, qc));
     if ((rc = idqn_backward_rest(h, stream))) return rc;  // conv backward: small-leaf gradients complete in grad_dev
     // all-reduce of the small-leaf region (+ the K losses when the caller keeps them in its reserved floats)
@@ -228,4 +227,42 @@ extern "C" int idqn_dp_step(idqn_dp_t dp, const void* state_dev, const void* nex
         return rc;
     if (side) IDQN_HIP_CHECK(hipStreamWaitEvent(q, dp->ev_small, 0));
     return idqn_finish_step_factored(h, a3_all, dh_all, dp->world * nb, nb, n, nb * X, X, n, nb * Y, Y, IDQN_FACTORED_REST, stream);
+}
+
+extern "C" int idqn_dp_step(idqn_dp_t dp, const void* state_dev, const void* next_state_dev, const int32_t* action_dev,
+                            const float* reward_dev, const uint8_t* terminal_dev, int32_t batch, int32_t global_batch,
+                            uint32_t flags, void* stream) {
+    IDQN_REQUIRE(dp, "idqn_dp_step: null handle");
+    IDQN_REQUIRE(!(flags & ~(IDQN_F_PROFILE | IDQN_F_PROFILE_ALL)), "idqn_dp_step: only the profile flags are supported");
+    IDQN_REQUIRE(global_batch == batch * dp->world, "idqn_dp_step: global batch %d is not %d ranks x %d samples (equal shards)",
+                 global_batch, dp->world, batch);
+    return dp_schedule(dp, [&] {
+        return idqn_learn_on_batch(dp->h, state_dev, next_state_dev, action_dev, reward_dev, terminal_dev, batch, global_batch,
+                                   IDQN_F_STOP_BEFORE_DENSE0_WGRAD | flags, stream);
+    }, batch, nullptr, stream);
+}
+
+extern "C" int idqn_dp_learn_on_replay(idqn_dp_t dp, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
+                                       const int32_t* rows_dev, int32_t stack, const int32_t* slots_host, const int32_t* slots_dev,
+                                       int32_t batch, int32_t global_batch, float* td_all_dev, uint32_t flags, void* stream) {
+    IDQN_REQUIRE(dp, "idqn_dp_learn_on_replay: null handle");
+    IDQN_REQUIRE(!(flags & ~(IDQN_F_PROFILE | IDQN_F_PROFILE_ALL)), "idqn_dp_learn_on_replay: only the profile flags are supported");
+    IDQN_REQUIRE((slots_host != nullptr) != (slots_dev != nullptr),
+                 "idqn_dp_learn_on_replay: exactly one of slots_host / slots_dev must be set (got %s)", slots_host ? "both" : "neither");
+    IDQN_REQUIRE(global_batch == batch * dp->world,
+                 "idqn_dp_learn_on_replay: global batch %d is not %d ranks x %d samples (equal shards)", global_batch, dp->world, batch);
+    IdqnDpView v;
+    int rc = idqn_internal_dp_view(dp->h, &v);  // (a non-cnn arch or the general-shape path: refused here, before anything is enqueued)
+    if (rc) return rc;
+    IDQN_REQUIRE(!v.td_abs || td_all_dev,
+                 "idqn_dp_learn_on_replay: prioritized-replay buffers are set (idqn_set_per_buffers) but td_all_dev is null: the other "
+                 "ranks' |TD| would not be gathered");
+    IDQN_REQUIRE(v.td_abs || !td_all_dev, "idqn_dp_learn_on_replay: td_all_dev is set but the handle writes no |TD| (idqn_set_per_buffers)");
+    return dp_schedule(dp, [&] {
+        const uint32_t f = IDQN_F_STOP_BEFORE_DENSE0_WGRAD | flags;
+        return slots_dev ? idqn_learn_on_replay_dev(dp->h, frame_ring_dev, n_frames, frame_bytes, rows_dev, slots_dev, batch, stack,
+                                                    global_batch, f, stream)
+                         : idqn_learn_on_replay(dp->h, frame_ring_dev, n_frames, frame_bytes, rows_dev, slots_host, batch, stack,
+                                                global_batch, f, stream);
+    }, batch, td_all_dev, stream);
 }

@@ -5,6 +5,7 @@
 struct IdqnDpView {
     float* grad;    // gradient arena: the first n_small floats are the small-leaf region + the caller's 64 reserved floats
     float* losses;  // the K per-head losses of the last step (wherever the caller keeps them)
+    float* td_abs;  // |TD| [K][batch] output of idqn_set_per_buffers (nullptr: none set)
     long n_small;
     int K, F, J;
 };

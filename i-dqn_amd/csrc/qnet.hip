@@ -333,7 +333,8 @@ struct idqn_handle_s {
     // Two contiguous regions = two collectives in the data-parallel step.  fc: w0n = 0, gP = P.
     long gP = 0, g_w0_begin = 0, g_w0_end = 0, g_w0_base = 0;
     // replay-sourced step (idqn_learn_on_replay): set for the duration of the call, the staging launch gathers from the ring
-    struct ReplaySrc { const uint8_t* frames; const int32_t* rows; long n_frames, frame_bytes; StageSlots slots; };
+    // (slots_dev != nullptr: the slots are read from that device array and `slots` is unused)
+    struct ReplaySrc { const uint8_t* frames; const int32_t* rows; long n_frames, frame_bytes; const int32_t* slots_dev; StageSlots slots; };
     const ReplaySrc* rp = nullptr;
     int32_t* rp_action = nullptr;   // [max_batch] scalars of the sampled rows, written by the staging launch
     float* rp_reward = nullptr;
@@ -1242,7 +1243,7 @@ int planes_stage(idqn_handle_s* h, NetSet& s, const uint8_t* st, const uint8_t* 
     if (train && h->rp) {
         a.frames = h->rp->frames; a.rows = h->rp->rows; a.n_frames = h->rp->n_frames; a.frame_bytes = h->rp->frame_bytes;
         a.act_out = h->rp_action; a.rew_out = h->rp_reward; a.term_out = h->rp_terminal;
-        return convp_launch_stage(a, a.n_prep_blocks + (int)blocks, q, &h->rp->slots);
+        return convp_launch_stage(a, a.n_prep_blocks + (int)blocks, q, h->rp->slots_dev ? nullptr : &h->rp->slots, h->rp->slots_dev);
     }
     if (debug_on("IDQN_STAGE_SKIP_PIXELS")) a.n_prep_blocks = 0;  // timing probe: the launch without its pixel half (wrong results)
     return convp_launch_stage(a, a.n_prep_blocks + (int)blocks, q);
@@ -2146,19 +2147,26 @@ int iqn_heads_forward(idqn_handle_s* h, const float* const* wbase_v, int V, int 
 }
 }  // namespace
 
-// iDQN.update_online_params (idqn.py:65-72) on the HBM frame ring: replay_buffer.py:215-230's sample() fused into the step
-extern "C" int idqn_learn_on_replay(idqn_handle_t h, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
-                                    const int32_t* rows_dev, const int32_t* slots_host, int32_t batch, int32_t stack,
-                                    int32_t batch_mean_divisor, uint32_t flags, void* stream) {
-    IDQN_REQUIRE(h && frame_ring_dev && rows_dev && slots_host, "idqn_learn_on_replay: null pointer");
-    IDQN_REQUIRE(h->cfg.arch == IDQN_ARCH_CNN && h->planes && !h->gc.on, "idqn_learn_on_replay: needs the cnn arch on the plane conv path");
-    IDQN_REQUIRE(batch >= 1 && batch <= 256 && batch <= h->cfg.max_batch, "idqn_learn_on_replay: batch %d not in [1, min(256, %d)]", batch,
+// iDQN.update_online_params (idqn.py:65-72) on the HBM frame ring: replay_buffer.py:215-230's sample() fused into the step.
+// Exactly one of slots_host / slots_dev is set.
+//
+// The replay source is read by ONE launch: the staging launch of cnn_forward (planes_stage), which writes the bf16 pixel planes
+// and the sampled rows' scalars into buffers the handle owns.  Everything after it -- the TD kernel, and on a split step
+// (IDQN_F_STOP_*) the rest that idqn_backward_rest / idqn_finish_step_factored enqueue later, Conv_0's weight gradient
+// included -- reads those handle-owned copies, never the ring, the rows or the slots.  So the source can stay a stack local
+// that is dropped on return, for split steps too: the later calls have nothing of it left to read.  (The stream order still
+// matters to the CALLER: the ring must not be overwritten before the staging launch has run.)
+static int learn_on_replay(idqn_handle_t h, const char* fn, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
+                           const int32_t* rows_dev, const int32_t* slots_host, const int32_t* slots_dev, int32_t batch, int32_t stack,
+                           int32_t batch_mean_divisor, uint32_t flags, void* stream) {
+    IDQN_REQUIRE(h && frame_ring_dev && rows_dev && (slots_host || slots_dev), "%s: null pointer", fn);
+    IDQN_REQUIRE(h->cfg.arch == IDQN_ARCH_CNN && h->planes && !h->gc.on, "%s: needs the cnn arch on the plane conv path", fn);
+    IDQN_REQUIRE(batch >= 1 && batch <= 256 && batch <= h->cfg.max_batch, "%s: batch %d not in [1, min(256, %d)]", fn, batch,
                  h->cfg.max_batch);
     IDQN_REQUIRE(stack == 4 && h->cfg.obs_c == 4 && frame_bytes == (int64_t)h->cfg.obs_h * h->cfg.obs_w && frame_bytes % 16 == 0 &&
                      n_frames >= 1 && ((uintptr_t)frame_ring_dev & 15) == 0,
-                 "idqn_learn_on_replay: built for uint8 frames of obs_h x obs_w bytes (a multiple of 16), stack 4 == obs_c (got stack %d, "
-                 "frame_bytes %ld, obs %d x %d x %d)", stack, (long)frame_bytes, h->cfg.obs_h, h->cfg.obs_w, h->cfg.obs_c);
-    IDQN_REQUIRE(!(flags & (IDQN_F_STOP_AFTER_DENSE0 | IDQN_F_STOP_BEFORE_DENSE0_WGRAD)), "idqn_learn_on_replay: the IDQN_F_STOP_* flags are not supported");
+                 "%s: built for uint8 frames of obs_h x obs_w bytes (a multiple of 16), stack 4 == obs_c (got stack %d, "
+                 "frame_bytes %ld, obs %d x %d x %d)", fn, stack, (long)frame_bytes, h->cfg.obs_h, h->cfg.obs_w, h->cfg.obs_c);
     if (!h->rp_action) {
         const int mb = h->cfg.max_batch;
         float* f = nullptr;
@@ -2169,14 +2177,31 @@ extern "C" int idqn_learn_on_replay(idqn_handle_t h, const uint8_t* frame_ring_d
     }
     idqn_handle_s::ReplaySrc src;
     src.frames = frame_ring_dev; src.rows = rows_dev; src.n_frames = n_frames; src.frame_bytes = frame_bytes;
+    src.slots_dev = slots_dev;
     memset(&src.slots, 0, sizeof(src.slots));
-    memcpy(src.slots.slot, slots_host, (size_t)batch * 4);
+    if (!slots_dev) memcpy(src.slots.slot, slots_host, (size_t)batch * 4);
     h->rp = &src;
     // (the state pointers only select the staging path; the replay source replaces them)
     const int rc = idqn_learn_on_batch(h, frame_ring_dev, frame_ring_dev, h->rp_action, h->rp_reward, h->rp_terminal, batch, batch_mean_divisor,
                                        flags, stream);
-    h->rp = nullptr;
+    h->rp = nullptr;  // (see above: nothing enqueued later reads the source)
     return rc;
+}
+
+extern "C" int idqn_learn_on_replay(idqn_handle_t h, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
+                                    const int32_t* rows_dev, const int32_t* slots_host, int32_t batch, int32_t stack,
+                                    int32_t batch_mean_divisor, uint32_t flags, void* stream) {
+    IDQN_REQUIRE(slots_host, "idqn_learn_on_replay: null pointer");
+    return learn_on_replay(h, "idqn_learn_on_replay", frame_ring_dev, n_frames, frame_bytes, rows_dev, slots_host, nullptr, batch, stack,
+                           batch_mean_divisor, flags, stream);
+}
+
+extern "C" int idqn_learn_on_replay_dev(idqn_handle_t h, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
+                                        const int32_t* rows_dev, const int32_t* slots_dev, int32_t batch, int32_t stack,
+                                        int32_t batch_mean_divisor, uint32_t flags, void* stream) {
+    IDQN_REQUIRE(slots_dev, "idqn_learn_on_replay_dev: null pointer");
+    return learn_on_replay(h, "idqn_learn_on_replay_dev", frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, slots_dev, batch,
+                           stack, batch_mean_divisor, flags, stream);
 }
 
 extern "C" int idqn_iqn_learn_on_batch(idqn_handle_t h, const void* state_dev, const void* next_state_dev,
@@ -2408,7 +2433,7 @@ int idqn_internal_dp_view(idqn_handle_t h, IdqnDpView* v) {  // (csrc/dp.hip)
     IDQN_REQUIRE(h && v, "null handle");
     IDQN_REQUIRE(h->cfg.arch == IDQN_ARCH_CNN && !h->gc.on && h->cfg.n_quantiles == 0,
                  "the data-parallel step is built for the MFMA cnn path of the i-DQN heads");
-    v->grad = h->grad; v->losses = h->losses; v->n_small = (long)h->cfg.n_heads * h->gP + 64;
+    v->grad = h->grad; v->losses = h->losses; v->td_abs = h->td_abs; v->n_small = (long)h->cfg.n_heads * h->gP + 64;
     v->K = h->cfg.n_heads; v->F = h->F; v->J = h->J;
     return IDQN_OK;
 }

@@ -22,7 +22,10 @@ void idqn_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 extern "C" const char* idqn_last_error(void) { return g_err; }
-extern "C" int idqn_abi_version(void) { return 4; }  // 2: idqn_config_t.n_quantiles, the i-IQN entry points; 3: sumtree_query_host(n_live), the idqn_dp_* family; 4: idqn_learn_on_replay
+// 2: idqn_config_t.n_quantiles, the i-IQN entry points; 3: sumtree_query_host(n_live), the idqn_dp_* family; 4: idqn_learn_on_replay.
+// Still 4 after idqn_learn_on_replay_dev, idqn_dp_learn_on_replay and per_priorities_from_td_gathered, and idqn_learn_on_replay
+// accepting the IDQN_F_STOP_* flags: additions only -- no existing signature, struct or behaviour changed (backward compatible).
+extern "C" int idqn_abi_version(void) { return 4; }
 
 #define ST_THREADS 1024
 #define ST_MAX_N 4096
@@ -350,13 +353,17 @@ __global__ __launch_bounds__(1024) void k_per_weights(const double* __restrict__
 
 // priority_i = (reduce_k |td[k][i]| + eps)^alpha ; reduce = mean (0) or max (1) over the K heads; also keeps the
 // running maximum priority (the reference's `max_recorded_priority`, sum_tree.py:18,32) in max_dev[0].
-__global__ void k_per_priorities(const float* __restrict__ td_abs, int K, int n, int reduce_max, double eps,
+// td_abs is [W][K][b] (the data-parallel step's gather of every rank's [K][b]; W = 1, b = n: the single-device [K][n]);
+// priority i = r b + j of the global batch comes from rank r's sample j -- the same arithmetic in the same order either way
+__global__ void k_per_priorities(const float* __restrict__ td_abs, int K, int n, int b, int reduce_max, double eps,
                                  double alpha, double* __restrict__ out, double* __restrict__ max_dev) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    const int r = i / b, j = i - r * b;
+    const float* td = td_abs + (long)r * K * b + j;
     double acc = 0.0;
     for (int k = 0; k < K; ++k) {
-        const double v = (double)td_abs[(long)k * n + i];
+        const double v = (double)td[(long)k * b];
         acc = reduce_max ? fmax(acc, v) : acc + v;
     }
     if (!reduce_max) acc /= (double)K;
@@ -621,7 +628,19 @@ extern "C" int per_importance_weights(const double* nodes_dev, int32_t depth, in
 extern "C" int per_priorities_from_td(const float* td_abs_dev, int32_t n_heads, int32_t n, int32_t reduce_max, double eps,
                                       double alpha, double* priorities_out_dev, double* max_priority_dev, void* stream) {
     IDQN_REQUIRE(td_abs_dev && priorities_out_dev && n_heads >= 1 && n >= 1, "per_priorities_from_td: bad arguments");
-    hipLaunchKernelGGL(k_per_priorities, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, td_abs_dev, n_heads, n,
+    hipLaunchKernelGGL(k_per_priorities, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, td_abs_dev, n_heads, n, n,
+                       reduce_max, eps, alpha, priorities_out_dev, max_priority_dev);
+    IDQN_HIP_CHECK(hipGetLastError());
+    return IDQN_OK;
+}
+
+extern "C" int per_priorities_from_td_gathered(const float* td_all_dev, int32_t world, int32_t n_heads, int32_t shard,
+                                               int32_t reduce_max, double eps, double alpha, double* priorities_out_dev,
+                                               double* max_priority_dev, void* stream) {
+    IDQN_REQUIRE(td_all_dev && priorities_out_dev && world >= 1 && n_heads >= 1 && shard >= 1 && (long)world * shard <= INT32_MAX,
+                 "per_priorities_from_td_gathered: bad arguments");
+    const int n = world * shard;
+    hipLaunchKernelGGL(k_per_priorities, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, td_all_dev, n_heads, n, shard,
                        reduce_max, eps, alpha, priorities_out_dev, max_priority_dev);
     IDQN_HIP_CHECK(hipGetLastError());
     return IDQN_OK;

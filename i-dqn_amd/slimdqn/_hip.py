@@ -48,6 +48,7 @@ SYMBOLS = {
     "idqn_destroy": (C.c_int, [_P]),
     "idqn_learn_on_batch": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_uint32, _P]),
     "idqn_learn_on_replay": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, _P]),
+    "idqn_learn_on_replay_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, _P]),
     "idqn_iqn_learn_on_batch": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_uint32, _P]),
     "idqn_iqn_q_values": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P, _P]),
     "idqn_backward_rest": (C.c_int, [_P, _P]),
@@ -61,6 +62,8 @@ SYMBOLS = {
     "idqn_dp_destroy": (C.c_int, [_P]),
     "idqn_dp_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "idqn_dp_step": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_uint32, _P]),
+    "idqn_dp_learn_on_replay": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P,
+                                          C.c_uint32, _P]),
     "idqn_set_per_buffers": (C.c_int, [_P, _P, _P]),
     "sumtree_set_one": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_double, _P, _P]),
     "sampler_mailbox_create": (C.c_int, [C.c_int32, C.POINTER(_P)]),
@@ -74,6 +77,8 @@ SYMBOLS = {
     "per_sample_leaves": (C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int32, _P, _P]),
     "per_importance_weights": (C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int64, C.c_double, _P, _P]),
     "per_priorities_from_td": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P, _P, _P]),
+    "per_priorities_from_td_gathered": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P,
+                                                  _P, _P]),
     "idqn_target_update": (C.c_int, [_P, _P]),
     "idqn_target_sync": (C.c_int, [_P, _P]),
     "idqn_q_values": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P]),

@@ -128,10 +128,20 @@ int idqn_learn_on_batch(idqn_handle_t h, const void* state_dev, const void* next
  *   rows_dev        int32 [capacity][8] element rows       (replay_gather_stacked documents the row)
  *   slots_host      int32 [batch] sampled element slots (= key % capacity), HOST memory, read before the call returns
  * Restrictions (IDQN_ERR_INVALID otherwise; callers then gather and call idqn_learn_on_batch): cnn arch on the plane conv
- * path, uint8 frames with frame_bytes == obs_h * obs_w and a multiple of 16, stack == obs_c == 4, batch <= 256.            */
+ * path, uint8 frames with frame_bytes == obs_h * obs_w and a multiple of 16, stack == obs_c == 4, batch <= 256.
+ * flags as idqn_learn_on_batch, the split steps IDQN_F_STOP_AFTER_DENSE0 / IDQN_F_STOP_BEFORE_DENSE0_WGRAD included (finished by
+ * idqn_backward_rest / idqn_finish_step_factored as after idqn_learn_on_batch; bit-identical to gather-then-learn under the same
+ * flag).  Only the staging launch reads the ring, the rows and the slots: nothing of them has to outlive this call.          */
 int idqn_learn_on_replay(idqn_handle_t h, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
                          const int32_t* rows_dev, const int32_t* slots_host, int32_t batch, int32_t stack,
                          int32_t batch_mean_divisor, uint32_t flags, void* stream);
+/* The same step (idqn.py:65-72, replay_buffer.py:215-230) with the slots in DEVICE memory: slots_dev int32 [batch], read by the
+ * staging launch itself (e.g. the leaves per_sample_leaves drew, samplers.py:105-116) -- no host round trip, no gather launch.
+ * Every slot must be a valid row of rows_dev (per_importance_weights clamps sampled leaves).  Same results, bit for bit, as
+ * idqn_learn_on_replay with the same slots on the host.                                                                       */
+int idqn_learn_on_replay_dev(idqn_handle_t h, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
+                             const int32_t* rows_dev, const int32_t* slots_dev, int32_t batch, int32_t stack,
+                             int32_t batch_mean_divisor, uint32_t flags, void* stream);
 /* Data-parallel overlap: with IDQN_F_STOP_AFTER_DENSE0 (implies gradients only) idqn_learn_on_batch returns
  * once the Dense_0 weight gradient -- 98 % of the gradient bytes, produced first in the backward pass -- is queued;
  * the caller starts all-reducing that slice (RCCL, async) and calls idqn_backward_rest for the conv backward,
@@ -191,6 +201,18 @@ int idqn_dp_info(idqn_dp_t dp, int32_t* rank, int32_t* world, int64_t* gather_by
 int idqn_dp_step(idqn_dp_t dp, const void* state_dev, const void* next_state_dev, const int32_t* action_dev,
                  const float* reward_dev, const uint8_t* terminal_dev, int32_t batch, int32_t global_batch, uint32_t flags,
                  void* stream);
+/* update_online_params (idqn.py:65-72 = replay_buffer.py:215-230 sample + learn_on_batch) sharded over the ranks: idqn_dp_step's
+ * schedule with this rank's shard staged straight from its replica of the frame ring (idqn_learn_on_replay's arguments).
+ * The shard's slots are slots_host (host memory, read before the call returns) OR slots_dev (device int32 [batch]): exactly one
+ * is non-NULL.  global_batch == world * batch (equal shards); every shard divides its loss by global_batch.
+ * With prioritized-replay buffers set on the handle (idqn_set_per_buffers: the shard's weights and its |TD| [K][batch]), the
+ * shard's |TD| is also all-gathered into td_all_dev, float [world][K][batch] (per_priorities_from_td_gathered reads that
+ * layout), on the collectives' stream; the compute stream is ordered behind it.  td_all_dev must be NULL without them.
+ * IDQN_E_INVALID: global_batch != world * batch, both or neither slot pointer, td_all_dev inconsistent with the handle, a non-cnn
+ * arch or the general-shape conv path.  flags: IDQN_F_PROFILE(_ALL).                                                          */
+int idqn_dp_learn_on_replay(idqn_dp_t dp, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
+                            const int32_t* rows_dev, int32_t stack, const int32_t* slots_host, const int32_t* slots_dev,
+                            int32_t batch, int32_t global_batch, float* td_all_dev, uint32_t flags, void* stream);
 
 /* iDQN.update_target_params, T-step (idqn.py:78-80): target <- online (a REAL copy; the reference
  * aliases immutable arrays), then online[k] <- online[k+1] for k < K-1.  Adam state is not shifted. */
@@ -308,6 +330,11 @@ int per_importance_weights(const double* nodes_dev, int32_t depth, int32_t* leav
  * max_priority_dev[0] (may be NULL) keeps the running maximum (sum_tree.py:18,32 `max_recorded_priority`).           */
 int per_priorities_from_td(const float* td_abs_dev, int32_t n_heads, int32_t n, int32_t reduce_max, double eps,
                            double alpha, double* priorities_out_dev, double* max_priority_dev, void* stream);
+/* The same from the data-parallel gather td_all_dev [world][K][shard] (idqn_dp_learn_on_replay): priority i = r * shard + j of
+ * the global batch is rank r's sample j, so the output is in global-batch order, ready for ONE sumtree_set on the global
+ * leaves.  Same mean / max, eps, alpha and running maximum; world == 1 is bit-identical to per_priorities_from_td.           */
+int per_priorities_from_td_gathered(const float* td_all_dev, int32_t world, int32_t n_heads, int32_t shard, int32_t reduce_max,
+                                    double eps, double alpha, double* priorities_out_dev, double* max_priority_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Replay store in HBM (slimdqn/sample_collection/replay_buffer.py:202-230).  The store the product uses is the
