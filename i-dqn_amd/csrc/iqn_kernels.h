@@ -13,7 +13,9 @@
 //   k_iqn_d0_bwd_adam     W0 . dh (plain rows) and the Dense_0 weight gradient as GEMMs in one launch, Adam of Dense_0/kernel in the
 //                         weight gradient's epilogue (few items: k_iqn_d0_bwd with two block splits + k_iqn_d0_adam)
 //   k_iqn_embed_bwd3      dL/dpsi (summed over the N fractions) and the embedding's gradients (k_iqn_embed_grad_sum)
-// then the plain step's conv backward and small-leaf Adam.  N not a multiple of 8 / 16: the plain step's per-block Dense_0 kernels.
+// then the plain step's conv backward and small-leaf Adam.  NB not a multiple of 8 / 16: the plain step's per-block Dense_0 kernels.
+// Minibatches of nb = ceil(B / 32) > 1 sample blocks: NB = N nb blocks per virtual net, block s N + q = fraction q of sample
+// block s; the launches above take NB where they take N, the loss runs per (head, sample block).
 #pragma once
 #include "cnn_kernels.h"
 #include "iqn_gemm.h"
@@ -21,20 +23,21 @@
 constexpr int IQN_EMBED = 64;  // cos features per fraction (IQN paper, section 3; Dopamine quantile_embedding_dim)
 
 // cos(pi * i * tau), i = 1..64, evaluated in fp64 and rounded once.  tau: [K][3][N][B] (floats in
-// (0, 1)); slot = (type * K + k) * N + q.  Padded samples (b >= B) get tau = 0.5.
+// (0, 1)); slot = (type * K + k) * NB + s * N + q: fraction q of sample block s.  Padded samples (b >= B) get tau = 0.5.
 struct IqnCosArgs {
     const float* tau;
     unsigned short* cosp;  // the block as MFMA B fragments in three exact bf16 planes: cosp[slot][k-step t][plane][lane (b, h)][8]
                            // = cos feature i = 16 t + 8 h + jj of sample b (k_iqn_embed3), or nullptr
     unsigned short* cosa;  // ... and as A fragments of cos (rows = features, k = samples): cosa[slot][row tile rt][k-step t][plane]
                            // [lane (i, h)][8] = feature 32 rt + i of samples 16 t + 8 h + jj (k_iqn_embed_bwd3), or nullptr
-    int K, N, B;
+    int K, N, B, NB;       // NB = N x sample blocks: the blocks of one virtual net
 };
 __global__ __launch_bounds__(256) void k_iqn_cos(IqnCosArgs a) {
     __shared__ float ct[IQN_EMBED][33];
-    const int slot = blockIdx.x, q = slot % a.N, v = slot / a.N, type = v / a.K, k = v - type * a.K;
-    const int b = threadIdx.x & 31;
-    const double tau = b < a.B ? (double)a.tau[(((long)k * 3 + type) * a.N + q) * a.B + b] : 0.5;
+    const int slot = blockIdx.x, blk = slot % a.NB, v = slot / a.NB, type = v / a.K, k = v - type * a.K;
+    const int sb = blk / a.N, q = blk - sb * a.N;
+    const int b = threadIdx.x & 31, bg = sb * 32 + b;
+    const double tau = bg < a.B ? (double)a.tau[(((long)k * 3 + type) * a.N + q) * a.B + bg] : 0.5;
     const int g = threadIdx.x >> 5;  // this thread: features i = 8 g .. 8 g + 7 = k-step g >> 1, half g & 1
     float c[8];
 #pragma unroll
@@ -95,13 +98,14 @@ __global__ __launch_bounds__(256) void k_iqn_we_pack(IqnWePackArgs a) {
 }
 
 struct IqnEmbed3Args {
-    const unsigned short* cosp;  // [V * N][4][3][64][8]
+    const unsigned short* cosp;  // [V * NB][4][3][64][8]
     const unsigned short* wep;   // [n_packed][F / 32][4][3][64][8]
     const float* const* wbase;   // [V] (bias)
-    const float* psi;
+    const float* psi;            // [2K][nb][F][32]
     float* x;
     long be_off;
     int K, N, F, n_packed;       // virtual net v reads packed net v < n_packed ? v : v - K  (the two target sets share one)
+    int nb;                      // sample blocks; a workgroup's fraction group lies inside one of them (its size divides N)
 };
 // grid (f tiles / 4, virtual net, fraction group): a wave keeps its tile's We fragments (48 registers), psi tile and bias for the
 // fractions of its group.  The cos fragments of a fraction are copied ONCE per workgroup into LDS by LDS-DMA (the four waves of a
@@ -116,7 +120,7 @@ __global__ __launch_bounds__(256) void k_iqn_embed3l(IqnEmbed3Args a) {
     const int ft = min((int)blockIdx.x * 4 + wave, a.F / 32 - 1);  // (a wave past the last tile repeats it: same barriers)
     const bool live = (int)blockIdx.x * 4 + wave < a.F / 32;
     const int v = blockIdx.y, type = v / a.K, k = v - type * a.K;
-    const int nq = a.N / (int)gridDim.z, q0 = blockIdx.z * nq;
+    const int NB = a.N * a.nb, nq = NB / (int)gridDim.z, q0 = blockIdx.z * nq, sb = q0 / a.N;
     const int f0 = ft * 32, pv = v < a.n_packed ? v : v - a.K;
     const unsigned short* Wf = a.wep + (((long)pv * (a.F / 32) + ft) * 12) * 512 + lane * 8;
     bf16x8 wf[4][3];
@@ -124,7 +128,7 @@ __global__ __launch_bounds__(256) void k_iqn_embed3l(IqnEmbed3Args a) {
     for (int t = 0; t < 4; ++t)
 #pragma unroll
         for (int p = 0; p < 3; ++p) wf[t][p] = *reinterpret_cast<const bf16x8*>(Wf + (t * 3 + p) * 512);
-    const unsigned long cos0 = (unsigned long)(a.cosp + ((long)(v * a.N + q0) * 12) * 512);  // 12 KB per fraction
+    const unsigned long cos0 = (unsigned long)(a.cosp + ((long)(v * NB + q0) * 12) * 512);  // 12 KB per fraction
     const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)&e3_lds[0];
     auto copy = [&](int q, int buf) {  // pieces wave, wave + 4, wave + 8 of fraction q
 #pragma unroll
@@ -133,7 +137,7 @@ __global__ __launch_bounds__(256) void k_iqn_embed3l(IqnEmbed3Args a) {
     };
     copy(0, 0);
     const float* P = a.wbase[v];
-    const float* psi = a.psi + (long)((type == 0 ? 0 : a.K) + k) * a.F * 32;
+    const float* psi = a.psi + ((long)((type == 0 ? 0 : a.K) + k) * a.nb + sb) * a.F * 32;
     float be[16], ps[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
@@ -163,7 +167,7 @@ __global__ __launch_bounds__(256) void k_iqn_embed3l(IqnEmbed3Args a) {
             acc = mfma_bf16(wf[t][0], c1, acc);
             acc = mfma_bf16(wf[t][0], c0, acc);
         }
-        float* X = a.x + (long)(v * a.N + q0 + q) * a.F * 32;
+        float* X = a.x + (long)(v * NB + q0 + q) * a.F * 32;
         if (live) {
 #pragma unroll
             for (int i = 0; i < 16; ++i)
@@ -172,13 +176,13 @@ __global__ __launch_bounds__(256) void k_iqn_embed3l(IqnEmbed3Args a) {
     }
 }
 
-// Z[slot][action][b] = b1[action] + the Dense_1 chunk partials in chunk order: one workgroup per (virtual net, fraction).
+// Z[slot][action][b] = b1[action] + the Dense_1 chunk partials in chunk order: one workgroup per (virtual net, block).
 struct IqnZArgs {
     const float* qpart;         // [V * N][J / 32][32 (action)][32]
     const float* const* wbase;  // [V]
     float* z;                   // [V * N][A][32]
     long b1_off;
-    int N, NJC, A;
+    int N, NJC, A;              // N: blocks per virtual net (fractions x sample blocks)
 };
 __global__ __launch_bounds__(256) void k_iqn_z(IqnZArgs a) {
     const int slot = blockIdx.x;
@@ -195,33 +199,37 @@ __global__ __launch_bounds__(256) void k_iqn_z(IqnZArgs a) {
 }
 
 // Greedy target action, targets, quantile Huber loss and its gradient from the Z of the three virtual nets of head k.
-// One workgroup per head: thread = (sample b = t & 31, group g = t >> 5).
+// One workgroup per (head, sample block s): thread = (sample b = t & 31, group g = t >> 5); block s of a virtual net holds
+// its fractions at blocks s N .. s N + N - 1.  One sample block: the workgroup writes the head's loss itself; more: each
+// writes its partial and k_iqn_loss_sum adds them in block order.
 struct IqnLossArgs {
-    const float* z;  // [V * N][A][32]
-    int K, N, A, B, Bdiv;
+    const float* z;  // [V * nb * N][A][32]
+    int K, N, A, B, Bdiv, nb;
     const int32_t* action;
     const float* reward;
     const uint8_t* terminal;
     const float* tau;  // [K][3][N][B]
     float gamma_n;
-    float* dq;      // [K][N][A][32]  dL/dZ_online
+    float* dq;      // [K][nb * N][A][32]  dL/dZ_online
     float* losses;  // [K]
+    float* lpart;   // [K][nb]: per-block partial sums of the loss (nb > 1)
     int32_t* count;
     double* cum;
     int finish_step;
-    float* dbg;  // [K][(2 N + 32 + 1)][32]: Z_online(a) rows, Z_target(a*) rows, q_select rows (32), a* row -- tests
+    float* dbg;  // [K][(2 N + 32 + 1)][32]: Z_online(a) rows, Z_target(a*) rows, q_select rows (32), a* row of sample block 0 -- tests
     const unsigned* gate_err;  // nonzero: a bounded wait of an earlier step's fused Dense_0 update (iqn_gemm.h, IqnD0Gate) gave up -> NaN losses
 };
 __global__ __launch_bounds__(256) void k_iqn_loss(IqnLossArgs a) {
     extern __shared__ float sm[];
-    const int k = blockIdx.x, t = threadIdx.x, b = t & 31, g = t >> 5, N = a.N;
+    const int k = blockIdx.x, sb = blockIdx.y, t = threadIdx.x, b = t & 31, g = t >> 5, N = a.N, NB = N * a.nb;
+    const int bs = sb * 32 + b;  // this thread's sample in the minibatch
     float* zon = sm;             // [N][32]
     float* zval = zon + N * 32;  // [N][32]
     float* qsel = zval + N * 32; // [32][32]
     float* red = qsel + 32 * 32; // [8][32]
     __shared__ int astar[32], act[32];
-    auto zat = [&](int v, int q, int ac) { return a.z[((long)(v * N + q) * a.A + ac) * 32 + b]; };
-    if (t < 32) act[t] = t < a.B ? a.action[t] : 0;
+    auto zat = [&](int v, int q, int ac) { return a.z[((long)(v * NB + sb * N + q) * a.A + ac) * 32 + b]; };
+    if (t < 32) act[t] = bs < a.B ? a.action[bs] : 0;
     // mean over the selection fractions of the target net's Z, per action (fraction order)
     for (int ac = g; ac < a.A; ac += 8) {
         float s = 0.f;
@@ -250,13 +258,13 @@ __global__ __launch_bounds__(256) void k_iqn_loss(IqnLossArgs a) {
         zon[q * 32 + b] = zat(k, q, act[b]);
     }
     __syncthreads();
-    const bool live = b < a.B;
-    const float rew = live ? a.reward[b] : 0.f;
-    const float cont = (live && a.terminal[b]) ? 0.f : a.gamma_n;  // (1 - terminal) * gamma^n
+    const bool live = bs < a.B;
+    const float rew = live ? a.reward[bs] : 0.f;
+    const float cont = (live && a.terminal[bs]) ? 0.f : a.gamma_n;  // (1 - terminal) * gamma^n
     float lsum = 0.f;
     for (int j = g; j < N; j += 8) {
         const float z = zon[j * 32 + b];
-        const float tj = live ? a.tau[(((long)k * 3 + 0) * N + j) * a.B + b] : 0.5f;
+        const float tj = live ? a.tau[(((long)k * 3 + 0) * N + j) * a.B + bs] : 0.5f;
         float gsum = 0.f, ls = 0.f;
         for (int i = 0; i < N; ++i) {
             const float d = (rew + cont * zval[i * 32 + b]) - z;
@@ -268,11 +276,11 @@ __global__ __launch_bounds__(256) void k_iqn_loss(IqnLossArgs a) {
         lsum += ls;
         const float dz = live ? -gsum / ((float)a.Bdiv * (float)N) : 0.f;
         for (int ac = 0; ac < a.A; ++ac)
-            a.dq[(((long)k * N + j) * a.A + ac) * 32 + b] = ac == act[b] ? dz : 0.f;
+            a.dq[(((long)k * NB + sb * N + j) * a.A + ac) * 32 + b] = ac == act[b] ? dz : 0.f;
     }
     red[g * 32 + b] = live ? lsum / (float)N : 0.f;
     __syncthreads();
-    if (a.dbg) {
+    if (a.dbg && sb == 0) {
         float* D = a.dbg + (long)k * (2 * N + 33) * 32;
         for (int e = t; e < N * 32; e += 256) { D[e] = zon[e]; D[N * 32 + e] = zval[e]; }
         for (int e = t; e < 32 * 32; e += 256) D[2 * N * 32 + e] = e < a.A * 32 ? qsel[e] : 0.f;
@@ -281,9 +289,13 @@ __global__ __launch_bounds__(256) void k_iqn_loss(IqnLossArgs a) {
     if (t == 0) {
         float s = 0.f;
         for (int x = 0; x < 32; ++x) {  // sample order, then group order
-            float sb = 0.f;
-            for (int gg = 0; gg < 8; ++gg) sb += red[gg * 32 + x];
-            s += sb;
+            float sx = 0.f;
+            for (int gg = 0; gg < 8; ++gg) sx += red[gg * 32 + x];
+            s += sx;
+        }
+        if (a.nb > 1) {
+            a.lpart[k * a.nb + sb] = s;
+            return;
         }
         const float loss = s / (float)a.Bdiv;
         a.losses[k] = (a.gate_err && *a.gate_err) ? __uint_as_float(0x7fc00000u) : loss;
@@ -294,18 +306,33 @@ __global__ __launch_bounds__(256) void k_iqn_loss(IqnLossArgs a) {
     }
 }
 
-// dL/dh of every fraction block + Dense_1 / Dense_0-bias gradients.  grid = (J / 32 chunks, head).
+// The head losses from the sample blocks' partials (nb > 1): added in block order, divided by Bdiv.  One workgroup, a thread per head.
+__global__ __launch_bounds__(256) void k_iqn_loss_sum(IqnLossArgs a) {
+    for (int k = threadIdx.x; k < a.K; k += 256) {
+        float s = 0.f;
+        for (int sb = 0; sb < a.nb; ++sb) s += a.lpart[k * a.nb + sb];
+        const float loss = s / (float)a.Bdiv;
+        a.losses[k] = (a.gate_err && *a.gate_err) ? __uint_as_float(0x7fc00000u) : loss;
+        if (a.finish_step) {
+            a.count[k] += 1;
+            a.cum[k] = a.cum[k] + (double)loss;
+        }
+    }
+}
+
+// dL/dh of every block + Dense_1 / Dense_0-bias gradients.  grid = (J / 32 chunks, head).
 struct IqnDhArgs {
-    const float* hbuf;  // [V * N][J][32]
+    const float* hbuf;  // [V * N][J][32]   (N: blocks per virtual net, fractions x sample blocks)
     const float* dq;    // [K][N][A][32]
     const float* const* wbase;
     long w1_off, gP, g_b0_off, g_w1_off, g_b1_off;
     int K, N, J, A;
     float* dh;    // [K][N][J][32]
-    float* hpart; // [QG][K][J * A + J + A]: Dense_1 kernel, Dense_0 bias, Dense_1 bias gradient sums over the fractions of group qg
+    float* hpart; // [QG][K][J * A + J + A]: Dense_1 kernel, Dense_0 bias, Dense_1 bias gradient sums over the blocks of group qg
 };
-// grid = (J / 32 chunks, head, fraction group): 80 workgroups walking all N blocks in turn were one latency chain per block
-// (90 us at N = 32); the groups' gradient partials are added in group order by k_iqn_head_grad_sum.
+// grid = (J / 32 chunks, head, block group): 80 workgroups walking all N blocks in turn were one latency chain per block
+// (90 us at N = 32); the groups' gradient partials are added in group order by k_iqn_head_grad_sum.  The groups take
+// consecutive block ranges (the host makes HG x nb groups of N / HG blocks: nb = 1 is the plain fraction grouping).
 __global__ __launch_bounds__(256) void k_iqn_dh(IqnDhArgs a) {
     __shared__ float hs[32][33], dqs[32 * 32], w1s[32 * 32];
     const int jc = blockIdx.x, k = blockIdx.y, qg = blockIdx.z, t = threadIdx.x, b = t & 31, jj = t >> 5;
@@ -387,26 +414,27 @@ __global__ __launch_bounds__(256) void k_iqn_head_grad_sum(IqnHeadGradSumArgs a)
 // The same backward on the bf16 matrix cores: the recomputed embedding from the pre-split planes (k_iqn_we_pack, cosp:
 // 24 products instead of 32 f32 MFMAs of twice the length), dL/dWe from the A-fragment planes of cos (cosa) and dphi split
 // in the kernel after its trip through the per-wave LDS tile (8 split3_pk per lane and fraction): 24 products instead of
-// 32.  grid = (f tiles / 4, head, fraction group): the N fractions of a tile are dealt to gridDim.z workgroups.
+// 32.  grid = (f tiles / 4, head, sample block x fraction group): the N fractions of a sample block's tile are dealt to QG
+// workgroups; z = s QG + qg.
 struct IqnEmbedBwd3Args {
-    const unsigned short* cosp;  // [V * N][12][512]
-    const unsigned short* cosa;  // [V * N][12][512]
+    const unsigned short* cosp;  // [V * nb * N][12][512]
+    const unsigned short* cosa;  // [V * nb * N][12][512]
     const unsigned short* wep;   // [n_packed][F / 32][12][512]  (online nets first)
     const float* const* wbase;
-    const float* psi;
-    const float* dx;
-    float* dpsi;
-    float* gpart;
+    const float* psi;            // [2K][nb][F][32]
+    const float* dx;             // [K][nb * N][F][32]
+    float* dpsi;                 // [QG][K][nb][F][32]: dL/dpsi of sample block s, summed over the fractions of group qg
+    float* gpart;                // [nb * QG][K][65][F]
     long be_off;
-    int K, N, F;
+    int K, N, F, nb;
 };
 __global__ __launch_bounds__(256, 2) void k_iqn_embed_bwd3(IqnEmbedBwd3Args a) {
     __shared__ float tile[4][32][33];
     extern __shared__ __attribute__((aligned(1024))) unsigned short eb3_cs[];  // [buffer 2][cosp | cosa][12 * 512]: 48 KB (dynamic)
     unsigned short (*cs)[2][12 * 512] = reinterpret_cast<unsigned short (*)[2][12 * 512]>(eb3_cs);
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), r = lane & 31, h = lane >> 5;
-    const int k = blockIdx.y, qg = blockIdx.z;
-    const int nq = a.N / (int)gridDim.z, q_begin = qg * nq;
+    const int k = blockIdx.y, QG = (int)gridDim.z / a.nb, sb = blockIdx.z / QG, qg = blockIdx.z - sb * QG, NB = a.N * a.nb;
+    const int nq = a.N / QG, q_begin = sb * a.N + qg * nq;
     const bool live = (int)blockIdx.x * 4 + wave < a.F / 32;
     const int ft = min((int)blockIdx.x * 4 + wave, a.F / 32 - 1);
     const int f0 = ft * 32;
@@ -420,7 +448,7 @@ __global__ __launch_bounds__(256, 2) void k_iqn_embed_bwd3(IqnEmbedBwd3Args a) {
             for (int p = 0; p < 3; ++p) wf[t][p] = *reinterpret_cast<const bf16x8*>(Wf + (t * 3 + p) * 512);
     }
     float be[16], ps[16], dps[16], dbe[16];
-    const float* psi = a.psi + (long)k * a.F * 32;
+    const float* psi = a.psi + ((long)k * a.nb + sb) * a.F * 32;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
         const int f = f0 + mfma_row(i, h);
@@ -435,7 +463,7 @@ __global__ __launch_bounds__(256, 2) void k_iqn_embed_bwd3(IqnEmbedBwd3Args a) {
     const unsigned lds_cs = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned short*)&cs[0][0][0];
     // this wave's quarter of the 24 KB [cosp | cosa] of fraction q -> buffer `buf` (six 1 KB pieces)
     auto stage = [&](int q, int buf) {
-        const long slot = (long)k * a.N + q;
+        const long slot = (long)k * NB + q;
 #pragma unroll
         for (int c = 0; c < 6; ++c) {
             const int piece = wave * 6 + c, which = piece >= 12, off = (piece - 12 * which) * 512;  // shorts
@@ -445,7 +473,7 @@ __global__ __launch_bounds__(256, 2) void k_iqn_embed_bwd3(IqnEmbedBwd3Args a) {
     };
     float dxr[2][16];
     auto fetch_dx = [&](int q, int st) {
-        const float* DX = a.dx + ((long)k * a.N + q) * a.F * 32;
+        const float* DX = a.dx + ((long)k * NB + q) * a.F * 32;
 #pragma unroll
         for (int i = 0; i < 16; ++i) dxr[st][i] = DX[(long)(f0 + mfma_row(i, h)) * 32 + r];
     };
@@ -514,8 +542,8 @@ __global__ __launch_bounds__(256, 2) void k_iqn_embed_bwd3(IqnEmbedBwd3Args a) {
     }
 #undef EB3_STEP
     if (!live) return;
-    float* DP = a.dpsi + ((long)qg * a.K + k) * a.F * 32;
-    float* G = a.gpart + ((long)qg * a.K + k) * 65 * a.F;
+    float* DP = a.dpsi + (((long)qg * a.K + k) * a.nb + sb) * a.F * 32;
+    float* G = a.gpart + ((long)blockIdx.z * a.K + k) * 65 * a.F;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
         const int fl = mfma_row(i, h);
@@ -529,7 +557,7 @@ __global__ __launch_bounds__(256, 2) void k_iqn_embed_bwd3(IqnEmbedBwd3Args a) {
     }
 }
 
-// dL/dWe, dL/dbe = the fraction groups' partials added in group order -> gradient arena.  One float4 per thread.
+// dL/dWe, dL/dbe = the (sample block, fraction group) partials added in group order -> gradient arena.  One float4 per thread.
 struct IqnEmbedGradSumArgs {
     const float* gpart;  // [QG][K][65][F]
     float* grad;
@@ -551,9 +579,9 @@ __global__ __launch_bounds__(256) void k_iqn_embed_grad_sum(IqnEmbedGradSumArgs 
     *reinterpret_cast<float4*>(e < we_n ? G + a.g_we_off + e : G + a.g_be_off + (e - we_n)) = s;
 }
 
-// mean over the N fractions of Z (acting): q[a] of ONE state = lane 0 of every block.  One wave per action.
+// mean over the N fractions of Z (acting).  One workgroup per sample block s: its fractions are blocks s N .. s N + N - 1.
 struct IqnQOutArgs {
-    const float* qpart;  // [N][J / 32][32][32]
+    const float* qpart;  // [nb * N][J / 32][32][32]
     const float* params;
     long b1_off;
     int N, NJC, A, n;
@@ -562,24 +590,26 @@ struct IqnQOutArgs {
 };
 __global__ __launch_bounds__(256) void k_iqn_q_out(IqnQOutArgs a) {
     __shared__ float qs[32 * 32];
+    const int sb = blockIdx.x, n0 = sb * 32;
+    const float* Q = a.qpart + (long)sb * a.N * a.NJC * 1024;
     for (int e = threadIdx.x; e < a.A * 32; e += 256) {
         const int ac = e >> 5, b = e & 31;
         float s = 0.f;
         for (int q = 0; q < a.N; ++q) {
             float z = 0.f;
-            for (int c = 0; c < a.NJC; ++c) z += a.qpart[(((long)q * a.NJC + c) * 32 + ac) * 32 + b];
+            for (int c = 0; c < a.NJC; ++c) z += Q[(((long)q * a.NJC + c) * 32 + ac) * 32 + b];
             s += z + a.params[a.b1_off + ac];
         }
         s /= (float)a.N;
         qs[e] = s;
-        if (b < a.n) a.q_out[b * a.A + ac] = s;
+        if (n0 + b < a.n) a.q_out[(long)(n0 + b) * a.A + ac] = s;
     }
     __syncthreads();
-    if (a.action && (int)threadIdx.x < a.n) {
+    if (a.action && (int)threadIdx.x < 32 && n0 + (int)threadIdx.x < a.n) {
         int best = 0;
         float bv = qs[threadIdx.x];
         for (int ac = 1; ac < a.A; ++ac)
             if (qs[ac * 32 + threadIdx.x] > bv) { bv = qs[ac * 32 + threadIdx.x]; best = ac; }
-        a.action[threadIdx.x] = best;
+        a.action[n0 + threadIdx.x] = best;
     }
 }

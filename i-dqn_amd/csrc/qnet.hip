@@ -110,8 +110,8 @@ int build_layout(const idqn_config_t& c, Layout& L) {
     IDQN_REQUIRE(c.n_features >= 1 && c.n_features <= IDQN_MAX_FEATURES, "n_features out of range");
     IDQN_REQUIRE(c.max_batch >= 1, "max_batch must be positive");
     IDQN_REQUIRE(c.n_quantiles >= 0 && c.n_quantiles <= 64, "n_quantiles must be in [0, 64]");
-    IDQN_REQUIRE(c.n_quantiles == 0 || (c.arch == IDQN_ARCH_CNN && c.max_batch <= 32),
-                 "i-IQN heads are built for the cnn arch and minibatches of at most 32 samples");
+    IDQN_REQUIRE(c.n_quantiles == 0 || (c.arch == IDQN_ARCH_CNN && c.max_batch <= 256),
+                 "i-IQN heads are built for the cnn arch and minibatches of at most 256 samples (max_batch %d)", c.max_batch);
     long off = 0;
     char nm[32];
     if (c.arch == IDQN_ARCH_CNN && !cnn_fast_shape(c)) {
@@ -221,9 +221,10 @@ struct FwdPlan { int n_items = 0, NT = 0, ring = 2, items_per_slot = 0, r_begin[
                  int row_parts = 0, n_wg = 0; CItem* items_dev = nullptr; };  // row_parts > 0: a plan of the persistent kernel (convp_pp.hip), n_wg workgroups
 struct WgradPlan { int n_items = 0, n_chunks = 0, chunk_major = 0, MT = 0, PG = 0; size_t lds = 0; };
 
-// workspace of the i-IQN heads (iqn_kernels.h): V = 3K virtual nets x N fraction blocks
+// workspace of the i-IQN heads (iqn_kernels.h): V = 3K virtual nets x NB = N x nb blocks (fraction q of sample block s
+// at block s N + q), sized for nb_max = ceil(max_batch / 32) sample blocks
 struct IqnWs {
-    int N = 0, V = 0, NS = 2;
+    int N = 0, V = 0, NS = 2, nb_max = 1;
     const float** wbase_v = nullptr;  // dev [V]: online k | target k | target k
     unsigned short* cosa = nullptr;  // A-fragment planes of the cos blocks [V * N][12][512]
     unsigned short *cosp = nullptr, *wep = nullptr;  // bf16 fragment planes of the cos blocks [V * N][12][512] and of We [2K][F / 32][12][512]
@@ -234,8 +235,12 @@ struct IqnWs {
     int HG = 1;              // fraction groups of k_iqn_dh (partials hpart)
     float* hpart = nullptr;  // [HG][K][J * A + J + A]
     float* clk = nullptr;  // IDQN_IQN_CLOCK=1: clock stamps of the forward GEMM's workgroups [<= 1024][4] int64 (debug buffer "iqn_clk")
-    int32_t* bwd_items = nullptr;  // dispatch order of the merged Dense_0 gradient launch with Adam in its epilogue (plan_iqn_bwd_order)
-    int bwd_blocks = 0;
+    // per sample-block count nb (index nb - 1): dispatch order of the merged Dense_0 gradient launch with Adam in its epilogue
+    // (plan_iqn_bwd_order), its workgroup count, and whether the planner's makespan prefers it to the two-split launch + Adam pass
+    int32_t* bwd_items[8] = {};
+    int bwd_blocks[8] = {};
+    bool bwd_fuse[8] = {};
+    float* lpart = nullptr;  // [K][nb]: per-sample-block loss partials (k_iqn_loss, nb > 1)
     unsigned* gate = nullptr;  // [2 * K * ceil(F / 256) + 64]: IqnD0Gate (arrived, passed, err) of the fused Dense_0 update
     bool d0_adam_done = false;  // this step's merged gradient launch updated Dense_0/kernel itself
     float* g1 = nullptr;  // second partial of the Dense_0 weight gradient [K][F * J] (iqn_gemm.h), N a multiple of 16 only
@@ -444,7 +449,7 @@ int netset_alloc(idqn_handle_s* h, NetSet& s, int n_nets, int nb, int n_in_sets,
     return IDQN_OK;
 }
 
-int plan_iqn_bwd_order(idqn_handle_s* h, int forced_e);
+int plan_iqn_bwd_order(idqn_handle_s* h, int nb, int forced_e);
 int cnn_setup(idqn_handle_s* h) {
     const idqn_config_t& c = h->cfg;
     int ih = c.obs_h, iw = c.obs_w, ci = c.obs_c;
@@ -499,7 +504,8 @@ int cnn_setup(idqn_handle_s* h) {
         h->wq_stride = (off + 1023) / 1024 * 1024;
     }
     if ((rc = netset_alloc(h, h->train, 2 * K, nb, 2, ""))) return rc;
-    if ((rc = netset_alloc(h, h->infer, 1, 1, 1, "infer_", 4))) return rc;
+    // (i-IQN Q-values take up to max_batch states per call: the acting set holds that many sample blocks)
+    if ((rc = netset_alloc(h, h->infer, 1, c.n_quantiles > 0 ? nb : 1, 1, "infer_", 4))) return rc;
     if (h->planes && debug_env("IDQN_CONV_PROF")) {
         h->cprof_role = atoi(debug_env("IDQN_CONV_PROF"));
         // role 10 = the chained forward launch: one [2][4096][8] block of stamps per layer
@@ -603,13 +609,14 @@ int cnn_setup(idqn_handle_s* h) {
     if ((rc = alloc_zero(&h->slab, slab_total, h, "slab"))) return rc;
     IDQN_HIP_CHECK(hipFuncSetAttribute((const void*)k_dense0_dgrad<4>, hipFuncAttributeMaxDynamicSharedMemorySize, h->J * 32 * 4));
     IDQN_HIP_CHECK(hipFuncSetAttribute((const void*)k_dense0_dgrad<3>, hipFuncAttributeMaxDynamicSharedMemorySize, h->J * 32 * 4));
-    if (c.n_quantiles > 0) {  // i-IQN heads: V = 3K virtual nets x N fraction blocks (iqn_kernels.h)
+    if (c.n_quantiles > 0) {  // i-IQN heads: V = 3K virtual nets x N fractions x nb sample blocks (iqn_kernels.h)
         IDQN_REQUIRE(h->planes, "i-IQN heads run on the plane conv path (IDQN_CONV=bf16x3)");
         IDQN_REQUIRE(h->J % 256 == 0, "i-IQN heads: dense width %d must be a multiple of 256", h->J);
+        IDQN_REQUIRE(nb <= 8, "i-IQN heads: max_batch %d above 256", c.max_batch);
         IqnWs& w = h->iqn;
-        w.N = c.n_quantiles; w.V = 3 * K;
+        w.N = c.n_quantiles; w.V = 3 * K; w.nb_max = nb;
         w.off_we = h->L.leaves[10].offset; w.off_be = h->L.leaves[11].offset;
-        const long VN = (long)w.V * w.N, KN = (long)K * w.N;
+        const long VN = (long)w.V * w.N * nb, KN = (long)K * w.N * nb;
         IDQN_HIP_CHECK(hipMalloc((void**)&w.wbase_v, sizeof(float*) * w.V));
         h->owned.push_back((void*)w.wbase_v);
         std::vector<const float*> wv(w.V);
@@ -638,19 +645,23 @@ int cnn_setup(idqn_handle_s* h) {
         // the embedding backward deals the fractions of a feature tile to QG workgroups (a divisor of N)
         w.QG = 4;
         while (w.QG > 1 && w.N % w.QG != 0) --w.QG;
-        if ((rc = alloc_zero(&w.dpsi, (long)w.QG * K * h->F * 32, h, "iqn_dpsi"))) return rc;
-        if ((rc = alloc_zero(&w.gpart, (long)w.QG * K * 65 * h->F, h, "iqn_gpart"))) return rc;
+        if ((rc = alloc_zero(&w.dpsi, (long)w.QG * K * nb * h->F * 32, h, "iqn_dpsi"))) return rc;
+        if ((rc = alloc_zero(&w.gpart, (long)nb * w.QG * K * 65 * h->F, h, "iqn_gpart"))) return rc;
         w.HG = 8;
         while (w.HG > 1 && w.N % w.HG != 0) --w.HG;
-        if ((rc = alloc_zero(&w.hpart, (long)w.HG * K * ((long)h->J * c.n_actions + h->J + c.n_actions), h, "iqn_hpart"))) return rc;
+        if ((rc = alloc_zero(&w.hpart, (long)nb * w.HG * K * ((long)h->J * c.n_actions + h->J + c.n_actions), h, "iqn_hpart"))) return rc;
+        if ((rc = alloc_zero(&w.lpart, (long)K * nb, h, "iqn_lpart"))) return rc;
         if (debug_env("IDQN_IQN_CLOCK") && (rc = alloc_zero(&w.clk, (1024 + 256 * 8 * 2 + 512) * 2, h, "iqn_clk"))) return rc;
-        if (w.N % 16 == 0 && (rc = alloc_zero(&w.g1, (long)K * h->F * h->J, h, "iqn_g1"))) return rc;
+        bool any16 = false;  // some batch size gives a block count NB = N nb that is a multiple of 16 (the split GEMM paths)
+        for (int b = 1; b <= nb; ++b) any16 = any16 || (w.N * b) % 16 == 0;
+        if (any16 && (rc = alloc_zero(&w.g1, (long)K * h->F * h->J, h, "iqn_g1"))) return rc;
         {
             float* gw = nullptr;
             if ((rc = alloc_zero(&gw, 2L * K * cdiv(h->F, 256) + 64, h, "iqn_gate"))) return rc;
             w.gate = reinterpret_cast<unsigned*>(gw);
         }
-        if (w.N % 16 == 0 && h->J % 256 == 0 && (rc = plan_iqn_bwd_order(h, debug_int("IDQN_IQN_BWD_EARLY", -1)))) return rc;
+        for (int b = 1; b <= nb; ++b)
+            if ((w.N * b) % 16 == 0 && h->J % 256 == 0 && (rc = plan_iqn_bwd_order(h, b, debug_int("IDQN_IQN_BWD_EARLY", -1)))) return rc;
         if ((rc = alloc_zero(&w.dbg, (long)K * (2 * w.N + 33) * 32, h, "iqn_dbg"))) return rc;
     }
     h->dominant = "k_dense0_wgrad";
@@ -666,6 +677,10 @@ int cnn_setup(idqn_handle_s* h) {
 // profiles/r6_iiqn_adam_fuse.txt).  Candidates `e`: the first e groups of the XCD back to back (their long items start in the
 // first round), then every other data-gradient item, then the remaining long items together as the last round.  The candidate
 // with the smallest list-scheduled makespan on the XCD's 32 CUs, averaged over +- 8 % of the long items' length, is taken.
+// One plan per sample-block count nb (NB = N nb blocks per net: NB / 8 data-gradient items per group, weight-gradient items
+// over 32 NB rows).  For nb > 1 the same model also decides between this launch and the two-split pair k_iqn_d0_bwd +
+// k_iqn_d0_adam (half-length weight-gradient items without epilogue, list-scheduled on all CUs, plus the Adam pass as a stream
+// of 32 bytes per Dense_0 element at 4 TB/s); nb = 1 keeps its rule (fused when the items exceed one round of the chip).
 static double iqn_bwd_makespan(const std::vector<char>& seq, double dw, int ncu) {
     std::priority_queue<double, std::vector<double>, std::greater<double>> cus;
     for (int i = 0; i < ncu; ++i) cus.push(0.0);
@@ -685,13 +700,15 @@ static std::vector<char> iqn_bwd_seq(int n, int e, int nbg, int n_jh) {  // 0 = 
     s.insert(s.end(), (size_t)n_jh * (n - e), 1);
     return s;
 }
-int plan_iqn_bwd_order(idqn_handle_s* h, int forced_e) {
+int plan_iqn_bwd_order(idqn_handle_s* h, int nb, int forced_e) {
     IqnWs& w = h->iqn;
-    const int K = h->cfg.n_heads, nbg = w.N / 8, n_jh = h->J / 256, G = K * cdiv(h->F, 256), per = nbg + n_jh;
-    // lengths in units of a data-gradient item: 8 blocks x 256 rows x J against 256 x 256 x (32 N) products (measured 141 : 84 us at N = 32, J = 512) + epilogue
-    const double dw = 1.68 * (w.N / 32.0) * (512.0 / h->J) + 0.33;
+    const int NB = w.N * nb;
+    const int K = h->cfg.n_heads, nbg = NB / 8, n_jh = h->J / 256, G = K * cdiv(h->F, 256), per = nbg + n_jh;
+    // lengths in units of a data-gradient item: 8 blocks x 256 rows x J against 256 x 256 x (32 NB) products (measured 141 : 84 us at NB = 32, J = 512) + epilogue
+    const double dw = 1.68 * (NB / 32.0) * (512.0 / h->J) + 0.33;
     const int S = cdiv(G, 8) * per;
     std::vector<int32_t> items((size_t)S * 8, -1);
+    double fused = 0;  // the slowest XCD's makespan (units)
     for (int x = 0; x < 8; ++x) {
         const int n = (G - x + 7) / 8;  // groups x, x + 8, ...
         int best_e = n;
@@ -703,7 +720,8 @@ int plan_iqn_bwd_order(idqn_handle_s* h, int forced_e) {
             if (e == 0 || sum < best) { best = sum; best_e = e; }
         }
         if (forced_e >= 0) best_e = std::min(forced_e, n);
-        if (debug_on("IDQN_PLAN_PRINT") && x == 0) fprintf(stderr, "[plan] iqn dense0 gradients: %d groups on XCD 0, %d of them back to back\n", n, best_e);
+        fused = std::max(fused, iqn_bwd_makespan(iqn_bwd_seq(n, best_e, nbg, n_jh), dw, std::max(1, h->n_cus / 8)));
+        if (debug_on("IDQN_PLAN_PRINT") && x == 0) fprintf(stderr, "[plan] iqn dense0 gradients (nb %d): %d groups on XCD 0, %d of them back to back\n", nb, n, best_e);
         int s = 0;
         auto put = [&](int g, int within) { items[(size_t)(s++) * 8 + x] = ((x + 8 * g) << 8) | within; };
         for (int g = 0; g < best_e; ++g)
@@ -713,10 +731,25 @@ int plan_iqn_bwd_order(idqn_handle_s* h, int forced_e) {
         for (int g = best_e; g < n; ++g)
             for (int i = nbg; i < per; ++i) put(g, i);
     }
-    if (w.bwd_items) (void)hipFree(w.bwd_items);
-    IDQN_HIP_CHECK(hipMalloc((void**)&w.bwd_items, items.size() * 4));
-    IDQN_HIP_CHECK(hipMemcpy(w.bwd_items, items.data(), items.size() * 4, hipMemcpyHostToDevice));
-    w.bwd_blocks = (int)items.size();
+    int32_t*& dst = w.bwd_items[nb - 1];
+    if (dst) (void)hipFree(dst);
+    IDQN_HIP_CHECK(hipMalloc((void**)&dst, items.size() * 4));
+    IDQN_HIP_CHECK(hipMemcpy(dst, items.data(), items.size() * 4, hipMemcpyHostToDevice));
+    w.bwd_blocks[nb - 1] = (int)items.size();
+    const int n_d = G * nbg, n_w1 = G * n_jh;
+    if (nb == 1) {
+        w.bwd_fuse[0] = n_d + n_w1 > cu_budget();
+    } else {
+        std::vector<char> seq((size_t)n_d, 0);
+        seq.insert(seq.end(), (size_t)2 * n_w1, 1);
+        const double unit_us = 84.0 * h->J / 512.0;
+        const double adam = (double)K * h->F * h->J * 32.0 / 4.0e6 / unit_us;
+        const double split = iqn_bwd_makespan(seq, (dw - 0.33) / 2, std::max(1, h->n_cus)) + adam;
+        w.bwd_fuse[nb - 1] = fused < split;
+        if (debug_on("IDQN_PLAN_PRINT"))
+            fprintf(stderr, "[plan] iqn dense0 update (nb %d): fused %.2f vs two splits + adam %.2f units -> %s\n", nb, fused, split,
+                    w.bwd_fuse[nb - 1] ? "fused" : "two splits");
+    }
     return IDQN_OK;
 }
 
@@ -1973,6 +2006,8 @@ extern "C" int idqn_destroy(idqn_handle_t h) {
     if (h->act_stream) (void)hipStreamDestroy(h->act_stream);
     if (h->act_mail) (void)hipHostFree(h->act_mail);
     if (h->fact_planes) (void)hipFree(h->fact_planes);
+    for (int32_t* p : h->iqn.bwd_items)
+        if (p) (void)hipFree(p);
     delete h;
     return IDQN_OK;
 }
@@ -2091,19 +2126,21 @@ extern "C" int idqn_learn_on_batch(idqn_handle_t h, const void* state_dev, const
 
 // ---- i-IQN heads (extension; iqn_kernels.h, oracle/iqn_ref.py) --------------------------------------------------------
 namespace {
-// fraction blocks -> Dense_0 -> hidden + Dense_1 partials, for `V` virtual nets whose trunk features are psi [.][F * 32]
+// fraction blocks -> Dense_0 -> hidden + Dense_1 partials, for `V` virtual nets whose trunk features are psi [.][nb][F * 32]:
+// NB = N x ceil(B / 32) blocks per virtual net, block s N + q = fraction q of sample block s
 int iqn_heads_forward(idqn_handle_s* h, const float* const* wbase_v, int V, int K_for_index, const float* psi, const float* tau,
                       int B, hipStream_t q) {
     IqnWs& w = h->iqn;
+    const int nb = cdiv(B, 32), NB = w.N * nb;
     IqnCosArgs ca;
     // the embedding on the bf16 matrix cores from operands split once per step
-    ca.tau = tau; ca.cosp = w.cosp; ca.cosa = w.cosa; ca.K = K_for_index; ca.N = w.N; ca.B = B;
-    hipLaunchKernelGGL(k_iqn_cos, dim3((unsigned)(V * w.N)), dim3(256), 0, q, ca);
+    ca.tau = tau; ca.cosp = w.cosp; ca.cosa = w.cosa; ca.K = K_for_index; ca.N = w.N; ca.B = B; ca.NB = NB;
+    hipLaunchKernelGGL(k_iqn_cos, dim3((unsigned)(V * NB)), dim3(256), 0, q, ca);
     tl_mark(h, q, "iqn cos features");
     {   // fractions per wave: 8 when that still leaves >= 8 waves per SIMD to overlap, else fewer 
         int per = 8;
         while (per > 1 && (w.N % per != 0)) --per;
-        const dim3 grid((unsigned)cdiv(h->F / 32, 4), (unsigned)V, (unsigned)(w.N / per));
+        const dim3 grid((unsigned)cdiv(h->F / 32, 4), (unsigned)V, (unsigned)(NB / per));  // (per divides N: a group stays in its sample block)
         {
             const int n_packed = std::min(V, 2 * K_for_index);  // virtual nets 2K .. 3K - 1 are the target nets again
             IqnWePackArgs pa;
@@ -2112,7 +2149,7 @@ int iqn_heads_forward(idqn_handle_s* h, const float* const* wbase_v, int V, int 
             tl_mark(h, q, "iqn embedding kernel planes");
             IqnEmbed3Args e3;
             e3.cosp = w.cosp; e3.wep = w.wep; e3.wbase = wbase_v; e3.psi = psi; e3.x = w.xq; e3.be_off = w.off_be;
-            e3.K = K_for_index; e3.N = w.N; e3.F = h->F; e3.n_packed = n_packed;
+            e3.K = K_for_index; e3.N = w.N; e3.F = h->F; e3.n_packed = n_packed; e3.nb = nb;
             // cos fragments through LDS, once per workgroup
             hipLaunchKernelGGL(k_iqn_embed3l, grid, dim3(256), 2 * 12288, q, e3);
         }
@@ -2120,16 +2157,16 @@ int iqn_heads_forward(idqn_handle_s* h, const float* const* wbase_v, int V, int 
     tl_mark(h, q, "iqn embedding x features");
     DenseFwdArgs d;
     d.in = w.xq; d.part = w.part; d.wbase = wbase_v; d.w_off = h->off_w0;
-    d.n_nets = V; d.nb = w.N; d.NS = w.NS; d.n_jt = h->J / 128; d.F = h->F; d.J = h->J;
-    d.n_items = (long)V * w.N * d.NS * d.n_jt;
+    d.n_nets = V; d.nb = NB; d.NS = w.NS; d.n_jt = h->J / 128; d.F = h->F; d.J = h->J;
+    d.n_items = (long)V * NB * d.NS * d.n_jt;
     d.net_rot = 0; d.bb_inner = 0; d.nt_from = 0;
-    // >= 8 fraction blocks per net: the tiled GEMM (iqn_gemm.h; fewer, or a count that is no multiple of 8: the per-block streaming kernel of the plain step)
-    if (w.N % 8 == 0 && h->J % 256 == 0 && h->F % 16 == 0) {
+    // >= 8 blocks per net: the tiled GEMM (iqn_gemm.h; fewer, or a count that is no multiple of 8: the per-block streaming kernel of the plain step)
+    if (NB % 8 == 0 && h->J % 256 == 0 && h->F % 16 == 0) {
         IqnD0FwdArgs g;
         g.x = w.xq; g.wbase = wbase_v; g.part = w.part; g.w_off = h->off_w0;
-        g.V = V; g.nb = w.N; g.NS = w.NS; g.F = h->F; g.J = h->J; g.clk = (long long*)w.clk;
+        g.V = V; g.nb = NB; g.NS = w.NS; g.F = h->F; g.J = h->J; g.clk = (long long*)w.clk;
         const size_t lds = 2 * (size_t)IG_STAGE;
-        const dim3 grid((unsigned)(V * (w.N / 8) * w.NS * (h->J / 256)));
+        const dim3 grid((unsigned)(V * (NB / 8) * w.NS * (h->J / 256)));
         static LdsAttrMark attr;
         if (attr.needs(lds)) IDQN_HIP_CHECK(hipFuncSetAttribute((const void*)k_iqn_d0_fwd<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(k_iqn_d0_fwd<2>, grid, dim3(512), lds, q, g);
@@ -2138,9 +2175,9 @@ int iqn_heads_forward(idqn_handle_s* h, const float* const* wbase_v, int V, int 
     }
     tl_mark(h, q, "iqn dense0 fwd");
     HiddenArgs hi;
-    hi.part = w.part; hi.wbase = wbase_v; hi.b0_off = h->off_b0; hi.w1_off = h->off_w1; hi.nb = w.N; hi.NS = w.NS;
+    hi.part = w.part; hi.wbase = wbase_v; hi.b0_off = h->off_b0; hi.w1_off = h->off_w1; hi.nb = NB; hi.NS = w.NS;
     hi.J = h->J; hi.A = h->cfg.n_actions; hi.hbuf = w.hbuf; hi.qpart = w.qpart;
-    hipLaunchKernelGGL(k_hidden, dim3(h->J / 32, (unsigned)(V * w.N)), dim3(256), 0, q, hi);
+    hipLaunchKernelGGL(k_hidden, dim3(h->J / 32, (unsigned)(V * NB)), dim3(256), 0, q, hi);
     tl_mark(h, q, "iqn hidden");
     IDQN_HIP_CHECK(hipGetLastError());
     return IDQN_OK;
@@ -2210,7 +2247,8 @@ extern "C" int idqn_iqn_learn_on_batch(idqn_handle_t h, const void* state_dev, c
     IDQN_REQUIRE(h && state_dev && next_state_dev && action_dev && reward_dev && terminal_dev && tau_dev,
                  "idqn_iqn_learn_on_batch: null pointer");
     IDQN_REQUIRE(h->iqn.N > 0, "idqn_iqn_learn_on_batch: the handle was created without quantile heads (cfg.n_quantiles)");
-    IDQN_REQUIRE(batch >= 1 && batch <= 32 && batch <= h->cfg.max_batch, "idqn_iqn_learn_on_batch: batch %d not in [1, 32]", batch);
+    IDQN_REQUIRE(batch >= 1 && batch <= 256 && batch <= h->cfg.max_batch, "idqn_iqn_learn_on_batch: batch %d not in [1, min(256, %d)]",
+                 batch, h->cfg.max_batch);
     IDQN_REQUIRE(!(flags & ~(IDQN_F_PROFILE | IDQN_F_PROFILE_ALL)), "idqn_iqn_learn_on_batch: only the profile flags are supported");
     // the quantile loss has no importance weights and writes no |TD|: refuse the combination instead of leaving stale priorities
     IDQN_REQUIRE(!h->is_weight && !h->td_abs,
@@ -2218,6 +2256,7 @@ extern "C" int idqn_iqn_learn_on_batch(idqn_handle_t h, const void* state_dev, c
     hipStream_t q = (hipStream_t)stream;
     IqnWs& w = h->iqn;
     const int K = h->cfg.n_heads, A = h->cfg.n_actions;
+    const int nb = cdiv(batch, 32), NB = w.N * nb;  // blocks per virtual net: fraction q of sample block s is block s N + q
     h->pend_B = 0; h->pend_stage = 0;
     h->tl_on = (flags & IDQN_F_PROFILE_ALL) != 0;
     if (h->tl_on && h->tl_ev.empty()) {
@@ -2231,62 +2270,64 @@ extern "C" int idqn_iqn_learn_on_batch(idqn_handle_t h, const void* state_dev, c
     if ((rc = cnn_forward(h, h->train, (const uint8_t*)state_dev, (const uint8_t*)next_state_dev, batch, q, false))) return rc;
     if ((rc = iqn_heads_forward(h, w.wbase_v, w.V, K, h->train.a3, tau_dev, batch, q))) return rc;
     IqnZArgs za;
-    za.qpart = w.qpart; za.wbase = w.wbase_v; za.z = w.z; za.b1_off = h->off_b1; za.N = w.N; za.NJC = h->J / 32; za.A = A;
-    hipLaunchKernelGGL(k_iqn_z, dim3((unsigned)(w.V * w.N)), dim3(256), 0, q, za);
+    za.qpart = w.qpart; za.wbase = w.wbase_v; za.z = w.z; za.b1_off = h->off_b1; za.N = NB; za.NJC = h->J / 32; za.A = A;
+    hipLaunchKernelGGL(k_iqn_z, dim3((unsigned)(w.V * NB)), dim3(256), 0, q, za);
     tl_mark(h, q, "iqn quantile values");
     IqnLossArgs la;
-    la.z = w.z; la.K = K; la.N = w.N; la.A = A;
+    la.z = w.z; la.K = K; la.N = w.N; la.A = A; la.nb = nb; la.lpart = w.lpart;
     la.B = batch; la.Bdiv = batch; la.action = action_dev; la.reward = reward_dev; la.terminal = terminal_dev; la.tau = tau_dev;
     la.gamma_n = h->gamma_n; la.dq = w.dq; la.losses = h->losses; la.count = h->count; la.cum = h->cum; la.finish_step = 1;
     la.dbg = w.dbg; la.gate_err = w.gate + 2L * K * cdiv(h->F, 256);
-    hipLaunchKernelGGL(k_iqn_loss, dim3(K), dim3(256), (size_t)(2 * w.N * 32 + 32 * 32 + 8 * 32) * 4, q, la);
+    hipLaunchKernelGGL(k_iqn_loss, dim3(K, nb), dim3(256), (size_t)(2 * w.N * 32 + 32 * 32 + 8 * 32) * 4, q, la);
+    if (nb > 1) hipLaunchKernelGGL(k_iqn_loss_sum, dim3(1), dim3(256), 0, q, la);
     tl_mark(h, q, "iqn quantile huber loss");
     const long w0n = h->g_w0_end - h->g_w0_begin;
     IqnDhArgs da;
     da.hbuf = w.hbuf; da.dq = w.dq; da.wbase = w.wbase_v; da.w1_off = h->off_w1;
-    da.K = K; da.N = w.N; da.J = h->J; da.A = A; da.dh = w.dh; da.hpart = w.hpart;
-    hipLaunchKernelGGL(k_iqn_dh, dim3(h->J / 32, K, w.HG), dim3(256), 0, q, da);
+    da.K = K; da.N = NB; da.J = h->J; da.A = A; da.dh = w.dh; da.hpart = w.hpart;
+    const int HG = w.HG * nb;  // groups of N / HG blocks each
+    hipLaunchKernelGGL(k_iqn_dh, dim3(h->J / 32, K, HG), dim3(256), 0, q, da);
     tl_mark(h, q, "iqn dh + dense1 grads");
     {
         IqnHeadGradSumArgs hs;
         hs.hpart = w.hpart; hs.grad = h->grad; hs.gP = h->gP;
         hs.g_b0_off = h->off_b0 - w0n; hs.g_w1_off = h->off_w1 - w0n; hs.g_b1_off = h->off_b1 - w0n;
-        hs.K = K; hs.J = h->J; hs.A = A; hs.QG = w.HG;
+        hs.K = K; hs.J = h->J; hs.A = A; hs.QG = HG;
         hipLaunchKernelGGL(k_iqn_head_grad_sum, dim3((unsigned)cdiv((long)h->J * A + h->J + A, 256), K), dim3(256), 0, q, hs);
         tl_mark(h, q, "iqn head grads (group sums)");
     }
     bool wgrad_done = false;
-    {   // W0 . dh for every fraction block (plain rows)
+    {   // W0 . dh for every block (plain rows)
         DenseDgradArgs dd;
         memset(&dd, 0, sizeof(dd));
         dd.dh = w.dh; dd.raw = w.dx; dd.wbase = h->train.wbase; dd.w_off = h->off_w0;
-        dd.K = K; dd.nb = w.N; dd.n_ft = h->F / 32; dd.F = h->F; dd.J = h->J; dd.C = h->conv[2].CO; dd.g = h->gda3;
-        dd.n_items = (long)K * w.N * cdiv(dd.n_ft, 4);
-        if (w.N % 8 == 0 && h->J % 16 == 0) {
+        dd.K = K; dd.nb = NB; dd.n_ft = h->F / 32; dd.F = h->F; dd.J = h->J; dd.C = h->conv[2].CO; dd.g = h->gda3;
+        dd.n_items = (long)K * NB * cdiv(dd.n_ft, 4);
+        if (NB % 8 == 0 && h->J % 16 == 0) {
             IqnD0DgradArgs g;
-            g.dh = w.dh; g.wbase = h->train.wbase; g.dx = w.dx; g.w_off = h->off_w0; g.K = K; g.nb = w.N; g.F = h->F; g.J = h->J;
+            g.dh = w.dh; g.wbase = h->train.wbase; g.dx = w.dx; g.w_off = h->off_w0; g.K = K; g.nb = NB; g.F = h->F; g.J = h->J;
             const size_t lds = 2 * (size_t)IG_STAGE;
-            const int n_d = K * (w.N / 8) * cdiv(h->F, 256);
-            // the weight-gradient GEMM rides in the same launch
-            const int n_groups = K * cdiv(h->F, 256), n_w1 = n_groups * (h->J / 256);
+            const int n_d = K * (NB / 8) * cdiv(h->F, 256);
             w.d0_adam_done = false;
-            if (w.g1 && w.bwd_items && n_d + n_w1 > cu_budget() && debug_int("IDQN_IQN_ADAM_FUSE", 1)) {
-                // more than one round of items even with unsplit weight-gradient tiles: one split, Adam in its epilogue (k_iqn_d0_bwd_adam)
+            // the weight-gradient GEMM rides in the same launch
+            if (w.g1 && w.bwd_items[nb - 1] && w.bwd_fuse[nb - 1] && debug_int("IDQN_IQN_ADAM_FUSE", 1)) {
+                // one split, Adam in its epilogue (k_iqn_d0_bwd_adam): where the plan says it beats two splits + the Adam pass
+                const int n_groups = K * cdiv(h->F, 256);
                 IqnD0WgradArgs gw;
-                gw.x = w.xq; gw.dh = w.dh; gw.g[0] = gw.g[1] = nullptr; gw.K = K; gw.nb = w.N; gw.F = h->F; gw.J = h->J; gw.KS = 1;
+                gw.x = w.xq; gw.dh = w.dh; gw.g[0] = gw.g[1] = nullptr; gw.K = K; gw.nb = NB; gw.F = h->F; gw.J = h->J; gw.KS = 1;
                 gw.theta = debug_on("IDQN_IQN_ADAM_SKIP") ? nullptr : h->online; gw.mu = h->mu; gw.nu = h->nu; gw.bcinv = h->bcinv; gw.ad = h->ad; gw.P = h->L.head_stride; gw.w_off = h->off_w0; gw.dump = reinterpret_cast<const char*>(w.g1);  // (g1: K * F * J floats, unused on this path)
                 IqnD0Gate gate;
                 gate.arrived = w.gate; gate.passed = w.gate + n_groups; gate.err = w.gate + 2L * n_groups;
                 gate.prof = (h->cprof && h->cprof_role == 11) ? (long long*)h->cprof : nullptr;
                 static LdsAttrMark attr;
                 if (attr.needs(lds)) IDQN_HIP_CHECK(hipFuncSetAttribute((const void*)k_iqn_d0_bwd_adam<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                hipLaunchKernelGGL(k_iqn_d0_bwd_adam<2>, dim3((unsigned)w.bwd_blocks), dim3(512), lds, q, g, gw, gate, w.bwd_items);
+                hipLaunchKernelGGL(k_iqn_d0_bwd_adam<2>, dim3((unsigned)w.bwd_blocks[nb - 1]), dim3(512), lds, q, g, gw, gate, w.bwd_items[nb - 1]);
                 wgrad_done = true;
                 w.d0_adam_done = true;
-            } else if (w.g1 && w.N % 16 == 0) {
+            } else if (w.g1 && NB % 16 == 0) {
                 IqnD0WgradArgs gw;
                 memset(&gw, 0, sizeof(gw));
-                gw.x = w.xq; gw.dh = w.dh; gw.g[0] = h->grad + h->g_w0_base; gw.g[1] = w.g1; gw.K = K; gw.nb = w.N; gw.F = h->F; gw.J = h->J; gw.KS = 2;
+                gw.x = w.xq; gw.dh = w.dh; gw.g[0] = h->grad + h->g_w0_base; gw.g[1] = w.g1; gw.K = K; gw.nb = NB; gw.F = h->F; gw.J = h->J; gw.KS = 2;
                 static LdsAttrMark attr;
                 if (attr.needs(lds)) IDQN_HIP_CHECK(hipFuncSetAttribute((const void*)k_iqn_d0_bwd<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
                 hipLaunchKernelGGL(k_iqn_d0_bwd<2>, dim3((unsigned)(n_d + K * cdiv(h->F, 256) * gw.KS * (h->J / 256))), dim3(512), lds, q, g, n_d, gw);
@@ -2305,36 +2346,36 @@ extern "C" int idqn_iqn_learn_on_batch(idqn_handle_t h, const void* state_dev, c
     {  // (the forward of this step packed the embedding kernels and wrote the cos planes)
         IqnEmbedBwd3Args e3;
         e3.cosp = w.cosp; e3.cosa = w.cosa; e3.wep = w.wep; e3.wbase = w.wbase_v; e3.psi = h->train.a3; e3.dx = w.dx;
-        e3.dpsi = w.dpsi; e3.gpart = w.gpart; e3.be_off = w.off_be; e3.K = K; e3.N = w.N; e3.F = h->F;
+        e3.dpsi = w.dpsi; e3.gpart = w.gpart; e3.be_off = w.off_be; e3.K = K; e3.N = w.N; e3.F = h->F; e3.nb = nb;
         const size_t lds = 2 * 2 * 12 * 512 * 2;
         static LdsAttrMark attr;
         if (attr.needs(lds)) IDQN_HIP_CHECK(hipFuncSetAttribute((const void*)k_iqn_embed_bwd3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_iqn_embed_bwd3, dim3((unsigned)cdiv(h->F / 32, 4), K, QG), dim3(256), lds, q, e3);
+        hipLaunchKernelGGL(k_iqn_embed_bwd3, dim3((unsigned)cdiv(h->F / 32, 4), K, QG * nb), dim3(256), lds, q, e3);
     }
     tl_mark(h, q, "iqn embedding backward");
     {
         IqnEmbedGradSumArgs gs;
         gs.gpart = w.gpart; gs.grad = h->grad; gs.gP = h->gP; gs.g_we_off = w.off_we - w0n; gs.g_be_off = w.off_be - w0n;
-        gs.K = K; gs.F = h->F; gs.QG = QG;
+        gs.K = K; gs.F = h->F; gs.QG = QG * nb;
         hipLaunchKernelGGL(k_iqn_embed_grad_sum, dim3((unsigned)cdiv(65L * h->F / 4, 256), K), dim3(256), 0, q, gs);
         tl_mark(h, q, "iqn embedding grads (group sums)");
     }
-    {   // dL/dpsi (the fraction groups' partials, in group order) -> ReLU mask, bf16 planes, per-position sums: what the conv
-        // backward of the plain step reads
+    {   // dL/dpsi of every sample block (the fraction groups' partials, in group order) -> ReLU mask, bf16 planes, per-position
+        // sums: what the conv backward of the plain step reads
         Da3FinalizeArgs fa;
         fa.dpart = w.dpsi; fa.a3 = h->train.a3; fa.da3 = h->da3; fa.da3p = h->da3p; fa.pb = h->pbuf[2];
-        fa.n_rows = (long)K * h->F; fa.n_jt = QG; fa.F = h->F; fa.C = h->conv[2].CO; fa.K = K; fa.nb = 1; fa.g = h->gda3;
+        fa.n_rows = (long)K * nb * h->F; fa.n_jt = QG; fa.F = h->F; fa.C = h->conv[2].CO; fa.K = K; fa.nb = nb; fa.g = h->gda3;
         hipLaunchKernelGGL(k_da3_finalize, dim3(cdiv(fa.n_rows * 8, 256)), dim3(256), 0, q, fa);
         tl_mark(h, q, "da3 finalize (sum, mask, planes)");
     }
-    // Dense_0 weight gradient over the N fraction blocks of every head + Adam: inside the merged launch above, or as a GEMM with
-    // two block splits and one streaming Adam pass (iqn_gemm.h), or (N not a multiple of 16) the plain step's fused kernel
+    // Dense_0 weight gradient over the NB blocks of every head + Adam: inside the merged launch above, or as a GEMM with
+    // two block splits and one streaming Adam pass (iqn_gemm.h), or (NB not a multiple of 16) the plain step's fused kernel
     if (w.d0_adam_done) {
-    } else if (w.g1 && w.N % 16 == 0) {
+    } else if (w.g1 && NB % 16 == 0) {
         const long n = (long)h->F * h->J;
         IqnD0WgradArgs g;
         memset(&g, 0, sizeof(g));
-        g.x = w.xq; g.dh = w.dh; g.g[0] = h->grad + h->g_w0_base; g.g[1] = w.g1; g.K = K; g.nb = w.N; g.F = h->F; g.J = h->J; g.KS = 2;
+        g.x = w.xq; g.dh = w.dh; g.g[0] = h->grad + h->g_w0_base; g.g[1] = w.g1; g.K = K; g.nb = NB; g.F = h->F; g.J = h->J; g.KS = 2;
         const size_t lds = 2 * (size_t)IG_STAGE;
         static LdsAttrMark attr;
         if (attr.needs(lds)) IDQN_HIP_CHECK(hipFuncSetAttribute((const void*)k_iqn_d0_wgrad<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -2348,7 +2389,7 @@ extern "C" int idqn_iqn_learn_on_batch(idqn_handle_t h, const void* state_dev, c
         hipLaunchKernelGGL(k_iqn_d0_adam, dim3((unsigned)cdiv(n / 4, 256), (unsigned)K), dim3(256), 0, q, aa);
         tl_mark(h, q, "iqn dense0 adam");
         IDQN_HIP_CHECK(hipGetLastError());
-    } else if ((rc = launch_dense0_wgrad(h, w.xq, w.dh, w.N, w.N, 0, (long)w.N * h->F * 32, (long)h->F * 32, 0, (long)w.N * h->J * 32,
+    } else if ((rc = launch_dense0_wgrad(h, w.xq, w.dh, NB, NB, 0, (long)NB * h->F * 32, (long)h->F * 32, 0, (long)NB * h->J * 32,
                                   (long)h->J * 32, true, (flags & IDQN_F_PROFILE) != 0, q, false)))
         return rc;
     if ((rc = cnn_backward_rest(h, batch, true, q))) return rc;
@@ -2360,7 +2401,7 @@ extern "C" int idqn_iqn_q_values(idqn_handle_t h, int32_t which, int32_t head, c
     IDQN_REQUIRE(h && states_dev && tau_dev && q_out_dev, "idqn_iqn_q_values: null pointer");
     IDQN_REQUIRE(h->iqn.N > 0, "idqn_iqn_q_values: the handle was created without quantile heads (cfg.n_quantiles)");
     IDQN_REQUIRE(head >= 0 && head < h->cfg.n_heads && (which == 0 || which == 1), "idqn_iqn_q_values: bad head / which");
-    IDQN_REQUIRE(n >= 1 && n <= 32, "idqn_iqn_q_values: n = %d, must be in [1, 32]", n);
+    IDQN_REQUIRE(n >= 1 && n <= h->cfg.max_batch, "idqn_iqn_q_values: n = %d, must be in [1, max_batch = %d]", n, h->cfg.max_batch);
     hipStream_t q = (hipStream_t)stream;
     IqnWs& w = h->iqn;
     const float* params = (which ? h->target : h->online) + (long)head * h->L.head_stride;
@@ -2372,7 +2413,7 @@ extern "C" int idqn_iqn_q_values(idqn_handle_t h, int32_t which, int32_t head, c
     IqnQOutArgs qo;
     qo.qpart = w.qpart; qo.params = params; qo.b1_off = h->off_b1; qo.N = w.N; qo.NJC = h->J / 32; qo.A = h->cfg.n_actions;
     qo.n = n; qo.q_out = q_out_dev; qo.action = action_out_dev;
-    hipLaunchKernelGGL(k_iqn_q_out, dim3(1), dim3(256), 0, q, qo);
+    hipLaunchKernelGGL(k_iqn_q_out, dim3((unsigned)cdiv(n, 32)), dim3(256), 0, q, qo);
     IDQN_HIP_CHECK(hipGetLastError());
     return IDQN_OK;
 }

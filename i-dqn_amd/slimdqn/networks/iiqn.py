@@ -62,7 +62,7 @@ class iIQN(iDQN):
         s, s2 = self._dev(batch.state, torch.uint8), self._dev(batch.next_state, torch.uint8)
         assert tuple(s.shape[1:]) == self._obs, f"state shape {tuple(s.shape)} vs observation_dim {self._obs}"
         B = int(s.shape[0])
-        assert B <= 32, "the quantile heads take minibatches of at most 32 samples"
+        assert 1 <= B <= 256, "the quantile heads take minibatches of 1 to 256 samples"
         a = self._dev(batch.action, torch.int32)
         r = self._dev(batch.reward, torch.float32)
         t = self._dev(batch.is_terminal, torch.uint8)
@@ -99,15 +99,23 @@ class iIQN(iDQN):
             taus = rng.random((self._n_quantiles, n)).astype(np.float32)
         taus = np.ascontiguousarray(taus, np.float32)
         assert taus.shape == (self._n_quantiles, n), taus.shape
+        assert 1 <= n <= 256, "the quantile heads take 1 to 256 states per call"
+        if self._tau_act.numel() < taus.size:
+            self._tau_act = torch.zeros(taus.size, dtype=torch.float32, device="cuda")
         self._upload("tau_act", taus, self._tau_act)
-        self._ensure_handle(32)
+        self._ensure_handle(n)  # (a handle holds Q-values of up to its max_batch states)
         self._keep_q = s
-        if not hasattr(self, "_action_out"):
-            self._action_out = torch.zeros(32, dtype=torch.int32, device="cuda")
+        q_out = self._q_out  # (more than its 32 rows: a buffer of this class, grown on demand)
+        if q_out.shape[0] < n:
+            if getattr(self, "_q_out_n", None) is None or self._q_out_n.shape[0] < n:
+                self._q_out_n = torch.zeros((n, q_out.shape[1]), dtype=torch.float32, device="cuda")
+            q_out = self._q_out_n
+        if not hasattr(self, "_action_out") or self._action_out.numel() < n:
+            self._action_out = torch.zeros(max(n, 32), dtype=torch.int32, device="cuda")
         _hip.check(_hip.lib().idqn_iqn_q_values(self._handle, int(which), int(head), _hip.ptr(s), n, _hip.ptr(self._tau_act),
-                                                _hip.ptr(self._q_out), _hip.ptr(self._action_out) if want_action else None,
+                                                _hip.ptr(q_out), _hip.ptr(self._action_out) if want_action else None,
                                                 _hip.current_stream()), "idqn_iqn_q_values")
-        return self._q_out[:n]
+        return q_out[:n]
 
     def q_values(self, params, state, idx_params: int, taus=None):
         """Mean over the fractions of Z(s, tau) of head ``idx_params``: device tensor [n, A]."""

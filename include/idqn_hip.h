@@ -96,7 +96,8 @@ int idqn_destroy(idqn_handle_t h);
  * names i-IQN and points at another repository), so nothing here replaces a reference function; oracle/iqn_ref.py states
  * the algorithm (implicit quantile network, Dabney et al. 2018, on the reference's conv trunk; the reference's chain of K
  * heads, idqn.py:13-24,96-109) and parity is pinned to that restatement only.
- * One gradient step of K heads on a minibatch of batch <= 32 samples: per head N online fractions, N action-selection
+ * One gradient step of K heads on a minibatch of 1 <= batch <= min(256, max_batch) samples (a handle with n_quantiles > 0
+ * takes max_batch <= 256): per head N online fractions, N action-selection
  * fractions and N target fractions per sample, tau_dev = float32 [K][3][N][batch] in (0, 1) (the host draws them);
  * quantile Huber loss (kappa = 1), sum over the online and mean over the target fractions, mean over the batch; Adam on
  * every leaf; count += 1, losses written, cum_losses accumulated -- as idqn_learn_on_batch.  flags: IDQN_F_PROFILE / IDQN_F_PROFILE_ALL only.
@@ -104,7 +105,7 @@ int idqn_destroy(idqn_handle_t h);
 int idqn_iqn_learn_on_batch(idqn_handle_t h, const void* state_dev, const void* next_state_dev,
                             const int32_t* action_dev, const float* reward_dev, const uint8_t* terminal_dev,
                             const float* tau_dev, int32_t batch, uint32_t flags, void* stream);
-/* Acting rule of IQN for n <= 32 states: q[a] = mean over the N fractions tau_dev [N][n] of Z(s, tau)[a] of head `head`
+/* Acting rule of IQN for 1 <= n <= max_batch states: q[a] = mean over the N fractions tau_dev [N][n] of Z(s, tau)[a] of head `head`
  * (which = 0 online / 1 target) -> q_out_dev [n][A]; action_out_dev [n] (may be NULL) = argmax, first maximum on ties. */
 int idqn_iqn_q_values(idqn_handle_t h, int32_t which, int32_t head, const void* states_dev, int32_t n,
                       const float* tau_dev, float* q_out_dev, int32_t* action_out_dev, void* stream);
