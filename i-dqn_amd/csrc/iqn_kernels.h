@@ -202,6 +202,12 @@ __global__ __launch_bounds__(256) void k_iqn_z(IqnZArgs a) {
 // One workgroup per (head, sample block s): thread = (sample b = t & 31, group g = t >> 5); block s of a virtual net holds
 // its fractions at blocks s N .. s N + N - 1.  One sample block: the workgroup writes the head's loss itself; more: each
 // writes its partial and k_iqn_loss_sum adds them in block order.
+//
+// Prioritized replay (PER = true, launched when idqn_set_per_buffers has set a buffer; PER = false is the plain step, instruction
+// for instruction): with l_kb = (1 / N') sum_ij rho_ij the per-sample loss, L_k = (1 / Bdiv) sum_b w_b l_kb and dL/dZ_online of
+// sample b is scaled by w_b (the quantile form of the plain heads' loss_k = sum_b w_b td_kb^2 / divisor), and
+// td_abs[k][b] = (1 / (N' N)) sum_ij |delta_ij| is the priority signal (|TD| for N = 1).  Its partial sums of the 8 thread
+// groups meet in LDS and are added in group order; one plain store per live sample, no atomics, nothing past B.
 struct IqnLossArgs {
     const float* z;  // [V * nb * N][A][32]
     int K, N, A, B, Bdiv, nb;
@@ -217,8 +223,11 @@ struct IqnLossArgs {
     double* cum;
     int finish_step;
     float* dbg;  // [K][(2 N + 32 + 1)][32]: Z_online(a) rows, Z_target(a*) rows, q_select rows (32), a* row of sample block 0 -- tests
-    const unsigned* gate_err;  // nonzero: a bounded wait of an earlier step's fused Dense_0 update (iqn_gemm.h, IqnD0Gate) gave up -> NaN losses
+    const unsigned* gate_err;  // nonzero: a bounded wait of an earlier step's fused Dense_0 update (iqn_gemm.h, IqnD0Gate) gave up -> NaN losses (and NaN td_abs)
+    const float* is_weight;    // [B] per-sample loss weights (prioritized-replay extension) or nullptr = plain mean
+    float* td_abs;             // [K][B] out: mean |pairwise TD error| per head and sample, or nullptr
 };
+template <bool PER>
 __global__ __launch_bounds__(256) void k_iqn_loss(IqnLossArgs a) {
     extern __shared__ float sm[];
     const int k = blockIdx.x, sb = blockIdx.y, t = threadIdx.x, b = t & 31, g = t >> 5, N = a.N, NB = N * a.nb;
@@ -227,6 +236,7 @@ __global__ __launch_bounds__(256) void k_iqn_loss(IqnLossArgs a) {
     float* zval = zon + N * 32;  // [N][32]
     float* qsel = zval + N * 32; // [32][32]
     float* red = qsel + 32 * 32; // [8][32]
+    float* tdr = red + 8 * 32;   // [8][32] (PER only: the launch sizes the dynamic LDS for it)
     __shared__ int astar[32], act[32];
     auto zat = [&](int v, int q, int ac) { return a.z[((long)(v * NB + sb * N + q) * a.A + ac) * 32 + b]; };
     if (t < 32) act[t] = bs < a.B ? a.action[bs] : 0;
@@ -261,25 +271,41 @@ __global__ __launch_bounds__(256) void k_iqn_loss(IqnLossArgs a) {
     const bool live = bs < a.B;
     const float rew = live ? a.reward[bs] : 0.f;
     const float cont = (live && a.terminal[bs]) ? 0.f : a.gamma_n;  // (1 - terminal) * gamma^n
-    float lsum = 0.f;
+    float lsum = 0.f, tdsum = 0.f;
+    float wgt = 1.f;
+    if (PER) wgt = (live && a.is_weight) ? a.is_weight[bs] : 1.f;
     for (int j = g; j < N; j += 8) {
         const float z = zon[j * 32 + b];
         const float tj = live ? a.tau[(((long)k * 3 + 0) * N + j) * a.B + bs] : 0.5f;
-        float gsum = 0.f, ls = 0.f;
+        float gsum = 0.f, ls = 0.f, as = 0.f;
         for (int i = 0; i < N; ++i) {
             const float d = (rew + cont * zval[i * 32 + b]) - z;
             const float ad = fabsf(d);
             const float w = fabsf(tj - (d < 0.f ? 1.f : 0.f));
             ls += w * (ad <= 1.f ? 0.5f * d * d : ad - 0.5f);
             gsum += w * (ad <= 1.f ? d : (d > 0.f ? 1.f : -1.f));
+            if (PER) as += ad;
         }
         lsum += ls;
-        const float dz = live ? -gsum / ((float)a.Bdiv * (float)N) : 0.f;
+        if (PER) tdsum += as;
+        float dz = live ? -gsum / ((float)a.Bdiv * (float)N) : 0.f;
+        if (PER) dz *= wgt;
         for (int ac = 0; ac < a.A; ++ac)
             a.dq[(((long)k * NB + sb * N + j) * a.A + ac) * 32 + b] = ac == act[b] ? dz : 0.f;
     }
-    red[g * 32 + b] = live ? lsum / (float)N : 0.f;
+    if (PER) {
+        red[g * 32 + b] = live ? lsum / (float)N * wgt : 0.f;
+        tdr[g * 32 + b] = tdsum;
+    } else {
+        red[g * 32 + b] = live ? lsum / (float)N : 0.f;
+    }
     __syncthreads();
+    if (PER && a.td_abs && t < 32 && live) {  // group order; dead lanes write nothing
+        float sx = 0.f;
+        for (int gg = 0; gg < 8; ++gg) sx += tdr[gg * 32 + t];
+        const float v = sx / ((float)N * (float)N);
+        a.td_abs[(long)k * a.B + bs] = (a.gate_err && *a.gate_err) ? __uint_as_float(0x7fc00000u) : v;
+    }
     if (a.dbg && sb == 0) {
         float* D = a.dbg + (long)k * (2 * N + 33) * 32;
         for (int e = t; e < N * 32; e += 256) { D[e] = zon[e]; D[N * 32 + e] = zval[e]; }

@@ -2195,8 +2195,12 @@ int iqn_heads_forward(idqn_handle_s* h, const float* const* wbase_v, int V, int 
 // matters to the CALLER: the ring must not be overwritten before the staging launch has run.)
 static int learn_on_replay(idqn_handle_t h, const char* fn, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
                            const int32_t* rows_dev, const int32_t* slots_host, const int32_t* slots_dev, int32_t batch, int32_t stack,
-                           int32_t batch_mean_divisor, uint32_t flags, void* stream) {
+                           const float* tau_dev, int32_t batch_mean_divisor, uint32_t flags, void* stream) {
     IDQN_REQUIRE(h && frame_ring_dev && rows_dev && (slots_host || slots_dev), "%s: null pointer", fn);
+    if (tau_dev) {  // the quantile step (idqn_iqn_learn_on_replay*): the limits of idqn_iqn_learn_on_batch, under the caller's name
+        IDQN_REQUIRE(h->iqn.N > 0, "%s: the handle was created without quantile heads (cfg.n_quantiles)", fn);
+        IDQN_REQUIRE(!(flags & ~(IDQN_F_PROFILE | IDQN_F_PROFILE_ALL)), "%s: only the profile flags are supported", fn);
+    }
     IDQN_REQUIRE(h->cfg.arch == IDQN_ARCH_CNN && h->planes && !h->gc.on, "%s: needs the cnn arch on the plane conv path", fn);
     IDQN_REQUIRE(batch >= 1 && batch <= 256 && batch <= h->cfg.max_batch, "%s: batch %d not in [1, min(256, %d)]", fn, batch,
                  h->cfg.max_batch);
@@ -2219,8 +2223,10 @@ static int learn_on_replay(idqn_handle_t h, const char* fn, const uint8_t* frame
     if (!slots_dev) memcpy(src.slots.slot, slots_host, (size_t)batch * 4);
     h->rp = &src;
     // (the state pointers only select the staging path; the replay source replaces them)
-    const int rc = idqn_learn_on_batch(h, frame_ring_dev, frame_ring_dev, h->rp_action, h->rp_reward, h->rp_terminal, batch, batch_mean_divisor,
-                                       flags, stream);
+    const int rc = tau_dev ? idqn_iqn_learn_on_batch(h, frame_ring_dev, frame_ring_dev, h->rp_action, h->rp_reward, h->rp_terminal, tau_dev,
+                                                     batch, flags, stream)
+                           : idqn_learn_on_batch(h, frame_ring_dev, frame_ring_dev, h->rp_action, h->rp_reward, h->rp_terminal, batch,
+                                                 batch_mean_divisor, flags, stream);
     h->rp = nullptr;  // (see above: nothing enqueued later reads the source)
     return rc;
 }
@@ -2230,7 +2236,7 @@ extern "C" int idqn_learn_on_replay(idqn_handle_t h, const uint8_t* frame_ring_d
                                     int32_t batch_mean_divisor, uint32_t flags, void* stream) {
     IDQN_REQUIRE(slots_host, "idqn_learn_on_replay: null pointer");
     return learn_on_replay(h, "idqn_learn_on_replay", frame_ring_dev, n_frames, frame_bytes, rows_dev, slots_host, nullptr, batch, stack,
-                           batch_mean_divisor, flags, stream);
+                           nullptr, batch_mean_divisor, flags, stream);
 }
 
 extern "C" int idqn_learn_on_replay_dev(idqn_handle_t h, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
@@ -2238,9 +2244,29 @@ extern "C" int idqn_learn_on_replay_dev(idqn_handle_t h, const uint8_t* frame_ri
                                         int32_t batch_mean_divisor, uint32_t flags, void* stream) {
     IDQN_REQUIRE(slots_dev, "idqn_learn_on_replay_dev: null pointer");
     return learn_on_replay(h, "idqn_learn_on_replay_dev", frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, slots_dev, batch,
-                           stack, batch_mean_divisor, flags, stream);
+                           stack, nullptr, batch_mean_divisor, flags, stream);
 }
 
+// iIQN.update_online_params on the HBM frame ring: the same helper, the quantile step behind the staging launch (k_iqn_loss reads
+// action / reward / terminal from h->rp_action / rp_reward / rp_terminal like the plain TD kernel).
+extern "C" int idqn_iqn_learn_on_replay(idqn_handle_t h, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
+                                        const int32_t* rows_dev, const int32_t* slots_host, const float* tau_dev, int32_t batch,
+                                        int32_t stack, uint32_t flags, void* stream) {
+    IDQN_REQUIRE(slots_host && tau_dev, "idqn_iqn_learn_on_replay: null pointer");
+    return learn_on_replay(h, "idqn_iqn_learn_on_replay", frame_ring_dev, n_frames, frame_bytes, rows_dev, slots_host, nullptr, batch,
+                           stack, tau_dev, batch, flags, stream);
+}
+
+extern "C" int idqn_iqn_learn_on_replay_dev(idqn_handle_t h, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
+                                            const int32_t* rows_dev, const int32_t* slots_dev, const float* tau_dev, int32_t batch,
+                                            int32_t stack, uint32_t flags, void* stream) {
+    IDQN_REQUIRE(slots_dev && tau_dev, "idqn_iqn_learn_on_replay_dev: null pointer");
+    return learn_on_replay(h, "idqn_iqn_learn_on_replay_dev", frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, slots_dev, batch,
+                           stack, tau_dev, batch, flags, stream);
+}
+
+// One i-IQN gradient step (include/idqn_hip.h).  With idqn_set_per_buffers the loss launch takes the importance weights and
+// writes the per-sample mean |pairwise TD error| (k_iqn_loss<true>); without them it is the plain launch.
 extern "C" int idqn_iqn_learn_on_batch(idqn_handle_t h, const void* state_dev, const void* next_state_dev,
                                        const int32_t* action_dev, const float* reward_dev, const uint8_t* terminal_dev,
                                        const float* tau_dev, int32_t batch, uint32_t flags, void* stream) {
@@ -2250,9 +2276,6 @@ extern "C" int idqn_iqn_learn_on_batch(idqn_handle_t h, const void* state_dev, c
     IDQN_REQUIRE(batch >= 1 && batch <= 256 && batch <= h->cfg.max_batch, "idqn_iqn_learn_on_batch: batch %d not in [1, min(256, %d)]",
                  batch, h->cfg.max_batch);
     IDQN_REQUIRE(!(flags & ~(IDQN_F_PROFILE | IDQN_F_PROFILE_ALL)), "idqn_iqn_learn_on_batch: only the profile flags are supported");
-    // the quantile loss has no importance weights and writes no |TD|: refuse the combination instead of leaving stale priorities
-    IDQN_REQUIRE(!h->is_weight && !h->td_abs,
-                 "idqn_iqn_learn_on_batch: prioritized-replay buffers are set (idqn_set_per_buffers) but the quantile heads do not use them");
     hipStream_t q = (hipStream_t)stream;
     IqnWs& w = h->iqn;
     const int K = h->cfg.n_heads, A = h->cfg.n_actions;
@@ -2278,7 +2301,11 @@ extern "C" int idqn_iqn_learn_on_batch(idqn_handle_t h, const void* state_dev, c
     la.B = batch; la.Bdiv = batch; la.action = action_dev; la.reward = reward_dev; la.terminal = terminal_dev; la.tau = tau_dev;
     la.gamma_n = h->gamma_n; la.dq = w.dq; la.losses = h->losses; la.count = h->count; la.cum = h->cum; la.finish_step = 1;
     la.dbg = w.dbg; la.gate_err = w.gate + 2L * K * cdiv(h->F, 256);
-    hipLaunchKernelGGL(k_iqn_loss, dim3(K, nb), dim3(256), (size_t)(2 * w.N * 32 + 32 * 32 + 8 * 32) * 4, q, la);
+    la.is_weight = h->is_weight; la.td_abs = h->td_abs;
+    // (N <= 64: at most 22 KB of dynamic LDS with the priority reduction buffer, inside the default limit)
+    const size_t loss_lds = (size_t)(2 * w.N * 32 + 32 * 32 + 8 * 32) * 4;
+    if (la.is_weight || la.td_abs) hipLaunchKernelGGL(k_iqn_loss<true>, dim3(K, nb), dim3(256), loss_lds + 8 * 32 * 4, q, la);
+    else hipLaunchKernelGGL(k_iqn_loss<false>, dim3(K, nb), dim3(256), loss_lds, q, la);
     if (nb > 1) hipLaunchKernelGGL(k_iqn_loss_sum, dim3(1), dim3(256), 0, q, la);
     tl_mark(h, q, "iqn quantile huber loss");
     const long w0n = h->g_w0_end - h->g_w0_begin;

@@ -50,6 +50,8 @@ SYMBOLS = {
     "idqn_learn_on_replay": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, _P]),
     "idqn_learn_on_replay_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, _P]),
     "idqn_iqn_learn_on_batch": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_uint32, _P]),
+    "idqn_iqn_learn_on_replay": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, _P, C.c_int32, C.c_int32, C.c_uint32, _P]),
+    "idqn_iqn_learn_on_replay_dev": (C.c_int, [_P, _P, C.c_int64, C.c_int64, _P, _P, _P, C.c_int32, C.c_int32, C.c_uint32, _P]),
     "idqn_iqn_q_values": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P, _P]),
     "idqn_backward_rest": (C.c_int, [_P, _P]),
     "idqn_export_dense0_factors": (C.c_int, [_P, _P, _P, _P]),

@@ -210,14 +210,24 @@ class DeviceAgent:
     # materialised.  Anything else (other buffers, shapes, the f32 conv mode) samples, gathers and learns as two calls.
     fuse_replay_sampling = True
 
+    def _replay_fusable(self, rb):
+        """Buffer-side conditions of the replay-sourced step (the ring's shape is checked once the slots are drawn:
+        ``_ring_fusable``); read on every call, the environment switch included."""
+        return (self.fuse_replay_sampling and self._arch == "cnn" and hasattr(rb, "sample_slots") and hasattr(rb, "ring_view")
+                and getattr(self, "_replay_fused_ok", True) and rb._batch_size <= 256 and os.environ.get("IDQN_LEARN_ON_REPLAY", "1") != "0")
+
+    def _ring_fusable(self, ring_view):
+        _, _, frame_bytes, _, stack, fshape, fdt = ring_view
+        return (stack == 4 and self._obs[2] == 4 and tuple(fshape) == tuple(self._obs[:2]) and np.dtype(fdt) == np.uint8
+                and frame_bytes % 16 == 0)
+
     def _sample_and_learn(self, replay_buffer):
         rb = replay_buffer
-        if not (self.fuse_replay_sampling and type(self)._learn is DeviceAgent._learn and self._arch == "cnn" and hasattr(rb, "sample_slots") and hasattr(rb, "ring_view")
-                and getattr(self, "_replay_fused_ok", True) and rb._batch_size <= 256 and os.environ.get("IDQN_LEARN_ON_REPLAY", "1") != "0"):
+        if not (type(self)._learn is DeviceAgent._learn and self._replay_fusable(rb)):
             return self._learn(rb.sample())
         slots = rb.sample_slots()
-        frames, n_frames, frame_bytes, rows, stack, fshape, fdt = rb.ring_view()
-        if not (stack == 4 and self._obs[2] == 4 and tuple(fshape) == tuple(self._obs[:2]) and np.dtype(fdt) == np.uint8 and frame_bytes % 16 == 0):
+        frames, n_frames, frame_bytes, rows, stack, fshape, fdt = view = rb.ring_view()
+        if not self._ring_fusable(view):
             self._replay_fused_ok = False
             return self._learn(rb._gather(slots))
         B = int(slots.size)

@@ -57,7 +57,65 @@ class iIQN(iDQN):
         """tau [K][3][N][B] in (0, 1): online, action-selection and target fractions of every head."""
         return self._tau_rng.random((self._K, 3, self._n_quantiles, batch_size)).astype(np.float32)
 
+    def _upload_fractions(self, B, taus=None):
+        """The step's fractions [K][3][N][B] -> ``self._tau_dev`` (drawn from ``_tau_rng`` unless given)."""
+        if taus is None:
+            taus = self.sample_fractions(B)
+        taus = np.ascontiguousarray(taus, np.float32)
+        assert taus.shape == (self._K, 3, self._n_quantiles, B), taus.shape
+        if self._tau_dev is None or self._tau_dev.numel() != taus.size:
+            self._tau_dev = torch.empty(taus.size, dtype=torch.float32, device="cuda")
+        self._upload("tau", taus, self._tau_dev)
+
+    def _learn_on_replay(self, view, slots_host=None, slots_dev=None, taus=None):
+        """The step on the buffer's frame ring (``idqn_iqn_learn_on_replay`` / ``_dev``): the fractions are drawn exactly as
+        ``_learn`` draws them.  Returns the library's code; ``E_INVALID`` = this handle runs another conv path, nothing was
+        enqueued and the drawn fractions are still in ``self._tau_dev`` for the two-call step."""
+        frames, n_frames, frame_bytes, rows, stack = view[:5]
+        B = int(slots_host.size if slots_dev is None else slots_dev.numel())
+        self._upload_fractions(B, taus)
+        self._ensure_handle(B)
+        lib = _hip.lib()
+        if slots_dev is None:
+            slots_host = np.ascontiguousarray(slots_host, np.int32)
+            return lib.idqn_iqn_learn_on_replay(self._handle, _hip.ptr(frames), int(n_frames), int(frame_bytes), _hip.ptr(rows),
+                                                slots_host.ctypes.data, _hip.ptr(self._tau_dev), B, int(stack), 0,
+                                                _hip.current_stream())
+        return lib.idqn_iqn_learn_on_replay_dev(self._handle, _hip.ptr(frames), int(n_frames), int(frame_bytes), _hip.ptr(rows),
+                                                _hip.ptr(slots_dev), _hip.ptr(self._tau_dev), B, int(stack), 0,
+                                                _hip.current_stream())
+
+    def _sample_and_learn(self, replay_buffer):
+        """``update_online_params``'s step: one C call on the frame ring where the buffer and the shapes allow it (the
+        conditions of ``DeviceAgent._sample_and_learn``), else sample, gather and ``_learn``."""
+        rb = replay_buffer
+        if not self._replay_fusable(rb):
+            return self._learn(rb.sample())
+        slots = rb.sample_slots()
+        view = rb.ring_view()
+        if not self._ring_fusable(view):
+            self._replay_fused_ok = False
+            return self._learn(rb._gather(slots))
+        B = int(slots.size)
+        taus = self.sample_fractions(B)
+        rc = self._learn_on_replay(view, slots_host=slots, taus=taus)
+        if rc == _hip.E_INVALID and self.__dict__.get("_replay_fused_ok") is None:
+            # this handle runs another conv path (IDQN_CONV=f32): same slots, same fractions, two calls, from now on
+            self._replay_fused_ok = False
+            return self._learn(rb._gather(slots), taus=taus)
+        _hip.check(rc, "idqn_iqn_learn_on_replay")
+        self._replay_fused_ok = True
+        return self._losses
+
     def _learn(self, batch, flags=0, mean_divisor=None, taus=None):
+        """One gradient step of the K quantile heads on a device-resident batch.
+
+        With prioritized-replay buffers set on the handle (``idqn_set_per_buffers``, what ``PrioritizedLearner`` does):
+        weights ``w`` [B] make the loss of head k ``(1 / B) sum_b w_b l_kb`` with ``l_kb = (1 / N) sum_ij rho_ij`` the per-sample
+        quantile Huber loss (``oracle/iqn_ref.py``'s ``aux["per_sample"]``), the gradient of sample b is scaled by ``w_b``, and
+        ``td_abs[k][b] = (1 / N^2) sum_ij |delta_ij|`` -- the mean absolute pairwise TD error, |TD| for N = 1 -- is written as
+        the priority signal.  Without them the step is the plain one, bit for bit.  ``mean_divisor`` (sharded minibatches) is
+        refused: there is no data-parallel i-IQN."""
         assert mean_divisor is None, "the quantile heads have no sharded-minibatch mode"
         s, s2 = self._dev(batch.state, torch.uint8), self._dev(batch.next_state, torch.uint8)
         assert tuple(s.shape[1:]) == self._obs, f"state shape {tuple(s.shape)} vs observation_dim {self._obs}"
@@ -66,13 +124,7 @@ class iIQN(iDQN):
         a = self._dev(batch.action, torch.int32)
         r = self._dev(batch.reward, torch.float32)
         t = self._dev(batch.is_terminal, torch.uint8)
-        if taus is None:
-            taus = self.sample_fractions(B)
-        taus = np.ascontiguousarray(taus, np.float32)
-        assert taus.shape == (self._K, 3, self._n_quantiles, B), taus.shape
-        if self._tau_dev is None or self._tau_dev.numel() != taus.size:
-            self._tau_dev = torch.empty(taus.size, dtype=torch.float32, device="cuda")
-        self._upload("tau", taus, self._tau_dev)
+        self._upload_fractions(B, taus)
         self._ensure_handle(B)
         self._keep = (s, s2, a, r, t)
         _hip.check(_hip.lib().idqn_iqn_learn_on_batch(self._handle, _hip.ptr(s), _hip.ptr(s2), _hip.ptr(a), _hip.ptr(r),

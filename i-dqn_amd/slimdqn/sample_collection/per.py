@@ -15,6 +15,9 @@ Design (Schaul et al. 2016, proportional variant), all on the GPU, no host synch
   -> ``per_importance_weights`` -> ``replay_gather_stacked`` -> ``idqn_learn_on_batch`` with the weights, which also
   emits |TD| per head and sample -> ``per_priorities_from_td`` (mean or max over the K heads, ``(.+eps)^alpha``)
   -> ``sumtree_set`` on the same leaves.
+* An ``iIQN`` agent takes the same loop: the quantile loss is weighted per sample and emits the mean absolute pairwise TD
+  error per head and sample as its |TD| (``iIQN._learn``).  On a buffer with Atari-shaped uint8 frames the gather is
+  skipped: the leaves go straight to ``idqn_iqn_learn_on_replay_dev``, bit-identical to the gathered step.
 """
 import numpy as np
 
@@ -92,6 +95,17 @@ class PrioritizedLearner:
         self._td_abs = torch.zeros((K, B), dtype=torch.float32, device="cuda")
         self._priorities = torch.empty(B, dtype=torch.float64, device="cuda")
 
+    def _replay_sourced(self):
+        """The buffer's ring view for an i-IQN agent whose replay-sourced step can read it (the agent's own conditions, its
+        switches included), else None."""
+        from slimdqn.networks.iiqn import iIQN
+
+        agent, rb = self.agent, self.rb
+        if not (isinstance(agent, iIQN) and agent._replay_fusable(rb)):
+            return None
+        view = rb.ring_view()
+        return view if agent._ring_fusable(view) else None
+
     def step(self):
         """One prioritized gradient step; returns the per-head losses (device tensor, not synchronised)."""
         import torch
@@ -111,12 +125,25 @@ class PrioritizedLearner:
         _hip.check(lib.per_importance_weights(_hip.ptr(tree._nodes_dev), tree._depth, _hip.ptr(self._leaves), B,
                                               len(self.sampler), self.beta, _hip.ptr(self._weights), q),
                    "per_importance_weights")
-        batch = rb._gather_device(self._leaves)
+        # i-IQN on a fused-capable buffer: the leaves (== replay slots, already in device memory) go to the replay-sourced step
+        view = self._replay_sourced()
+        batch = rb._gather_device(self._leaves) if view is None else None
         agent._ensure_handle(B)
         _hip.check(lib.idqn_set_per_buffers(agent._handle, _hip.ptr(self._weights), _hip.ptr(self._td_abs)),
                    "idqn_set_per_buffers")
         try:
-            losses = agent._learn(batch)
+            if view is None:
+                losses = agent._learn(batch)
+            else:
+                taus = agent.sample_fractions(B)
+                rc = agent._learn_on_replay(view, slots_dev=self._leaves, taus=taus)
+                if rc == _hip.E_INVALID and agent.__dict__.get("_replay_fused_ok") is None:
+                    agent._replay_fused_ok = False  # another conv path: gathered steps from now on, same leaves and fractions
+                    losses = agent._learn(rb._gather_device(self._leaves), taus=taus)
+                else:
+                    _hip.check(rc, "idqn_iqn_learn_on_replay_dev")
+                    agent._replay_fused_ok = True
+                    losses = agent._losses
         finally:
             _hip.check(lib.idqn_set_per_buffers(agent._handle, None, None), "idqn_set_per_buffers")
         _hip.check(lib.per_priorities_from_td(_hip.ptr(self._td_abs), agent._K, B, self.reduce_max, self.eps,

@@ -101,7 +101,11 @@ int idqn_destroy(idqn_handle_t h);
  * fractions and N target fractions per sample, tau_dev = float32 [K][3][N][batch] in (0, 1) (the host draws them);
  * quantile Huber loss (kappa = 1), sum over the online and mean over the target fractions, mean over the batch; Adam on
  * every leaf; count += 1, losses written, cum_losses accumulated -- as idqn_learn_on_batch.  flags: IDQN_F_PROFILE / IDQN_F_PROFILE_ALL only.
- * Refused (IDQN_ERR_*) while idqn_set_per_buffers has buffers set: the quantile loss takes no importance weights. */
+ * With idqn_set_per_buffers: weights w float32 [batch] make the loss of head k (1 / batch) sum_b w_b l_kb, where
+ * l_kb = (1 / N) sum_ij rho_ij is the per-sample quantile Huber loss, and scale dL/dZ_online of sample b by w_b (the quantile
+ * form of loss_k = sum_b w_b td_kb^2 / divisor); td_abs_out [K][batch] receives (1 / N^2) sum_ij |delta_ij|, the mean absolute
+ * pairwise TD error (|TD| for N = 1; per_priorities_from_td reads it unchanged).  Either pointer may be NULL; with both NULL the
+ * step is the plain one, bit for bit.  A step whose losses are NaN (a gave-up wait of the fused Dense_0 update) writes NaN there. */
 int idqn_iqn_learn_on_batch(idqn_handle_t h, const void* state_dev, const void* next_state_dev,
                             const int32_t* action_dev, const float* reward_dev, const uint8_t* terminal_dev,
                             const float* tau_dev, int32_t batch, uint32_t flags, void* stream);
@@ -143,6 +147,20 @@ int idqn_learn_on_replay(idqn_handle_t h, const uint8_t* frame_ring_dev, int64_t
 int idqn_learn_on_replay_dev(idqn_handle_t h, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
                              const int32_t* rows_dev, const int32_t* slots_dev, int32_t batch, int32_t stack,
                              int32_t batch_mean_divisor, uint32_t flags, void* stream);
+/* The i-IQN step on the HBM frame ring: replay_gather_stacked + idqn_iqn_learn_on_batch as ONE call, the way idqn_learn_on_replay
+ * fuses the plain step.  Arguments frame_ring_dev .. stack as idqn_learn_on_replay (slots_host: HOST memory, read before the call
+ * returns), tau_dev as idqn_iqn_learn_on_batch.  Same results, bit for bit, as the gather followed by idqn_iqn_learn_on_batch on
+ * its outputs, importance weights and td_abs of idqn_set_per_buffers included.  Only the staging launch reads the ring, the rows
+ * and the slots.  Restrictions (IDQN_E_INVALID otherwise): those of idqn_learn_on_replay plus those of idqn_iqn_learn_on_batch
+ * -- a handle with n_quantiles > 0, batch <= min(256, max_batch), flags IDQN_F_PROFILE / IDQN_F_PROFILE_ALL only.          */
+int idqn_iqn_learn_on_replay(idqn_handle_t h, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
+                             const int32_t* rows_dev, const int32_t* slots_host, const float* tau_dev, int32_t batch,
+                             int32_t stack, uint32_t flags, void* stream);
+/* The same step with the slots in DEVICE memory (slots_dev int32 [batch], e.g. the leaves per_sample_leaves drew); bit-identical
+ * to idqn_iqn_learn_on_replay with the same slots on the host.                                                              */
+int idqn_iqn_learn_on_replay_dev(idqn_handle_t h, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
+                                 const int32_t* rows_dev, const int32_t* slots_dev, const float* tau_dev, int32_t batch,
+                                 int32_t stack, uint32_t flags, void* stream);
 /* Data-parallel overlap: with IDQN_F_STOP_AFTER_DENSE0 (implies gradients only) idqn_learn_on_batch returns
  * once the Dense_0 weight gradient -- 98 % of the gradient bytes, produced first in the backward pass -- is queued;
  * the caller starts all-reducing that slice (RCCL, async) and calls idqn_backward_rest for the conv backward,
