@@ -21,6 +21,7 @@
 #include <tuple>
 
 #include "act_kernels.h"
+#include "iqn_act_kernels.h"
 #include "cnn_kernels.h"
 #include "fc_kernels.h"
 #include "fc_par_kernels.h"
@@ -294,6 +295,9 @@ struct idqn_handle_s {
     std::map<std::tuple<const void*, const void*, const void*, const void*, const void*, int, int, const void*, const void*>,
              std::pair<int, hipGraphExec_t>> step_graphs;
     std::map<std::tuple<int, const void*, void*, void*>, hipGraphExec_t> act_graphs;  // (net, host state, q out, host action)
+    // idqn_iqn_act_host (iqn_act_kernels.h): fractions, their cosines [N][64], x [F][NP], Dense_0 partials [NRG][J / 32][2][NP][16]
+    float *iact_tau = nullptr, *iact_cos = nullptr, *iact_x = nullptr, *iact_part = nullptr;
+    std::map<std::tuple<int, const void*, const void*, void*, void*>, hipGraphExec_t> iact_graphs;  // (net, state, fractions, q out, action)
     const float* infer_pbase = nullptr;  // parameter base of the net the last idqn_q_values call evaluated
     float *infer_hbuf = nullptr, *infer_qpart = nullptr;  // k_hidden outputs of the single inference net
     float* wt[3] = {nullptr, nullptr, nullptr};  // transformed weights of the Conv_1 / Conv_2 data gradients
@@ -2001,6 +2005,7 @@ extern "C" int idqn_destroy(idqn_handle_t h) {
     for (auto& e : h->tl_ev)
         if (e) (void)hipEventDestroy(e);
     for (auto& g : h->act_graphs) (void)hipGraphExecDestroy(g.second);
+    for (auto& g : h->iact_graphs) (void)hipGraphExecDestroy(g.second);
     for (auto& g : h->step_graphs)
         if (g.second.second) (void)hipGraphExecDestroy(g.second.second);
     if (h->act_stream) (void)hipStreamDestroy(h->act_stream);
@@ -2566,6 +2571,31 @@ __global__ void k_argmax_rows(const float* __restrict__ q, int n, int A, int32_t
     }
 }
 
+// psi(s) of ONE state on the latency path (act_kernels.h): three k_act_conv launches, pixels and HWIO leaves as they are;
+// the F features are left in h->act_a[2] in the order Dense_0's rows expect.
+static int act_trunk(idqn_handle_t h, const float* params, const void* states_dev, hipStream_t q) {
+    const float* in = nullptr;
+    int ih = h->cfg.obs_h, iw = h->cfg.obs_w;
+    for (int i = 0; i < 3; ++i) {
+        const ConvL& l = h->conv[i];
+        ActConvArgs a;
+        a.in_u8 = i == 0 ? (const uint8_t*)states_dev : nullptr; a.in = in; a.params = params; a.out = h->act_a[i];
+        a.w_off = l.w_off; a.b_off = l.b_off; a.IH = ih; a.IW = iw; a.CI = l.CI; a.OH = l.OH; a.OW = l.OW; a.CO = l.CO;
+        a.K = l.K; a.S = l.S; a.PLh = l.PLh; a.PLw = l.PLw;
+        a.KS = i == 0 ? 8 : 16;  // lane slices: layer 0 has 64 units of 4 channels, the others K*K*CI/32 units of 32
+        const int per = 256 / a.KS;
+        const dim3 grid(cdiv((long)l.OH * l.OW * l.CO, per));
+        const int units = l.K * l.K * (l.CI % 32 == 0 ? l.CI / 32 : l.CI / 4), upt = cdiv(units, a.KS);
+        IDQN_REQUIRE(l.CI % 32 == 0 || (l.CI == 4 && upt <= 8), "acting path: Conv_%d has %d input channels", i, l.CI);
+        if (l.CI % 32 != 0) hipLaunchKernelGGL((k_act_conv<4, 8>), grid, dim3(256), 0, q, a);
+        else if (upt <= 1) hipLaunchKernelGGL((k_act_conv<32, 1>), grid, dim3(256), 0, q, a);
+        else if (upt <= 2) hipLaunchKernelGGL((k_act_conv<32, 2>), grid, dim3(256), 0, q, a);
+        else { IDQN_REQUIRE(upt <= 4, "acting path: %d units per lane slice", upt); hipLaunchKernelGGL((k_act_conv<32, 4>), grid, dim3(256), 0, q, a); }
+        in = h->act_a[i]; ih = l.OH; iw = l.OW;
+    }
+    return IDQN_OK;
+}
+
 static int q_values_impl(idqn_handle_t h, int32_t which, int32_t head, const void* states_dev, int32_t n,
                          float* q_out_dev, int32_t* action_out_dev, void* stream) {
     IDQN_REQUIRE(h && states_dev && q_out_dev, "idqn_q_values: null pointer");
@@ -2588,25 +2618,8 @@ static int q_values_impl(idqn_handle_t h, int32_t which, int32_t head, const voi
     }
     if (h->cfg.arch == IDQN_ARCH_CNN && n == 1 && !act_generic() && h->J <= 512 && h->cfg.n_actions <= 32) {
         // one state: the latency path (act_kernels.h) -- pixels and parameter leaves as they are, five small launches
-        const float* in = nullptr;
-        int ih = h->cfg.obs_h, iw = h->cfg.obs_w;
-        for (int i = 0; i < 3; ++i) {
-            const ConvL& l = h->conv[i];
-            ActConvArgs a;
-            a.in_u8 = i == 0 ? (const uint8_t*)states_dev : nullptr; a.in = in; a.params = params; a.out = h->act_a[i];
-            a.w_off = l.w_off; a.b_off = l.b_off; a.IH = ih; a.IW = iw; a.CI = l.CI; a.OH = l.OH; a.OW = l.OW; a.CO = l.CO;
-            a.K = l.K; a.S = l.S; a.PLh = l.PLh; a.PLw = l.PLw;
-            a.KS = i == 0 ? 8 : 16;  // lane slices: layer 0 has 64 units of 4 channels, the others K*K*CI/32 units of 32
-            const int per = 256 / a.KS;
-            const dim3 grid(cdiv((long)l.OH * l.OW * l.CO, per));
-            const int units = l.K * l.K * (l.CI % 32 == 0 ? l.CI / 32 : l.CI / 4), upt = cdiv(units, a.KS);
-            IDQN_REQUIRE(l.CI % 32 == 0 || (l.CI == 4 && upt <= 8), "acting path: Conv_%d has %d input channels", i, l.CI);
-            if (l.CI % 32 != 0) hipLaunchKernelGGL((k_act_conv<4, 8>), grid, dim3(256), 0, q, a);
-            else if (upt <= 1) hipLaunchKernelGGL((k_act_conv<32, 1>), grid, dim3(256), 0, q, a);
-            else if (upt <= 2) hipLaunchKernelGGL((k_act_conv<32, 2>), grid, dim3(256), 0, q, a);
-            else { IDQN_REQUIRE(upt <= 4, "acting path: %d units per lane slice", upt); hipLaunchKernelGGL((k_act_conv<32, 4>), grid, dim3(256), 0, q, a); }
-            in = h->act_a[i]; ih = l.OH; iw = l.OW;
-        }
+        int rc = act_trunk(h, params, states_dev, q);
+        if (rc) return rc;
         ActDenseArgs d;
         d.a3 = h->act_a[2]; d.params = params; d.part = h->act_part; d.w_off = h->off_w0; d.F = h->F; d.J = h->J;
         d.NRG = std::max(1, 256 / (h->J / 128));  // one workgroup per CU
@@ -2659,16 +2672,49 @@ extern "C" int idqn_best_action(idqn_handle_t h, int32_t which, int32_t head, co
     return q_values_impl(h, which, head, states_dev, n, q_out_dev, action_out_dev, stream);
 }
 
+// The i-IQN chain behind idqn_iqn_act_host for the state in h->act_state and the fractions in h->iact_tau: cosines,
+// trunk, embedding, Dense_0 partials, head (iqn_act_kernels.h).  Row groups of Dense_0: NRG * NP = 512, i.e. 1 MB of
+// partials for J = 512 (6 % of the Dense_0 kernel they come from) -- the head's single CU has to read them all -- over
+// NRG * J / 32 workgroups of 8 waves (256 for N <= 32, 128 for N <= 64).
+static int iqn_act_chain(idqn_handle_t h, int32_t which, int32_t head, float* q_out_dev, hipStream_t q) {
+    const float* params = (which ? h->target : h->online) + (long)head * h->L.head_stride;
+    const int N = h->iqn.N, MT = N > 32 ? 2 : 1, NP = 32 * MT, NRG = 512 / NP;
+    IqnActCosArgs ca;
+    ca.tau = h->iact_tau; ca.cosv = h->iact_cos;
+    hipLaunchKernelGGL(k_iqn_act_cos, dim3((unsigned)N), dim3(64), 0, q, ca);
+    int rc = act_trunk(h, params, h->act_state, q);
+    if (rc) return rc;
+    IqnActEmbedArgs ea;
+    ea.cosv = h->iact_cos; ea.psi = h->act_a[2]; ea.params = params; ea.x = h->iact_x; ea.we_off = h->iqn.off_we;
+    ea.be_off = h->iqn.off_be; ea.F = h->F; ea.N = N; ea.NP = NP;
+    hipLaunchKernelGGL(k_iqn_act_embed, dim3((unsigned)cdiv(h->F, 64), (unsigned)MT), dim3(256), 0, q, ea);
+    IqnActDenseArgs d;
+    d.x = h->iact_x; d.params = params; d.part = h->iact_part; d.w_off = h->off_w0; d.F = h->F; d.J = h->J; d.NP = NP; d.NRG = NRG;
+    const dim3 dgrid((unsigned)(NRG * (h->J / 32)));
+    if (MT == 1) hipLaunchKernelGGL(k_iqn_act_dense0<1>, dgrid, dim3(512), 0, q, d);
+    else hipLaunchKernelGGL(k_iqn_act_dense0<2>, dgrid, dim3(512), 0, q, d);
+    IqnActHeadArgs ha;
+    ha.part = h->iact_part; ha.params = params; ha.b0_off = h->off_b0; ha.w1_off = h->off_w1; ha.b1_off = h->off_b1;
+    ha.NRG = NRG; ha.J = h->J; ha.A = h->cfg.n_actions; ha.N = N; ha.NP = NP; ha.q_out = q_out_dev; ha.action = h->act_action;
+    ha.mail = h->act_use_mail ? h->act_mail_dev : nullptr; ha.seq = h->act_seq;
+    if (MT == 1) hipLaunchKernelGGL(k_iqn_act_head<1>, dim3(1), dim3(1024), 0, q, ha);
+    else hipLaunchKernelGGL(k_iqn_act_head<2>, dim3(1), dim3(1024), 0, q, ha);
+    IDQN_HIP_CHECK(hipGetLastError());
+    return IDQN_OK;
+}
+
 // select_action's greedy branch for ONE state that lives on the host (slimdqn/sample_collection/utils.py:8-21: the
 // reference uploads the state, runs best_action and blocks on `.item()`): upload from pinned memory, the five launches of
 // the single-state path, the action back into pinned memory, one stream synchronisation -- replayed as ONE hipGraph per
 // (net, buffers) after the first call (seven eager API calls cost more host time than the ~35 us of GPU work).
 static int act_host_wait(idqn_handle_t h, int32_t* action_host_pinned, hipStream_t q);
 // wait = false: the launch only (idqn_act_host_begin); the result is collected by act_host_wait (idqn_act_host_end)
+// tau_host_pinned != nullptr: the i-IQN chain on that many fractions (idqn_iqn_act_host; its entry checked the arguments)
 static int act_host_impl(idqn_handle_t h, int32_t which, int32_t head, const void* state_host_pinned, float* q_out_dev,
-                         int32_t* action_host_pinned, void* stream, bool wait) {
+                         int32_t* action_host_pinned, void* stream, bool wait, const float* tau_host_pinned = nullptr) {
     IDQN_REQUIRE(h && state_host_pinned && q_out_dev && action_host_pinned, "idqn_act_host: null pointer");
     IDQN_REQUIRE(head >= 0 && head < h->cfg.n_heads && (which == 0 || which == 1), "idqn_act_host: bad head / which");
+    const bool iqn = tau_host_pinned != nullptr;
     hipStream_t q = (hipStream_t)stream;
     const bool cnn = h->cfg.arch == IDQN_ARCH_CNN;
     // bytes of one state: uint8 pixels (cnn) or float32 features (fc)
@@ -2682,7 +2728,16 @@ static int act_host_impl(idqn_handle_t h, int32_t which, int32_t head, const voi
     // The single-state path ends in a kernel that can write the action straight into mapped host memory, followed by a
     // sequence number the host polls (IDQN_ACT_POLL=0: a device-to-host copy and a stream synchronisation instead).
     static const bool no_poll = getenv("IDQN_ACT_POLL") && atoi(getenv("IDQN_ACT_POLL")) == 0;
-    const bool poll = !no_poll && ((cnn && !h->gc.on) ? (!act_generic() && h->J <= 512 && h->cfg.n_actions <= 32) : true);
+    // (the i-IQN chain always ends in k_iqn_act_head, which writes the mailbox: it never takes the generic route, so
+    // IDQN_ACT_GENERIC has no say in it)
+    const bool poll = !no_poll && (iqn || ((cnn && !h->gc.on) ? (!act_generic() && h->J <= 512 && h->cfg.n_actions <= 32) : true));
+    if (iqn && !h->iact_tau) {
+        const long NP = h->iqn.N > 32 ? 64 : 32;
+        float* p = nullptr;
+        IDQN_HIP_CHECK(hipMalloc((void**)&p, (size_t)(64 + 64 * IQN_ACT_EMBED + (long)h->F * NP + 512L * h->J) * 4));
+        h->owned.push_back((void*)p);
+        h->iact_tau = p; h->iact_cos = p + 64; h->iact_x = h->iact_cos + 64 * IQN_ACT_EMBED; h->iact_part = h->iact_x + (long)h->F * NP;
+    }
     if (poll && !h->act_mail) {
         IDQN_HIP_CHECK(hipHostMalloc((void**)&h->act_mail, 64, hipHostMallocMapped | hipHostMallocCoherent));
         memset(h->act_mail, 0, 64);
@@ -2702,8 +2757,10 @@ static int act_host_impl(idqn_handle_t h, int32_t which, int32_t head, const voi
     }
     auto issue = [&](hipStream_t qs) -> int {
         if (!direct) IDQN_HIP_CHECK(hipMemcpyAsync(h->act_state, state_host_pinned, E, hipMemcpyHostToDevice, qs));
+        if (iqn) IDQN_HIP_CHECK(hipMemcpyAsync(h->iact_tau, tau_host_pinned, (size_t)h->iqn.N * 4, hipMemcpyHostToDevice, qs));
         h->act_use_mail = poll;
-        int rc = q_values_impl(h, which, head, direct ? direct : (const void*)h->act_state, 1, q_out_dev, h->act_action, (void*)qs);
+        int rc = iqn ? iqn_act_chain(h, which, head, q_out_dev, qs)
+                     : q_values_impl(h, which, head, direct ? direct : (const void*)h->act_state, 1, q_out_dev, h->act_action, (void*)qs);
         h->act_use_mail = false;
         if (rc) return rc;
         if (!poll) IDQN_HIP_CHECK(hipMemcpyAsync(action_host_pinned, h->act_action, 4, hipMemcpyDeviceToHost, qs));
@@ -2712,24 +2769,40 @@ static int act_host_impl(idqn_handle_t h, int32_t which, int32_t head, const voi
     static const bool use_graph = !(getenv("IDQN_ACT_GRAPH") && atoi(getenv("IDQN_ACT_GRAPH")) == 0);
     int rc = IDQN_OK;
     if (use_graph) {
-        auto key = std::make_tuple(which * h->cfg.n_heads + head, state_host_pinned, (void*)q_out_dev, (void*)action_host_pinned);
-        auto it = h->act_graphs.find(key);
-        if (it == h->act_graphs.end()) {
-            // (captured on a stream of the handle's own: the caller's may be the legacy default stream, which cannot
-            // capture; the instantiated graph is then launched on the caller's stream like any other work)
+        // (captured on a stream of the handle's own: the caller's may be the legacy default stream, which cannot
+        // capture; the instantiated graph is then launched on the caller's stream like any other work)
+        auto capture = [&](hipGraphExec_t* exec) -> int {
             hipGraph_t graph = nullptr;
-            hipGraphExec_t exec = nullptr;
             if (!h->act_stream) IDQN_HIP_CHECK(hipStreamCreateWithFlags(&h->act_stream, hipStreamNonBlocking));
             IDQN_HIP_CHECK(hipStreamBeginCapture(h->act_stream, hipStreamCaptureModeRelaxed));
-            rc = issue(h->act_stream);
+            const int rc2 = issue(h->act_stream);
             const hipError_t e = hipStreamEndCapture(h->act_stream, &graph);
-            if (rc) return rc;
+            if (rc2) return rc2;
             IDQN_HIP_CHECK(e);
-            IDQN_HIP_CHECK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+            IDQN_HIP_CHECK(hipGraphInstantiate(exec, graph, nullptr, nullptr, 0));
             IDQN_HIP_CHECK(hipGraphDestroy(graph));
-            it = h->act_graphs.emplace(key, exec).first;
+            return IDQN_OK;
+        };
+        const int net = which * h->cfg.n_heads + head;
+        hipGraphExec_t exec = nullptr;
+        if (iqn) {
+            auto key = std::make_tuple(net, state_host_pinned, (const void*)tau_host_pinned, (void*)q_out_dev, (void*)action_host_pinned);
+            auto it = h->iact_graphs.find(key);
+            if (it == h->iact_graphs.end()) {
+                if ((rc = capture(&exec))) return rc;
+                it = h->iact_graphs.emplace(key, exec).first;
+            }
+            exec = it->second;
+        } else {
+            auto key = std::make_tuple(net, state_host_pinned, (void*)q_out_dev, (void*)action_host_pinned);
+            auto it = h->act_graphs.find(key);
+            if (it == h->act_graphs.end()) {
+                if ((rc = capture(&exec))) return rc;
+                it = h->act_graphs.emplace(key, exec).first;
+            }
+            exec = it->second;
         }
-        IDQN_HIP_CHECK(hipGraphLaunch(it->second, q));
+        IDQN_HIP_CHECK(hipGraphLaunch(exec, q));
     } else {
         rc = issue(q);
         if (rc) return rc;
@@ -2776,6 +2849,31 @@ extern "C" int idqn_act_host_begin(idqn_handle_t h, int32_t which, int32_t head,
                                    int32_t* action_host_pinned, void* stream) {
     IDQN_REQUIRE(h && h->act_pending == 0, "idqn_act_host_begin: null handle, or an acting launch is already pending");
     return act_host_impl(h, which, head, state_host_pinned, q_out_dev, action_host_pinned, stream, false);
+}
+// argument checks of the two i-IQN entries, under their own names: everything is refused before anything is enqueued (the
+// same tests at the head of act_host_impl then cannot fire for them).  The last clause is an invariant, not a case: idqn_create
+// accepts quantile heads only on shapes the MFMA path is built for, all of which satisfy it.
+static int iqn_act_check(idqn_handle_t h, const char* fn, int32_t which, int32_t head, const void* state_host_pinned,
+                         const float* tau_host_pinned, float* q_out_dev, int32_t* action_host_pinned) {
+    IDQN_REQUIRE(h && state_host_pinned && tau_host_pinned && q_out_dev && action_host_pinned, "%s: null pointer", fn);
+    IDQN_REQUIRE(h->iqn.N > 0, "%s: the handle was created without quantile heads (cfg.n_quantiles)", fn);
+    IDQN_REQUIRE(head >= 0 && head < h->cfg.n_heads && (which == 0 || which == 1), "%s: bad head / which", fn);
+    IDQN_REQUIRE(h->act_pending == 0, "%s: an acting launch is already pending (idqn_act_host_end collects it)", fn);
+    IDQN_REQUIRE(h->F % 2 == 0 && h->J % 32 == 0 && h->J <= 512 && h->cfg.n_actions <= 32 && h->iqn.N <= 64,
+                 "%s: the single-state kernels take even F, J = 32 m <= 512, <= 32 actions, <= 64 fractions", fn);
+    return IDQN_OK;
+}
+extern "C" int idqn_iqn_act_host(idqn_handle_t h, int32_t which, int32_t head, const void* state_host_pinned,
+                                 const float* tau_host_pinned, float* q_out_dev, int32_t* action_host_pinned, void* stream) {
+    int rc = iqn_act_check(h, "idqn_iqn_act_host", which, head, state_host_pinned, tau_host_pinned, q_out_dev, action_host_pinned);
+    if (rc) return rc;
+    return act_host_impl(h, which, head, state_host_pinned, q_out_dev, action_host_pinned, stream, true, tau_host_pinned);
+}
+extern "C" int idqn_iqn_act_host_begin(idqn_handle_t h, int32_t which, int32_t head, const void* state_host_pinned,
+                                       const float* tau_host_pinned, float* q_out_dev, int32_t* action_host_pinned, void* stream) {
+    int rc = iqn_act_check(h, "idqn_iqn_act_host_begin", which, head, state_host_pinned, tau_host_pinned, q_out_dev, action_host_pinned);
+    if (rc) return rc;
+    return act_host_impl(h, which, head, state_host_pinned, q_out_dev, action_host_pinned, stream, false, tau_host_pinned);
 }
 extern "C" int idqn_act_host_end(idqn_handle_t h, int32_t* action_host_pinned, void* stream) {
     IDQN_REQUIRE(h && action_host_pinned, "idqn_act_host_end: null pointer");

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from slimdqn import _hip, prng
+from slimdqn.networks._agent import _HostAction, _PendingHostAction
 from slimdqn.networks.idqn import iDQN
 
 
@@ -174,8 +175,45 @@ class iIQN(iDQN):
         assert params is self.params or params is self.target_params
         return self._iqn_q(0 if params is self.params else 1, idx_params, state, taus)
 
+    def _act_host(self, which, head, src, taus, key):
+        """``best_action`` for ONE state in host memory (the trainer's case): ``idqn_iqn_act_host`` -- the state and the N
+        fractions go through pinned buffers of this agent, the single-state chain is replayed as one graph and the action
+        comes back through the mailbox (a ``_PendingHostAction`` with ``lazy_host_actions``, like ``DeviceAgent._best_action``)."""
+        if taus is None:  # drawn as _iqn_q draws them: a function of the key, _tau_rng untouched unless there is none
+            rng = prng.generator(prng.split(key, 2)[1]) if key is not None else self._tau_rng
+            taus = rng.random((self._n_quantiles, 1)).astype(np.float32)
+        taus = np.ascontiguousarray(taus, np.float32)
+        assert taus.size == self._n_quantiles, taus.shape
+        if not hasattr(self, "_act_pin"):
+            self._act_pin = torch.empty(int(np.prod(self._obs)), dtype=torch.uint8).pin_memory()
+            self._act_pin_np = self._act_pin.numpy()
+            self._act_tau_pin = torch.empty(self._n_quantiles, dtype=torch.float32).pin_memory()
+            self._act_tau_np = self._act_tau_pin.numpy()
+            self._act_out = torch.zeros(4, dtype=torch.int32).pin_memory()
+            self._act_out_np = self._act_out.numpy()
+        pending = getattr(self, "_act_in_flight", None)
+        if pending is not None:  # (a lazy action nobody collected: finish it before the staging buffers are rewritten)
+            pending.item()
+        self._act_pin_np[:] = src.reshape(-1)
+        self._act_tau_np[:] = taus.reshape(-1)
+        self._ensure_handle(32)
+        args = (self._handle, int(which), int(head), C.c_void_p(self._act_pin.data_ptr()), C.c_void_p(self._act_tau_pin.data_ptr()),
+                _hip.ptr(self._q_out), C.c_void_p(self._act_out.data_ptr()), _hip.current_stream())
+        if self.lazy_host_actions:
+            _hip.check(_hip.lib().idqn_iqn_act_host_begin(*args), "idqn_iqn_act_host_begin")
+            self._act_in_flight = _PendingHostAction(self)
+            return self._act_in_flight
+        _hip.check(_hip.lib().idqn_iqn_act_host(*args), "idqn_iqn_act_host")
+        return _HostAction(int(self._act_out_np[0]))
+
     def best_action(self, params, state, key, taus=None):
         idx_params = prng.randint(key, 0, self.n_networks)
         assert params is self.params or params is self.target_params
-        self._iqn_q(0 if params is self.params else 1, idx_params, state, taus, want_action=True, key=key)
+        which = 0 if params is self.params else 1
+        st = getattr(state, "tensor", state)
+        if not (isinstance(st, torch.Tensor) and st.is_cuda):
+            src = np.asarray(st)
+            if src.size == int(np.prod(self._obs)):  # one state on the host: the latency path
+                return self._act_host(which, idx_params, src, taus, key)
+        self._iqn_q(which, idx_params, state, taus, want_action=True, key=key)
         return self._action_out[0]

@@ -264,6 +264,19 @@ int idqn_act_host_begin(idqn_handle_t h, int32_t which, int32_t head, const void
                         int32_t* action_host_pinned, void* stream);
 int idqn_act_host_end(idqn_handle_t h, int32_t* action_host_pinned, void* stream);
 
+/* The same for the i-IQN heads (a handle with cfg.n_quantiles = N > 0): the acting rule of IQN on the reference's
+ * best_action protocol (idqn.py:126-131; oracle/iqn_ref.py:157-160, `greedy_action`) for ONE uint8 state and N quantile
+ * fractions tau [N] in (0, 1), both in PINNED host memory:  q[a] = (1 / N) sum_l Z(s, tau_l)[a]  of head `head`, summed in
+ * the order l = 0 .. N - 1, is left in q_out_dev [A]; its first maximum is in action_host_pinned[0] when the call returns.
+ * Mailbox, graph replay (one linear chain per (net, buffers)), IDQN_ACT_POLL and IDQN_ACT_GRAPH as for idqn_act_host; every
+ * sum runs in a fixed order, so eager and replayed calls give the same bits.  IDQN_E_INVALID, before anything is enqueued:
+ * a handle without quantile heads, a bad head / which, a null pointer, a launch still pending.                          */
+int idqn_iqn_act_host(idqn_handle_t h, int32_t which, int32_t head, const void* state_host_pinned,
+                      const float* tau_host_pinned, float* q_out_dev, int32_t* action_host_pinned, void* stream);
+/* ... in two halves: idqn_act_host_end collects the action of either kind; one launch is pending per handle.         */
+int idqn_iqn_act_host_begin(idqn_handle_t h, int32_t which, int32_t head, const void* state_host_pinned,
+                            const float* tau_host_pinned, float* q_out_dev, int32_t* action_host_pinned, void* stream);
+
 /* Test / debug access to internal activation buffers by name (device pointer + byte size).        */
 int idqn_debug_buffer(idqn_handle_t h, const char* name, void** ptr_dev, int64_t* nbytes);
 /* Mean duration (ms) and launch count of the dominant kernel over the IDQN_F_PROFILE calls since
