@@ -21,6 +21,7 @@
 #include <tuple>
 
 #include "act_kernels.h"
+#include "act_many_kernels.h"
 #include "iqn_act_kernels.h"
 #include "cnn_kernels.h"
 #include "fc_kernels.h"
@@ -298,6 +299,16 @@ struct idqn_handle_s {
     // idqn_iqn_act_host (iqn_act_kernels.h): fractions, their cosines [N][64], x [F][NP], Dense_0 partials [NRG][J / 32][2][NP][16]
     float *iact_tau = nullptr, *iact_cos = nullptr, *iact_x = nullptr, *iact_part = nullptr;
     std::map<std::tuple<int, const void*, const void*, void*, void*>, hipGraphExec_t> iact_graphs;  // (net, state, fractions, q out, action)
+    // idqn_act_host_many (act_many_kernels.h).  Nothing here is shared with the single-state path but the capture stream.
+    uint8_t* many_pin = nullptr;        // pinned block {ActManyTable, states [32][state bytes]} (hipHostMalloc)
+    uint8_t* many_block = nullptr;      // its device copy, uploaded by the chain's one copy node
+    float *many_a[3] = {nullptr, nullptr, nullptr}, *many_part = nullptr;  // activations [32][..], Dense_0 partials [32][NRG][J]
+    int32_t* many_action = nullptr;     // [32]
+    int32_t* many_mail = nullptr;       // host mailbox {action[32], sequence} (mapped + coherent)
+    int32_t* many_mail_dev = nullptr;   // its device address
+    unsigned* many_ctr = nullptr;       // device side: {sequence number, finished workgroups}
+    unsigned many_expected = 0;         // sequence number the next idqn_act_host_many call waits for
+    std::map<std::tuple<int, void*, void*>, hipGraphExec_t> many_graphs;  // (n, q out, host actions)
     const float* infer_pbase = nullptr;  // parameter base of the net the last idqn_q_values call evaluated
     float *infer_hbuf = nullptr, *infer_qpart = nullptr;  // k_hidden outputs of the single inference net
     float* wt[3] = {nullptr, nullptr, nullptr};  // transformed weights of the Conv_1 / Conv_2 data gradients
@@ -2006,10 +2017,13 @@ extern "C" int idqn_destroy(idqn_handle_t h) {
         if (e) (void)hipEventDestroy(e);
     for (auto& g : h->act_graphs) (void)hipGraphExecDestroy(g.second);
     for (auto& g : h->iact_graphs) (void)hipGraphExecDestroy(g.second);
+    for (auto& g : h->many_graphs) (void)hipGraphExecDestroy(g.second);
     for (auto& g : h->step_graphs)
         if (g.second.second) (void)hipGraphExecDestroy(g.second.second);
     if (h->act_stream) (void)hipStreamDestroy(h->act_stream);
     if (h->act_mail) (void)hipHostFree(h->act_mail);
+    if (h->many_mail) (void)hipHostFree(h->many_mail);
+    if (h->many_pin) (void)hipHostFree(h->many_pin);
     if (h->fact_planes) (void)hipFree(h->fact_planes);
     for (int32_t* p : h->iqn.bwd_items)
         if (p) (void)hipFree(p);
@@ -2878,6 +2892,163 @@ extern "C" int idqn_iqn_act_host_begin(idqn_handle_t h, int32_t which, int32_t h
 extern "C" int idqn_act_host_end(idqn_handle_t h, int32_t* action_host_pinned, void* stream) {
     IDQN_REQUIRE(h && action_host_pinned, "idqn_act_host_end: null pointer");
     return act_host_wait(h, action_host_pinned, (hipStream_t)stream);
+}
+
+// select_action's greedy branch for n <= 32 host states, one head each (act_many_kernels.h): the states are copied behind
+// the head / group table in the handle's pinned block, ONE copy node uploads the block, five launches follow (three conv
+// layers, Dense_0 per group of states with one head, the head kernel per state), and the n actions come back through a
+// mailbox of their own.  One linear hipGraph per (n, buffers) serves every head assignment and both parameter sets.
+static int act_many_conv_plan(idqn_handle_t h, int i, int* KS, int* upt) {
+    const ConvL& l = h->conv[i];
+    *KS = i == 0 ? 8 : 16;  // as act_trunk
+    const int units = l.K * l.K * (l.CI % 32 == 0 ? l.CI / 32 : l.CI / 4);
+    *upt = cdiv(units, *KS);
+    IDQN_REQUIRE(l.CI % 32 == 0 ? *upt <= 4 : (l.CI == 4 && *upt <= 8), "idqn_act_host_many: Conv_%d is outside the acting kernels' shapes", i);
+    return IDQN_OK;
+}
+
+static int act_many_chain(idqn_handle_t h, int n, size_t state_bytes, float* q_out_dev, bool poll, int32_t* actions_host_pinned,
+                          hipStream_t q) {
+    IDQN_HIP_CHECK(hipMemcpyAsync(h->many_block, h->many_pin, sizeof(ActManyTable) + (size_t)n * state_bytes, hipMemcpyHostToDevice, q));
+    ActManyNets nets;
+    nets.tab = (const ActManyTable*)h->many_block; nets.online = h->online; nets.target = h->target; nets.pstride = h->L.head_stride;
+    const float* in = nullptr;
+    int ih = h->cfg.obs_h, iw = h->cfg.obs_w;
+    for (int i = 0; i < 3; ++i) {
+        const ConvL& l = h->conv[i];
+        ActManyConvArgs a;
+        a.nets = nets; a.in_u8 = i == 0 ? h->many_block + sizeof(ActManyTable) : nullptr; a.in = in; a.out = h->many_a[i];
+        a.w_off = l.w_off; a.b_off = l.b_off; a.IH = ih; a.IW = iw; a.CI = l.CI; a.OH = l.OH; a.OW = l.OW; a.CO = l.CO;
+        a.K = l.K; a.S = l.S; a.PLh = l.PLh; a.PLw = l.PLw;
+        int upt = 0;
+        int rc = act_many_conv_plan(h, i, &a.KS, &upt);
+        if (rc) return rc;
+        const dim3 grid(cdiv((long)l.OH * l.OW * l.CO, 256 / a.KS), n);
+        if (l.CI % 32 != 0) hipLaunchKernelGGL((k_act_many_conv<4, 8>), grid, dim3(256), 0, q, a);
+        else if (upt <= 1) hipLaunchKernelGGL((k_act_many_conv<32, 1>), grid, dim3(256), 0, q, a);
+        else if (upt <= 2) hipLaunchKernelGGL((k_act_many_conv<32, 2>), grid, dim3(256), 0, q, a);
+        else hipLaunchKernelGGL((k_act_many_conv<32, 4>), grid, dim3(256), 0, q, a);
+        in = h->many_a[i]; ih = l.OH; iw = l.OW;
+    }
+    ActManyDenseArgs d;
+    d.nets = nets; d.a3 = h->many_a[2]; d.part = h->many_part; d.w_off = h->off_w0; d.F = h->F; d.J = h->J;
+    d.NRG = std::max(1, 256 / (h->J / 128));  // as the single-state path
+    hipLaunchKernelGGL(k_act_many_dense0, dim3(d.NRG * (h->J / 128), std::min(n, h->cfg.n_heads)), dim3(256), 0, q, d);
+    ActManyHeadArgs ha;
+    ha.nets = nets; ha.part = h->many_part; ha.b0_off = h->off_b0; ha.w1_off = h->off_w1; ha.b1_off = h->off_b1;
+    ha.NP = d.NRG; ha.J = h->J; ha.A = h->cfg.n_actions; ha.n = n; ha.q_out = q_out_dev; ha.action = h->many_action;
+    ha.mail = poll ? h->many_mail_dev : nullptr; ha.ctr = h->many_ctr;
+    hipLaunchKernelGGL(k_act_many_head, dim3(n), dim3(1024), 0, q, ha);
+    IDQN_HIP_CHECK(hipGetLastError());
+    if (!poll) IDQN_HIP_CHECK(hipMemcpyAsync(actions_host_pinned, h->many_action, (size_t)n * 4, hipMemcpyDeviceToHost, q));
+    return IDQN_OK;
+}
+
+extern "C" int idqn_act_host_many(idqn_handle_t h, int32_t which, const int32_t* heads_host, const void* states_host_pinned, int32_t n,
+                                  float* q_out_dev, int32_t* actions_host_pinned, void* stream) {
+    IDQN_REQUIRE(h && heads_host && states_host_pinned && q_out_dev && actions_host_pinned, "idqn_act_host_many: null pointer");
+    IDQN_REQUIRE(n >= 1 && n <= ACT_MANY_MAX, "idqn_act_host_many: n = %d, must be in [1, %d]", n, ACT_MANY_MAX);
+    IDQN_REQUIRE(which == 0 || which == 1, "idqn_act_host_many: which = %d", which);
+    const int K = h->cfg.n_heads;
+    for (int e = 0; e < n; ++e) IDQN_REQUIRE(heads_host[e] >= 0 && heads_host[e] < K, "idqn_act_host_many: head %d of state %d", heads_host[e], e);
+    IDQN_REQUIRE(h->act_pending == 0, "idqn_act_host_many: an idqn_act_host_begin is still waiting for its _end");
+    IDQN_REQUIRE(h->iqn.N == 0, "idqn_act_host_many: the handle was created with quantile heads");
+    IDQN_REQUIRE(h->cfg.arch == IDQN_ARCH_CNN && !h->gc.on && !act_generic() && h->J <= 512 && h->J % 128 == 0 && h->cfg.n_actions <= 32,
+                 "idqn_act_host_many: the handle is outside the single-state cnn acting path (fc, general shapes, IDQN_ACT_GENERIC, J > 512, A > 32)");
+    for (int i = 0; i < 3; ++i) {
+        int ks = 0, upt = 0;
+        int rc = act_many_conv_plan(h, i, &ks, &upt);
+        if (rc) return rc;
+    }
+    hipStream_t q = (hipStream_t)stream;
+    const size_t sb = (size_t)h->cfg.obs_h * h->cfg.obs_w * h->cfg.obs_c;  // bytes of one state
+    IDQN_REQUIRE(sb % 4 == 0, "idqn_act_host_many: %zu bytes per state", sb);
+    static const bool no_poll = getenv("IDQN_ACT_POLL") && atoi(getenv("IDQN_ACT_POLL")) == 0;
+    static const bool use_graph = !(getenv("IDQN_ACT_GRAPH") && atoi(getenv("IDQN_ACT_GRAPH")) == 0);
+    const bool poll = !no_poll;
+    if (!h->many_block) {
+        const size_t block = sizeof(ActManyTable) + ACT_MANY_MAX * sb + 64;
+        const long NRG = std::max(1, 256 / (h->J / 128));
+        long fl[4] = {0, 0, 0, ACT_MANY_MAX * NRG * h->J};
+        for (int i = 0; i < 3; ++i) fl[i] = (long)ACT_MANY_MAX * h->conv[i].OH * h->conv[i].OW * h->conv[i].CO;
+        uint8_t *pin = nullptr, *dev = nullptr;
+        float* f = nullptr;
+        int32_t *act = nullptr, *mail = nullptr;
+        IDQN_HIP_CHECK(hipHostMalloc((void**)&pin, block, hipHostMallocDefault));
+        h->many_pin = pin;
+        IDQN_HIP_CHECK(hipHostMalloc((void**)&mail, 256, hipHostMallocMapped | hipHostMallocCoherent));
+        h->many_mail = mail;
+        memset(mail, 0, 256);
+        IDQN_HIP_CHECK(hipHostGetDevicePointer((void**)&h->many_mail_dev, mail, 0));
+        IDQN_HIP_CHECK(hipMalloc((void**)&f, (size_t)(fl[0] + fl[1] + fl[2] + fl[3]) * 4));
+        h->owned.push_back((void*)f);
+        IDQN_HIP_CHECK(hipMalloc((void**)&act, 256));  // actions [32], then the two counters
+        h->owned.push_back((void*)act);
+        IDQN_HIP_CHECK(hipMemset(act, 0, 256));
+        IDQN_HIP_CHECK(hipMalloc((void**)&dev, block));
+        h->owned.push_back((void*)dev);
+        IDQN_HIP_CHECK(hipStreamSynchronize(nullptr));  // (the memset runs on the null stream, which does not order against q)
+        h->many_a[0] = f; h->many_a[1] = f + fl[0]; h->many_a[2] = h->many_a[1] + fl[1]; h->many_part = h->many_a[2] + fl[2];
+        h->many_action = act; h->many_ctr = (unsigned*)(act + ACT_MANY_MAX);
+        h->many_block = dev;
+    }
+    // the table: states grouped by head, in state order within a group
+    ActManyTable* tb = (ActManyTable*)h->many_pin;
+    tb->n = n; tb->which = which; tb->pad = 0;
+    int ng = 0, pos = 0;
+    for (int k = 0; k < K && pos < n; ++k) {
+        const int start = pos;
+        for (int e = 0; e < n; ++e)
+            if (heads_host[e] == k) tb->order[pos++] = e;
+        if (pos > start) { tb->g_head[ng] = k; tb->g_start[ng] = start; tb->g_count[ng] = pos - start; ++ng; }
+    }
+    tb->n_groups = ng;
+    for (int e = 0; e < n; ++e) tb->head[e] = heads_host[e];
+    memcpy(h->many_pin + sizeof(ActManyTable), states_host_pinned, (size_t)n * sb);
+    int rc = IDQN_OK;
+    if (use_graph) {
+        auto key = std::make_tuple((int)n, (void*)q_out_dev, (void*)actions_host_pinned);
+        auto it = h->many_graphs.find(key);
+        if (it == h->many_graphs.end()) {
+            hipGraph_t graph = nullptr;
+            hipGraphExec_t exec = nullptr;
+            if (!h->act_stream) IDQN_HIP_CHECK(hipStreamCreateWithFlags(&h->act_stream, hipStreamNonBlocking));
+            IDQN_HIP_CHECK(hipStreamBeginCapture(h->act_stream, hipStreamCaptureModeRelaxed));
+            rc = act_many_chain(h, n, sb, q_out_dev, poll, actions_host_pinned, h->act_stream);
+            const hipError_t e = hipStreamEndCapture(h->act_stream, &graph);
+            if (rc) return rc;
+            IDQN_HIP_CHECK(e);
+            IDQN_HIP_CHECK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+            IDQN_HIP_CHECK(hipGraphDestroy(graph));
+            it = h->many_graphs.emplace(key, exec).first;
+        }
+        IDQN_HIP_CHECK(hipGraphLaunch(it->second, q));
+    } else if ((rc = act_many_chain(h, n, sb, q_out_dev, poll, actions_host_pinned, q))) {
+        return rc;
+    }
+    if (!poll) {
+        IDQN_HIP_CHECK(hipStreamSynchronize(q));
+        return IDQN_OK;
+    }
+    const unsigned want = ++h->many_expected;
+    volatile int32_t* mail = h->many_mail;
+    bool seen = false;
+    for (long spin = 0; spin < (1L << 34); ++spin) {  // as act_host_wait
+        if ((unsigned)mail[ACT_MANY_MAX] == want) { seen = true; break; }
+        __builtin_ia32_pause();
+        if ((spin & 0xfffff) == 0xfffff && hipStreamQuery(q) != hipErrorNotReady) {
+            seen = (unsigned)mail[ACT_MANY_MAX] == want;
+            break;
+        }
+    }
+    if (!seen) {  // resynchronise the counters, then report
+        IDQN_HIP_CHECK(hipStreamSynchronize(q));
+        IDQN_HIP_CHECK(hipMemcpy(&h->many_expected, h->many_ctr, 4, hipMemcpyDeviceToHost));
+        IDQN_HIP_CHECK(hipMemset(h->many_ctr + 1, 0, 4));
+        IDQN_REQUIRE(false, "idqn_act_host_many: the acting launch finished without delivering its actions");
+    }
+    for (int e = 0; e < n; ++e) actions_host_pinned[e] = mail[e];
+    return IDQN_OK;
 }
 
 extern "C" int idqn_debug_buffer(idqn_handle_t h, const char* name, void** ptr_dev, int64_t* nbytes) {

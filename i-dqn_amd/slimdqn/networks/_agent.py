@@ -309,6 +309,49 @@ class DeviceAgent:
                                                _hip.ptr(self._action_out), _hip.current_stream()), "idqn_best_action")
         return self._action_out[0]
 
+    def _best_actions(self, which, heads, states):
+        """Greedy actions (host int array [n], first maximum on ties) of n <= 32 host states, state i on head ``heads[i]``:
+        the states are staged into one pinned block and ONE C call (``idqn_act_host_many``) uploads them, runs the
+        single-state arithmetic per state with the Dense_0 stream shared among the states of a head and brings the n
+        actions back; the Q rows are left in ``self._q_out[:n]``.  A handle outside that call's domain (MLP, general-shape
+        cnn, quantile heads, ...) answers ``E_INVALID`` once, and from then on this is a loop of ``_best_action``: same
+        actions, same Q rows."""
+        heads = np.ascontiguousarray(np.asarray(heads, np.int32).reshape(-1))
+        n = int(heads.size)
+        if not 1 <= n <= 32 or len(states) != n:
+            raise ValueError(f"best_actions takes 1..32 states and as many heads, got {len(states)} and {n}")
+        if heads.min() < 0 or heads.max() >= self._K:
+            raise ValueError(f"best_actions: heads {heads.tolist()} outside [0, {self._K})")
+        pending = getattr(self, "_act_in_flight", None)
+        if pending is not None:  # (a lazy single-state action nobody collected, as in _best_action)
+            pending.item()
+        size = int(np.prod(self._obs))
+        srcs = [np.asarray(getattr(s, "tensor", s)) for s in states]
+        assert all(a.size == size for a in srcs), "best_actions takes single states"
+        self._ensure_handle(32)
+        if getattr(self, "_act_many_ok", True):
+            if not hasattr(self, "_acts_pin"):
+                dt = torch.uint8 if self._arch == "cnn" else torch.float32
+                self._acts_pin = torch.empty((32, size), dtype=dt).pin_memory()
+                self._acts_pin_np = self._acts_pin.numpy()
+                self._acts_out = torch.zeros(32, dtype=torch.int32).pin_memory()
+                self._acts_out_np = self._acts_out.numpy()
+            for i, a in enumerate(srcs):
+                self._acts_pin_np[i] = a.reshape(-1)  # casts like the array conversion of the reference's jit would
+            rc = _hip.lib().idqn_act_host_many(self._handle, int(which), heads.ctypes.data, C.c_void_p(self._acts_pin.data_ptr()), n,
+                                               _hip.ptr(self._q_out), C.c_void_p(self._acts_out.data_ptr()), _hip.current_stream())
+            if rc != _hip.E_INVALID or self.__dict__.get("_act_many_ok") is not None:
+                _hip.check(rc, "idqn_act_host_many")
+                self._act_many_ok = True
+                return self._acts_out_np[:n].astype(np.int64)
+            self._act_many_ok = False  # this handle acts one state at a time, from now on
+        actions, rows = np.empty(n, np.int64), []
+        for i in range(n):
+            actions[i] = int(self._best_action(which, int(heads[i]), srcs[i]).item())
+            rows.append(self._q_out[0].clone())
+        self._q_out[:n] = torch.stack(rows)
+        return actions
+
     def _debug(self, name):
         """Internal activation buffer as a flat float32 device tensor (tests only)."""
         p, nbytes = C.c_void_p(), C.c_int64()

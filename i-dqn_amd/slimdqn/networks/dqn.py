@@ -49,3 +49,9 @@ class DQN(DeviceAgent):
         """dqn.py:88-92."""
         assert params is self.params or params is self.target_params
         return self._best_action(0 if params is self.params else 1, 0, state)
+
+    def best_actions(self, params, states, keys=None):
+        """``[best_action(params, s).item() for s in states]`` as a host int array, for up to 32 host states: one device
+        call (``DeviceAgent._best_actions``)."""
+        assert params is self.params or params is self.target_params
+        return self._best_actions(0 if params is self.params else 1, [0] * len(states), states)

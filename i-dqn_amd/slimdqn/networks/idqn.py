@@ -84,3 +84,15 @@ class iDQN(DeviceAgent):
         idx_params = prng.randint(key, 0, self.n_networks)
         assert params is self.params or params is self.target_params
         return self._best_action(0 if params is self.params else 1, idx_params, state)
+
+    def best_actions(self, params, states, keys):
+        """``[best_action(params, states[i], keys[i]).item() for i]`` as a host int array, for up to 32 host states (a
+        vector of environments): every head is drawn from its own key as ``best_action`` draws it, and one device call
+        evaluates them all (``DeviceAgent._best_actions``).  Agents with an acting rule of their own (quantile heads,
+        head-parallel ranks) loop over it."""
+        assert params is self.params or params is self.target_params
+        assert len(states) == len(keys)
+        if type(self).best_action is not iDQN.best_action:
+            return np.array([int(self.best_action(params, s, k).item()) for s, k in zip(states, keys)], np.int64)
+        heads = [prng.randint(k, 0, self.n_networks) for k in keys]
+        return self._best_actions(0 if params is self.params else 1, heads, states)

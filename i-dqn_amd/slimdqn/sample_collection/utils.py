@@ -37,6 +37,28 @@ def select_action(best_action_fn, params, state, key, n_actions, epsilon_fn, n_t
     return best_action_fn(params, state, key=greedy_key)  # device scalar
 
 
+def select_actions(best_actions_fn, params, states, keys, n_actions, epsilon_fn, n_training_steps):
+    """``select_action`` for E environments at once: host int list ``[E]`` equal to
+    ``[select_action(best_action_fn, params, states[i], keys[i], ...).item() for i]``.  Every environment splits its key
+    three ways as ``select_action`` does; the exploring ones get their random action on the host, all the others go
+    through ONE ``best_actions_fn(params, greedy states, greedy keys)`` call (none if every environment explores)."""
+    assert len(states) == len(keys)
+    epsilon = epsilon_fn(n_training_steps)
+    actions, greedy, greedy_keys = [None] * len(keys), [], []
+    for i, key in enumerate(keys):
+        explore_key, random_action_key, greedy_key = prng.split(key, 3)
+        if prng.uniform(explore_key) <= epsilon:
+            actions[i] = prng.randint(random_action_key, 0, n_actions)
+        else:
+            greedy.append(i)
+            greedy_keys.append(greedy_key)
+    if greedy:
+        best = best_actions_fn(params, [states[i] for i in greedy], greedy_keys)
+        for i, a in zip(greedy, best):
+            actions[i] = int(a)
+    return actions
+
+
 def collect_single_sample(key, env, agent, rb: ReplayBuffer, p, epsilon_schedule, n_training_steps: int):
     """One environment step into the replay buffer; returns ``(reward, episode_ended)``.
 

@@ -277,6 +277,19 @@ int idqn_iqn_act_host(idqn_handle_t h, int32_t which, int32_t head, const void* 
 int idqn_iqn_act_host_begin(idqn_handle_t h, int32_t which, int32_t head, const void* state_host_pinned,
                             const float* tau_host_pinned, float* q_out_dev, int32_t* action_host_pinned, void* stream);
 
+/* select_action's greedy branch for n <= 32 host states at once, one head each (a vector of environments, each drawing
+ * its head as idqn.py:126-131 does): heads_host [n] (ordinary host memory, read before the call returns) and n uint8
+ * states in PINNED host memory; row e of q_out_dev [n][A] and actions_host_pinned[e] are, byte for byte, what
+ * idqn_act_host gives for (which, heads_host[e], state e) -- the same kernels' arithmetic with a state dimension
+ * (csrc/act_many_kernels.h).  States that share a head share one stream of that head's Dense_0 kernel.  Blocking, like
+ * idqn_act_host; one linear hipGraph per (n, buffers) serves every head assignment and both parameter sets (the heads
+ * travel as data); a mailbox and sequence counter of its own; IDQN_ACT_GRAPH=0 and IDQN_ACT_POLL=0 as for idqn_act_host.
+ * IDQN_E_INVALID, before anything is enqueued: n outside [1, 32], a head outside [0, K), which not 0 / 1, a null pointer,
+ * an idqn_act_host_begin still pending, a handle with quantile heads, and every handle outside the single-state cnn
+ * path (fc, general-shape cnn, IDQN_ACT_GENERIC, J > 512, A > 32).                                                      */
+int idqn_act_host_many(idqn_handle_t h, int32_t which, const int32_t* heads_host, const void* states_host_pinned, int32_t n,
+                       float* q_out_dev, int32_t* actions_host_pinned, void* stream);
+
 /* Test / debug access to internal activation buffers by name (device pointer + byte size).        */
 int idqn_debug_buffer(idqn_handle_t h, const char* name, void** ptr_dev, int64_t* nbytes);
 /* Mean duration (ms) and launch count of the dominant kernel over the IDQN_F_PROFILE calls since
