@@ -9,6 +9,9 @@ import os
 import numpy as np
 import pytest
 
+import cnn_stages as S
+from cnn_stages import relerr as _relerr, unpack_act as _unpack_act, unpack_planes as _unpack_planes  # noqa: F401  (test_gpu_configs.py imports them from here)
+
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -39,28 +42,6 @@ def _agent(name):
     return agent, bs, rec, (arch, obs, A, feats, K, B, steps, p, pt, batches)
 
 
-def _unpack_act(buf, n_slots, slot, H, W, C, lo_h, lo_w, Hp, Wp):
-    """device [slot][Hp*Wp*C][32] -> numpy [32, H, W, C]"""
-    a = buf.cpu().numpy()[: n_slots * Hp * Wp * C * 32].reshape(n_slots, Hp, Wp, C, 32)[slot]
-    return a[lo_h : lo_h + H, lo_w : lo_w + W].transpose(3, 0, 1, 2)
-
-
-def _dgrad_pad(I, O, K, S, PL):
-    mn, mx = 0, O - 1
-    for i in range(I):
-        for k in range(K):
-            t = i + PL - k
-            if t % S:
-                continue
-            o = t // S
-            mn, mx = min(mn, o), max(mx, o)
-    return -mn, mx - (O - 1)
-
-
-def _relerr(got, want):
-    return float(np.abs(got - want).max() / (np.abs(want).max() + 1e-30))
-
-
 @pytest.fixture(params=["bf16x3", "f32"])
 def conv_mode(request, monkeypatch):
     """Conv arithmetic of the agents a test creates: the plane kernels (csrc/convp.h: f32-accurate products on the bf16
@@ -69,81 +50,23 @@ def conv_mode(request, monkeypatch):
     return request.param
 
 
-def _unpack_planes(buf, n_slots, slot, H, W, C, lo_h, lo_w, Hp, Wp):
-    """device [slot][Hp][Wp][3 planes][C][32] bf16 (read through a float32 view) -> numpy [32, H, W, C] = sum of planes"""
-    raw = buf.cpu().numpy().view(np.uint16)[: n_slots * Hp * Wp * 3 * C * 32].reshape(n_slots, Hp, Wp, 3, C, 32)[slot]
-    f = (raw.astype(np.uint32) << 16).view(np.float32).astype(np.float64).sum(axis=2).astype(np.float32)
-    return f[lo_h : lo_h + H, lo_w : lo_w + W].transpose(3, 0, 1, 2)
-
-
 @pytest.mark.parametrize("name", ["cnn_small", "cnn_atari_k5"])
 def test_cnn_every_stage_against_oracle(name, conv_mode):
-    """Forward activations, Q-values, every backward intermediate and every leaf gradient, stage by stage."""
+    """Forward activations, Q-values, every backward intermediate and every leaf gradient, stage by stage
+    (tests/cnn_stages.py does the reading and comparing)."""
     import torch
 
-    from oracle import qnet_ref as Q
     from slimdqn import _hip
 
     agent, bs, rec, (arch, obs, A, feats, K, B, steps, p, pt, batches) = _agent(name)
     losses = agent._learn(bs[0], flags=_hip.F_GRADS_ONLY).cpu().numpy()
     torch.cuda.synchronize()
-    nb = (B + 31) // 32
-    # geometry (same rules as csrc/qnet.hip)
-    H, W, C = obs
-    geo = []
-    for (k, s), f in zip(Q.CNN_GEOM, feats[:3]):
-        oh, lh, hh = Q.same_pad(H, k, s)
-        ow, lw, hw = Q.same_pad(W, k, s)
-        geo.append(dict(IH=H, IW=W, CI=C, OH=oh, OW=ow, CO=f, lo_h=lh, hi_h=hh, lo_w=lw, hi_w=hw, k=k, s=s))
-        H, W, C = oh, ow, f
     g_hat = rec["hyper"]["gamma"] ** rec["hyper"]["n"]
-    errs = {}
-    planes = conv_mode == "bf16x3"
-    unpack = _unpack_planes if planes else _unpack_act
-    sfx = "p" if planes else ""
+    oracle = S.oracle_heads(p, pt, batches[0], K, g_hat)
     for k in range(K):
-        loss, grads, aux = Q.loss_and_grads(Q.head(p, k), Q.head(pt, k), batches[0], arch, g_hat)
-        assert abs(losses[k] - loss) <= LOSS_ATOL, (k, losses[k], loss)
-        tape = aux["tape"]
-        # forward activations of the online net k (slot k*nb + 0)
-        for li, bufname in enumerate(["a1", "a2", "a3"]):
-            if li < 2:
-                gi = geo[li + 1]
-                Hp, Wp = gi["IH"] + gi["lo_h"] + gi["hi_h"], gi["IW"] + gi["lo_w"] + gi["hi_w"]
-                got = unpack(agent._debug(bufname + sfx), 2 * K * nb, k * nb, gi["IH"], gi["IW"], gi["CI"], gi["lo_h"],
-                             gi["lo_w"], Hp, Wp)
-            else:
-                go = geo[2]
-                got = _unpack_act(agent._debug(bufname), 2 * K * nb, k * nb, go["OH"], go["OW"], go["CO"], 0, 0,
-                                  go["OH"], go["OW"])
-            errs[f"h{k}_{bufname}"] = _relerr(got[: min(B, 32)], tape[li][4][:32])
-        q = agent._debug("q").cpu().numpy().reshape(2 * K, nb, 32, 32)
-        errs[f"h{k}_q"] = _relerr(q[k, 0, :A, : min(B, 32)].T, aux["q"][:32])
-        errs[f"h{k}_qnext"] = _relerr(q[K + k, 0, :A, : min(B, 32)].T, aux["q_next"][:32])
-        # backward intermediates
-        dh = agent._debug("dh").cpu().numpy()[: K * nb * feats[3] * 32].reshape(K, nb, feats[3], 32)
-        errs[f"h{k}_dh"] = _relerr(dh[k, 0].T[: min(B, 32)], aux["trace"]["d_dense0"][:32])
-        g2, g1 = geo[2], geo[1]
-        l3h, h3h = _dgrad_pad(g2["IH"], g2["OH"], g2["k"], g2["s"], g2["lo_h"])
-        l3w, h3w = _dgrad_pad(g2["IW"], g2["OW"], g2["k"], g2["s"], g2["lo_w"])
-        got = unpack(agent._debug("da3" + sfx), K * nb, k * nb, g2["OH"], g2["OW"], g2["CO"], l3h, l3w,
-                          g2["OH"] + l3h + h3h, g2["OW"] + l3w + h3w)
-        errs[f"h{k}_da3"] = _relerr(got[: min(B, 32)], aux["trace"]["d_conv2"][:32])
-        l2h, h2h = _dgrad_pad(g1["IH"], g1["OH"], g1["k"], g1["s"], g1["lo_h"])
-        l2w, h2w = _dgrad_pad(g1["IW"], g1["OW"], g1["k"], g1["s"], g1["lo_w"])
-        got = unpack(agent._debug("da2" + sfx), K * nb, k * nb, g1["OH"], g1["OW"], g1["CO"], l2h, l2w,
-                          g1["OH"] + l2h + h2h, g1["OW"] + l2w + h2w)
-        errs[f"h{k}_da2"] = _relerr(got[: min(B, 32)], aux["trace"]["d_conv1"][:32])
-        g0 = geo[0]
-        got = unpack(agent._debug("da1" + sfx), K * nb, k * nb, g0["OH"], g0["OW"], g0["CO"], 0, 0, g0["OH"], g0["OW"])
-        errs[f"h{k}_da1"] = _relerr(got[: min(B, 32)], aux["trace"]["d_conv0"][:32])
-        # leaf gradients
-        G = agent._flat_grad()
-        for leaf in grads:
-            errs[f"h{k}_grad_{leaf}"] = _relerr(G[leaf][k], grads[leaf])
-    print("\nstage relative errors (max |got - want| / max |want|):")
-    for n_, e in errs.items():
-        print(f"  {n_:32s} {e:.3e}")
+        assert abs(losses[k] - oracle[k][0]) <= LOSS_ATOL, (k, losses[k], oracle[k][0])
+    errs = S.stage_errors(agent, p, pt, batches[0], obs, feats, A, K, B, g_hat, conv_mode, oracle=oracle)
+    S.print_stage_errors(errs)
     bad = {n_: e for n_, e in errs.items() if not e < 2e-5}
     assert not bad, bad
 

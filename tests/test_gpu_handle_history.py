@@ -80,6 +80,15 @@ def test_plane_cnn_path(conv_mode):
     _run(_idqn(obs, feats, A, 2), 256, PLANE_SCRIPT)
 
 
+def test_odd_frame_geometry(conv_mode):
+    """(9, 13, 4) -- Conv_0 pads (3, 4) on both axes, Conv_1 sees a 3x4 input, F = 128 (tests/test_gpu_conv_geometry.py) --
+    with B = 33, 5, 40 in turn: pad lanes and compact slot addressing at a block size the other scripts do not have."""
+    script = [learn(33, 1), q_values(0, 1, 5, 101), learn(5, 2), act_host(0, 0, 102), learn(40, 3), q_values(1, 0, 32, 103),
+              learn(33, 4), act_host(1, 1, 104, lazy=True), grads_then_adam(5, 5), learn(40, 6), act_dev(0, 1, 105)]
+    assert [op.args["B"] for op in script if op.kind in H.BATCH_OPS] == [33, 5, 40, 33, 5, 40]
+    _run(_idqn((9, 13, 4), [32, 64, 32, 128], 4, 2), 64, script)
+
+
 def test_nature_shape():
     """The conv launch plans and the fused Dense_0 update of the (84, 84, 4) / [32, 64, 64, 512] network."""
     script = [learn(64, 1), act_host(0, 0, 101), learn(20, 2), q_values(1, 1, 32, 102), learn(32, 3),

@@ -12,6 +12,8 @@ from collections import namedtuple
 import numpy as np
 import pytest
 
+import cnn_stages as S
+
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -37,30 +39,7 @@ def _setup(name):
 def test_iqn_step_against_golden(name):
     agent, batch, taus, rec, (obs, A, feats, K, B, N, p, pt) = _setup(name)
     losses = agent._learn(batch, taus=taus).cpu().numpy()
-    want = np.asarray(rec["losses"])
-    assert np.abs(losses - want).max() <= 1e-5 * max(1.0, np.abs(want).max()), (losses, want)
-    # quantile values of head 0, greedy target action
-    dbg = agent._debug("iqn_dbg").cpu().numpy().reshape(K, 2 * N + 33, 32)[0]
-    z_on, z_tg, q_sel, a_star = dbg[:N, :B], dbg[N : 2 * N, :B], dbg[2 * N : 2 * N + A, :B].T, dbg[2 * N + 32, :B]
-    assert np.array_equal(a_star.astype(np.int64), np.asarray(rec["a_star_head0"]))
-    for got, key in ((z_on, "z_online_head0"), (z_tg, "z_target_head0"), (q_sel, "q_select_head0")):
-        w = np.asarray(rec[key])
-        assert np.abs(got - w).max() <= 2e-5 * max(1.0, np.abs(w).max()), key
-    # first step from zero Adam state: mu = (1 - b1) g, so every leaf's gradient is read off mu
-    mu = agent._flat(agent._mu)
-    par = agent._flat(agent._online)
-    for leaf, r in rec["leaves"].items():
-        idx = np.asarray(r["idx"])
-        g = mu[leaf].reshape(K, -1)[:, idx] / (1.0 - 0.9)
-        wg, scale = np.asarray(r["grad"]), np.asarray(r["grad_absmax"])[:, None]
-        assert (np.abs(g - wg) <= 3e-5 * scale + 1e-12).all(), (leaf, np.abs(g - wg).max(), scale.max())
-        # post-Adam parameters: one step moves a parameter by at most lr; the update direction is sign-like for tiny
-        # gradients, so the bar is a fraction of lr wherever the gradient is not negligible
-        wp = np.asarray(r["param"])
-        big = np.abs(wg) > 1e-3 * scale
-        assert (np.abs(par[leaf].reshape(K, -1)[:, idx] - wp)[big] <= 0.02 * rec["hyper"]["lr"] + 2e-7 * np.abs(wp[big])).all(), leaf
-    assert (agent._count.cpu().numpy() == 1).all()
-    assert np.allclose(agent.cumulated_losses, want, rtol=2e-6, atol=1e-5)
+    S.check_iqn_step(agent, losses, rec, A, K, B, N)
 
 
 def test_iqn_acting_against_oracle():

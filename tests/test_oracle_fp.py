@@ -12,6 +12,9 @@ from oracle import torch_ref as T
 
 CASES = [("cnn", (20, 20, 4), [32, 32, 32, 128], 5, 2, 8), ("fc", 8, [50, 40], 4, 3, 16),
          ("cnn", (84, 84, 4), [32, 64, 64, 512], 6, 1, 3)]
+# frames that are no multiple of 4: SAME pads (3,4) / (3,3) x (2,3) on Conv_0, odd and even Conv_1 inputs
+GEOMETRY_CASES = [("cnn", (9, 13, 4), [32, 32, 32, 128], 4, 2, 5), ("cnn", (22, 31, 4), [32, 32, 32, 128], 4, 2, 5)]
+CASES += GEOMETRY_CASES
 
 
 def _setup(arch, obs, feats, A, K, B, seed=0):
@@ -37,7 +40,7 @@ def test_numpy_and_autograd_restatements_agree(arch, obs, feats, A, K, B):
             assert np.abs(g1[n] - g2[n]).max() <= 1e-9 * (np.abs(g2[n]).max() + 1e-30), n
 
 
-@pytest.mark.parametrize("arch,obs,feats,A,K,B", CASES[:2])
+@pytest.mark.parametrize("arch,obs,feats,A,K,B", CASES[:2] + GEOMETRY_CASES)
 def test_gradients_match_central_differences(arch, obs, feats, A, K, B):
     """A third angle on the fp oracle that needs no automatic differentiation at all: the analytic gradients of
     `loss_and_grads` (the hand-written backward the HIP kernels are pinned to) against central differences of ITS OWN fp64
@@ -53,7 +56,10 @@ def test_gradients_match_central_differences(arch, obs, feats, A, K, B):
     for n, leaf in hp.items():
         flat = leaf.reshape(-1)
         for i in rng.choice(flat.size, size=min(6, flat.size), replace=False):
-            old, eps = flat[i], 1e-5 * max(1.0, abs(flat[i]))
+            # (step 1e-7: a conv bias moves every position of its channel, and at the larger frames a step of 1e-5 puts a
+            # pre-activation within the step of zero in about one coordinate in fifty; fp64 rounding of the quotient stays
+            # near 1e-9, far below the bar)
+            old, eps = flat[i], 1e-7 * max(1.0, abs(flat[i]))
             flat[i] = old + eps
             lp = Q.loss_and_grads(hp, ht, batch, arch, 0.99)[0]
             flat[i] = old - eps
@@ -70,9 +76,45 @@ def test_same_padding_geometry():
     assert Q.same_pad(84, 8, 4) == (21, 2, 2)
     assert Q.same_pad(21, 4, 2) == (11, 1, 2)
     assert Q.same_pad(11, 3, 1) == (11, 1, 1)
+    # by hand from XLA's SAME rule (out = ceil(i / s), total = max((out - 1) s + k - i, 0), lo = total // 2): the other
+    # residues of i mod s, an even input of Conv_1, and layers that collapse to one position
+    assert Q.same_pad(21, 8, 4) == (6, 3, 4)
+    assert Q.same_pad(22, 8, 4) == (6, 3, 3)
+    assert Q.same_pad(23, 8, 4) == (6, 2, 3)
+    assert Q.same_pad(8, 8, 4) == (2, 2, 2)
+    assert Q.same_pad(6, 4, 2) == (3, 1, 1)
+    assert Q.same_pad(2, 4, 2) == (1, 1, 1)
+    assert Q.same_pad(1, 3, 1) == (1, 1, 1)
     shapes = dict(Q.leaf_shapes("cnn", (84, 84, 4), 6, [32, 64, 64, 512]))
     assert shapes["Dense_0/kernel"] == (7744, 512)
     assert sum(int(np.prod(s)) for s in shapes.values()) == 4046502  # params per head
+
+
+def test_conv_forward_by_explicit_index_arithmetic():
+    """The oracle's three conv layers at (9, 13, 4) against y[o] = sum_k x[o s + k - lo] w[k] written as plain loops, reads
+    outside the input counting as zero: no padding array, no im2col, no call into the oracle's geometry.  The low pads are
+    the literals of the SAME rule (total = (ceil(i / s) - 1) s + k - i, lo = total // 2), worked out by hand per axis."""
+    rng = np.random.default_rng(21)
+    x = rng.standard_normal((2, 9, 13, 4))
+    # (kernel, stride, (OH, OW), (lo_h, lo_w)):  9 -> 3 (total 7, lo 3), 13 -> 4 (total 7, lo 3);  3 -> 2 (total 3, lo 1),
+    # 4 -> 2 (total 2, lo 1);  2 -> 2 (total 2, lo 1) on both axes
+    for (k, s, (oh, ow), (lo_h, lo_w)), co in zip(((8, 4, (3, 4), (3, 3)), (4, 2, (2, 2), (1, 1)), (3, 1, (2, 2), (1, 1))), (5, 3, 4)):
+        b, h, w, ci = x.shape
+        wgt, bias = rng.standard_normal((k, k, ci, co)), rng.standard_normal(co)
+        want = np.zeros((b, oh, ow, co))
+        for o_h in range(oh):
+            for o_w in range(ow):
+                acc = np.tile(bias, (b, 1))
+                for kh in range(k):
+                    for kw in range(k):
+                        ih, iw = o_h * s + kh - lo_h, o_w * s + kw - lo_w
+                        if 0 <= ih < h and 0 <= iw < w:
+                            acc = acc + x[:, ih, iw, :] @ wgt[kh, kw]
+                want[:, o_h, o_w] = acc
+        got, _ = Q.conv_fwd(x, wgt, bias, s)
+        assert got.shape == want.shape
+        assert np.abs(got - want).max() <= 1e-12
+        x = np.maximum(want, 0)
 
 
 def test_compute_target_and_loss_formulae():
