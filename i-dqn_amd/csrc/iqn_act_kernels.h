@@ -8,6 +8,7 @@
 // carries the FRACTIONS (NP = 32 or 64 of them, zero rows behind N), its row side 32 hidden units (Dense_0) or the
 // actions (Dense_1), so that the partials of one launch are the B operand of the next as they lie in memory.
 // All sums run in a fixed order: no atomics, the same bits on every call.
+// iqn_act_many_kernels.h repeats this arithmetic per state: a change of summation order has to be made in both headers.
 #pragma once
 #include "common.h"
 

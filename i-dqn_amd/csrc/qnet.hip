@@ -23,6 +23,7 @@
 #include "act_kernels.h"
 #include "act_many_kernels.h"
 #include "iqn_act_kernels.h"
+#include "iqn_act_many_kernels.h"
 #include "cnn_kernels.h"
 #include "fc_kernels.h"
 #include "fc_par_kernels.h"
@@ -309,6 +310,17 @@ struct idqn_handle_s {
     unsigned* many_ctr = nullptr;       // device side: {sequence number, finished workgroups}
     unsigned many_expected = 0;         // sequence number the next idqn_act_host_many call waits for
     std::map<std::tuple<int, void*, void*>, hipGraphExec_t> many_graphs;  // (n, q out, host actions)
+    // idqn_iqn_act_host_many (iqn_act_many_kernels.h): buffers, mailbox and counters of its own, as above.
+    uint8_t* imany_pin = nullptr;       // pinned block {IqnActManyBlock, states [32][state bytes]} (hipHostMalloc)
+    uint8_t* imany_block = nullptr;     // its device copy
+    float *imany_a[3] = {nullptr, nullptr, nullptr};  // activations [32][..]
+    float *imany_cos = nullptr, *imany_x = nullptr, *imany_part = nullptr;  // [32][64][64], [32][F][NP], [32][NRG][J / 32][2][NP][16]
+    int32_t* imany_action = nullptr;    // [32]
+    int32_t* imany_mail = nullptr;      // host mailbox {action[32], sequence} (mapped + coherent)
+    int32_t* imany_mail_dev = nullptr;
+    unsigned* imany_ctr = nullptr;      // device side: {sequence number, finished workgroups}
+    unsigned imany_expected = 0;
+    std::map<std::tuple<int, void*, void*>, hipGraphExec_t> imany_graphs;  // (n, q out, host actions)
     const float* infer_pbase = nullptr;  // parameter base of the net the last idqn_q_values call evaluated
     float *infer_hbuf = nullptr, *infer_qpart = nullptr;  // k_hidden outputs of the single inference net
     float* wt[3] = {nullptr, nullptr, nullptr};  // transformed weights of the Conv_1 / Conv_2 data gradients
@@ -2018,12 +2030,15 @@ extern "C" int idqn_destroy(idqn_handle_t h) {
     for (auto& g : h->act_graphs) (void)hipGraphExecDestroy(g.second);
     for (auto& g : h->iact_graphs) (void)hipGraphExecDestroy(g.second);
     for (auto& g : h->many_graphs) (void)hipGraphExecDestroy(g.second);
+    for (auto& g : h->imany_graphs) (void)hipGraphExecDestroy(g.second);
     for (auto& g : h->step_graphs)
         if (g.second.second) (void)hipGraphExecDestroy(g.second.second);
     if (h->act_stream) (void)hipStreamDestroy(h->act_stream);
     if (h->act_mail) (void)hipHostFree(h->act_mail);
     if (h->many_mail) (void)hipHostFree(h->many_mail);
     if (h->many_pin) (void)hipHostFree(h->many_pin);
+    if (h->imany_mail) (void)hipHostFree(h->imany_mail);
+    if (h->imany_pin) (void)hipHostFree(h->imany_pin);
     if (h->fact_planes) (void)hipFree(h->fact_planes);
     for (int32_t* p : h->iqn.bwd_items)
         if (p) (void)hipFree(p);
@@ -3046,6 +3061,189 @@ extern "C" int idqn_act_host_many(idqn_handle_t h, int32_t which, const int32_t*
         IDQN_HIP_CHECK(hipMemcpy(&h->many_expected, h->many_ctr, 4, hipMemcpyDeviceToHost));
         IDQN_HIP_CHECK(hipMemset(h->many_ctr + 1, 0, 4));
         IDQN_REQUIRE(false, "idqn_act_host_many: the acting launch finished without delivering its actions");
+    }
+    for (int e = 0; e < n; ++e) actions_host_pinned[e] = mail[e];
+    return IDQN_OK;
+}
+
+// The i-IQN acting rule for n <= 32 host states, one head and N fractions each (iqn_act_many_kernels.h): table, fractions
+// and states sit in the handle's pinned block, ONE copy node uploads it, seven launches follow (three conv layers,
+// cosines, embedding, Dense_0 per group of states with one head, the head kernel per state) and the n actions come back
+// through a mailbox of this path's own.  One linear hipGraph per (n, buffers) serves every head assignment, both
+// parameter sets and every set of fractions.  NRG as iqn_act_chain.
+static int iqn_act_many_chain(idqn_handle_t h, int n, size_t state_bytes, float* q_out_dev, bool poll, int32_t* actions_host_pinned,
+                              hipStream_t q) {
+    IDQN_HIP_CHECK(hipMemcpyAsync(h->imany_block, h->imany_pin, sizeof(IqnActManyBlock) + (size_t)n * state_bytes, hipMemcpyHostToDevice, q));
+    const IqnActManyBlock* blk = (const IqnActManyBlock*)h->imany_block;
+    ActManyNets nets;
+    nets.tab = &blk->tab; nets.online = h->online; nets.target = h->target; nets.pstride = h->L.head_stride;
+    const float* in = nullptr;
+    int ih = h->cfg.obs_h, iw = h->cfg.obs_w;
+    for (int i = 0; i < 3; ++i) {
+        const ConvL& l = h->conv[i];
+        ActManyConvArgs a;
+        a.nets = nets; a.in_u8 = i == 0 ? h->imany_block + sizeof(IqnActManyBlock) : nullptr; a.in = in; a.out = h->imany_a[i];
+        a.w_off = l.w_off; a.b_off = l.b_off; a.IH = ih; a.IW = iw; a.CI = l.CI; a.OH = l.OH; a.OW = l.OW; a.CO = l.CO;
+        a.K = l.K; a.S = l.S; a.PLh = l.PLh; a.PLw = l.PLw;
+        int upt = 0;
+        int rc = act_many_conv_plan(h, i, &a.KS, &upt);
+        if (rc) return rc;
+        const dim3 grid(cdiv((long)l.OH * l.OW * l.CO, 256 / a.KS), n);
+        if (l.CI % 32 != 0) hipLaunchKernelGGL((k_act_many_conv<4, 8>), grid, dim3(256), 0, q, a);
+        else if (upt <= 1) hipLaunchKernelGGL((k_act_many_conv<32, 1>), grid, dim3(256), 0, q, a);
+        else if (upt <= 2) hipLaunchKernelGGL((k_act_many_conv<32, 2>), grid, dim3(256), 0, q, a);
+        else hipLaunchKernelGGL((k_act_many_conv<32, 4>), grid, dim3(256), 0, q, a);
+        in = h->imany_a[i]; ih = l.OH; iw = l.OW;
+    }
+    const int N = h->iqn.N, MT = N > 32 ? 2 : 1, NP = 32 * MT, NRG = 512 / NP;
+    IqnActManyCosArgs ca;
+    ca.tau = &blk->tau[0][0]; ca.cosv = h->imany_cos;
+    hipLaunchKernelGGL(k_iqn_act_many_cos, dim3((unsigned)N, (unsigned)n), dim3(64), 0, q, ca);
+    IqnActManyEmbedArgs ea;
+    ea.nets = nets; ea.cosv = h->imany_cos; ea.psi = h->imany_a[2]; ea.x = h->imany_x; ea.we_off = h->iqn.off_we;
+    ea.be_off = h->iqn.off_be; ea.F = h->F; ea.N = N; ea.NP = NP;
+    hipLaunchKernelGGL(k_iqn_act_many_embed, dim3((unsigned)cdiv(h->F, 64), (unsigned)MT, (unsigned)n), dim3(256), 0, q, ea);
+    IqnActManyDenseArgs d;
+    d.nets = nets; d.x = h->imany_x; d.part = h->imany_part; d.w_off = h->off_w0; d.F = h->F; d.J = h->J; d.NP = NP; d.NRG = NRG;
+    const dim3 dgrid((unsigned)(NRG * (h->J / 32)), (unsigned)std::min(n, h->cfg.n_heads));
+    if (MT == 1) hipLaunchKernelGGL(k_iqn_act_many_dense0<1>, dgrid, dim3(512), 0, q, d);
+    else hipLaunchKernelGGL(k_iqn_act_many_dense0<2>, dgrid, dim3(512), 0, q, d);
+    IqnActManyHeadArgs ha;
+    ha.nets = nets; ha.part = h->imany_part; ha.b0_off = h->off_b0; ha.w1_off = h->off_w1; ha.b1_off = h->off_b1;
+    ha.NRG = NRG; ha.J = h->J; ha.A = h->cfg.n_actions; ha.N = N; ha.NP = NP; ha.n = n; ha.q_out = q_out_dev;
+    ha.action = h->imany_action; ha.mail = poll ? h->imany_mail_dev : nullptr; ha.ctr = h->imany_ctr;
+    if (MT == 1) hipLaunchKernelGGL(k_iqn_act_many_head<1>, dim3(n), dim3(1024), 0, q, ha);
+    else hipLaunchKernelGGL(k_iqn_act_many_head<2>, dim3(n), dim3(1024), 0, q, ha);
+    IDQN_HIP_CHECK(hipGetLastError());
+    if (!poll) IDQN_HIP_CHECK(hipMemcpyAsync(actions_host_pinned, h->imany_action, (size_t)n * 4, hipMemcpyDeviceToHost, q));
+    return IDQN_OK;
+}
+
+extern "C" int idqn_iqn_act_host_many(idqn_handle_t h, int32_t which, const int32_t* heads_host, const void* states_host_pinned,
+                                      const float* taus_host_pinned, int32_t n, float* q_out_dev, int32_t* actions_host_pinned,
+                                      void* stream) {
+    IDQN_REQUIRE(h && heads_host && states_host_pinned && taus_host_pinned && q_out_dev && actions_host_pinned,
+                 "idqn_iqn_act_host_many: null pointer");
+    IDQN_REQUIRE(n >= 1 && n <= ACT_MANY_MAX, "idqn_iqn_act_host_many: n = %d, must be in [1, %d]", n, ACT_MANY_MAX);
+    IDQN_REQUIRE(which == 0 || which == 1, "idqn_iqn_act_host_many: which = %d", which);
+    IDQN_REQUIRE(h->iqn.N > 0, "idqn_iqn_act_host_many: the handle was created without quantile heads (cfg.n_quantiles)");
+    const int K = h->cfg.n_heads, N = h->iqn.N;
+    for (int e = 0; e < n; ++e) IDQN_REQUIRE(heads_host[e] >= 0 && heads_host[e] < K, "idqn_iqn_act_host_many: head %d of state %d", heads_host[e], e);
+    IDQN_REQUIRE(h->act_pending == 0, "idqn_iqn_act_host_many: an acting launch is still pending (idqn_act_host_end collects it)");
+    IDQN_REQUIRE(h->cfg.arch == IDQN_ARCH_CNN && !h->gc.on && h->F % 2 == 0 && h->J % 32 == 0 && h->J <= 512 &&
+                     h->cfg.n_actions <= 32 && N <= 64,
+                 "idqn_iqn_act_host_many: the single-state kernels take even F, J = 32 m <= 512, <= 32 actions, <= 64 fractions");
+    for (int i = 0; i < 3; ++i) {
+        int ks = 0, upt = 0;
+        int rc = act_many_conv_plan(h, i, &ks, &upt);
+        if (rc) return rc;
+    }
+    hipStream_t q = (hipStream_t)stream;
+    const size_t sb = (size_t)h->cfg.obs_h * h->cfg.obs_w * h->cfg.obs_c;  // bytes of one state
+    IDQN_REQUIRE(sb % 4 == 0, "idqn_iqn_act_host_many: %zu bytes per state", sb);
+    static const bool no_poll = getenv("IDQN_ACT_POLL") && atoi(getenv("IDQN_ACT_POLL")) == 0;
+    static const bool use_graph = !(getenv("IDQN_ACT_GRAPH") && atoi(getenv("IDQN_ACT_GRAPH")) == 0);
+    const bool poll = !no_poll;
+    if (!h->imany_block) {
+        const size_t block = sizeof(IqnActManyBlock) + ACT_MANY_MAX * sb + 64;
+        const long NP = N > 32 ? 64 : 32;
+        long fl[6] = {0, 0, 0, (long)ACT_MANY_MAX * 64 * IQN_ACT_EMBED, (long)ACT_MANY_MAX * h->F * NP, (long)ACT_MANY_MAX * 512 * h->J};
+        for (int i = 0; i < 3; ++i) fl[i] = (long)ACT_MANY_MAX * h->conv[i].OH * h->conv[i].OW * h->conv[i].CO;
+        uint8_t *pin = nullptr, *dev = nullptr;
+        float* f = nullptr;
+        int32_t *act = nullptr, *mail = nullptr, *mail_dev = nullptr;
+        // everything into locals first: a failure part-way frees what it got and leaves the handle as it was
+        auto alloc = [&]() -> int {
+            IDQN_HIP_CHECK(hipHostMalloc((void**)&pin, block, hipHostMallocDefault));
+            IDQN_HIP_CHECK(hipHostMalloc((void**)&mail, 256, hipHostMallocMapped | hipHostMallocCoherent));
+            memset(mail, 0, 256);
+            IDQN_HIP_CHECK(hipHostGetDevicePointer((void**)&mail_dev, mail, 0));
+            IDQN_HIP_CHECK(hipMalloc((void**)&f, (size_t)(fl[0] + fl[1] + fl[2] + fl[3] + fl[4] + fl[5]) * 4));
+            IDQN_HIP_CHECK(hipMalloc((void**)&act, 256));  // actions [32], then the two counters
+            IDQN_HIP_CHECK(hipMemset(act, 0, 256));
+            IDQN_HIP_CHECK(hipMalloc((void**)&dev, block));
+            IDQN_HIP_CHECK(hipStreamSynchronize(nullptr));  // (the memset runs on the null stream, which does not order against q)
+            return IDQN_OK;
+        };
+        if (const int arc = alloc()) {
+            if (pin) (void)hipHostFree(pin);
+            if (mail) (void)hipHostFree(mail);
+            if (f) (void)hipFree(f);
+            if (act) (void)hipFree(act);
+            if (dev) (void)hipFree(dev);
+            return arc;
+        }
+        h->owned.push_back((void*)f);
+        h->owned.push_back((void*)act);
+        h->owned.push_back((void*)dev);
+        h->imany_pin = pin; h->imany_mail = mail; h->imany_mail_dev = mail_dev;
+        h->imany_a[0] = f; h->imany_a[1] = f + fl[0]; h->imany_a[2] = h->imany_a[1] + fl[1]; h->imany_cos = h->imany_a[2] + fl[2];
+        h->imany_x = h->imany_cos + fl[3]; h->imany_part = h->imany_x + fl[4];
+        h->imany_action = act; h->imany_ctr = (unsigned*)(act + ACT_MANY_MAX);
+        h->imany_block = dev;
+    }
+    // the table (states grouped by head, in state order within a group), the fractions, the states
+    IqnActManyBlock* blk = (IqnActManyBlock*)h->imany_pin;
+    ActManyTable* tb = &blk->tab;
+    tb->n = n; tb->which = which; tb->pad = 0;
+    int ng = 0, pos = 0;
+    for (int k = 0; k < K && pos < n; ++k) {
+        const int start = pos;
+        for (int e = 0; e < n; ++e)
+            if (heads_host[e] == k) tb->order[pos++] = e;
+        if (pos > start) { tb->g_head[ng] = k; tb->g_start[ng] = start; tb->g_count[ng] = pos - start; ++ng; }
+    }
+    tb->n_groups = ng;
+    for (int e = 0; e < n; ++e) {
+        tb->head[e] = heads_host[e];
+        memcpy(blk->tau[e], taus_host_pinned + (size_t)e * N, (size_t)N * 4);
+    }
+    memcpy(h->imany_pin + sizeof(IqnActManyBlock), states_host_pinned, (size_t)n * sb);
+    int rc = IDQN_OK;
+    if (use_graph) {
+        auto key = std::make_tuple((int)n, (void*)q_out_dev, (void*)actions_host_pinned);
+        auto it = h->imany_graphs.find(key);
+        if (it == h->imany_graphs.end()) {
+            hipGraph_t graph = nullptr;
+            hipGraphExec_t exec = nullptr;
+            if (!h->act_stream) IDQN_HIP_CHECK(hipStreamCreateWithFlags(&h->act_stream, hipStreamNonBlocking));
+            IDQN_HIP_CHECK(hipStreamBeginCapture(h->act_stream, hipStreamCaptureModeRelaxed));
+            rc = iqn_act_many_chain(h, n, sb, q_out_dev, poll, actions_host_pinned, h->act_stream);
+            const hipError_t e = hipStreamEndCapture(h->act_stream, &graph);
+            if (rc) {  // (the graph of a chain that reported an error is not kept)
+                if (graph) (void)hipGraphDestroy(graph);
+                return rc;
+            }
+            IDQN_HIP_CHECK(e);
+            const hipError_t ei = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+            (void)hipGraphDestroy(graph);
+            IDQN_HIP_CHECK(ei);
+            it = h->imany_graphs.emplace(key, exec).first;
+        }
+        IDQN_HIP_CHECK(hipGraphLaunch(it->second, q));
+    } else if ((rc = iqn_act_many_chain(h, n, sb, q_out_dev, poll, actions_host_pinned, q))) {
+        return rc;
+    }
+    if (!poll) {
+        IDQN_HIP_CHECK(hipStreamSynchronize(q));
+        return IDQN_OK;
+    }
+    const unsigned want = ++h->imany_expected;
+    volatile int32_t* mail = h->imany_mail;
+    bool seen = false;
+    for (long spin = 0; spin < (1L << 34); ++spin) {  // as act_host_wait
+        if ((unsigned)mail[ACT_MANY_MAX] == want) { seen = true; break; }
+        __builtin_ia32_pause();
+        if ((spin & 0xfffff) == 0xfffff && hipStreamQuery(q) != hipErrorNotReady) {
+            seen = (unsigned)mail[ACT_MANY_MAX] == want;
+            break;
+        }
+    }
+    if (!seen) {  // resynchronise the counters, then report
+        IDQN_HIP_CHECK(hipStreamSynchronize(q));
+        IDQN_HIP_CHECK(hipMemcpy(&h->imany_expected, h->imany_ctr, 4, hipMemcpyDeviceToHost));
+        IDQN_HIP_CHECK(hipMemset(h->imany_ctr + 1, 0, 4));
+        IDQN_REQUIRE(false, "idqn_iqn_act_host_many: the acting launch finished without delivering its actions");
     }
     for (int e = 0; e < n; ++e) actions_host_pinned[e] = mail[e];
     return IDQN_OK;

@@ -16,6 +16,7 @@ F_GRADS_ONLY, F_PROFILE, F_STOP_AFTER_DENSE0, F_STOP_BEFORE_DENSE0_WGRAD, F_PROF
 FACTORED_DENSE0, FACTORED_REST = 1, 2
 DP_SIDE_STREAM, DP_UNIQUE_ID_BYTES = 1, 128
 E_INVALID, E_HIP, E_RANGE, E_ASSERT = -1, -2, -3, -4
+ACT_MANY_MAX, IQN_ACT_MANY_SC = 32, 4  # csrc/act_many_kernels.h, csrc/iqn_act_many_kernels.h: states per call / per Dense_0 chunk
 
 
 class HipExtensionError(RuntimeError):
@@ -91,6 +92,7 @@ SYMBOLS = {
     "idqn_act_host_many": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _P, _P, _P]),
     "idqn_iqn_act_host": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     "idqn_iqn_act_host_begin": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
+    "idqn_iqn_act_host_many": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P]),
     "idqn_debug_buffer": (C.c_int, [_P, C.c_char_p, C.POINTER(_P), C.POINTER(C.c_int64)]),
     "idqn_profile_read": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_char_p]),
     "idqn_profile_table": (C.c_int, [_P, C.c_char_p, C.c_int32]),

@@ -88,8 +88,8 @@ class iDQN(DeviceAgent):
     def best_actions(self, params, states, keys):
         """``[best_action(params, states[i], keys[i]).item() for i]`` as a host int array, for up to 32 host states (a
         vector of environments): every head is drawn from its own key as ``best_action`` draws it, and one device call
-        evaluates them all (``DeviceAgent._best_actions``).  Agents with an acting rule of their own (quantile heads,
-        head-parallel ranks) loop over it."""
+        evaluates them all (``DeviceAgent._best_actions``).  Agents with an acting rule of their own (head-parallel
+        ranks) loop over it; ``iIQN`` overrides this method with a device call of its own."""
         assert params is self.params or params is self.target_params
         assert len(states) == len(keys)
         if type(self).best_action is not iDQN.best_action:

@@ -217,3 +217,70 @@ class iIQN(iDQN):
                 return self._act_host(which, idx_params, src, taus, key)
         self._iqn_q(which, idx_params, state, taus, want_action=True, key=key)
         return self._action_out[0]
+
+    def best_actions(self, params, states, keys, taus=None):
+        """``[best_action(params, states[i], keys[i]).item() for i]`` as a host int64 array, for 1..32 host states: head i is
+        ``prng.randint(keys[i], 0, K)`` and fraction row i is what ``_act_host`` draws from ``keys[i]`` (``_tau_rng`` is left
+        alone; ``taus`` [n][N] overrides the draw).  States and fractions are staged into pinned blocks of this agent and ONE
+        C call (``idqn_iqn_act_host_many``) evaluates them all: row i of ``self._q_out[:n]`` and action i are, byte for
+        byte, the single-state call's.  A handle that answers ``E_INVALID`` once on an otherwise valid call makes this the
+        loop of single-state calls from then on: same actions, same rows."""
+        assert params is self.params or params is self.target_params
+        n = len(states)
+        if not 1 <= n <= 32 or len(keys) != n:
+            raise ValueError(f"best_actions takes 1..32 states and as many keys, got {n} and {len(keys)}")
+        N = self._n_quantiles
+        heads = [prng.randint(k, 0, self.n_networks) for k in keys]
+        if taus is None:
+            taus = np.stack([prng.generator(prng.split(k, 2)[1]).random((N, 1)).astype(np.float32)[:, 0] for k in keys])
+        return self._act_host_many(0 if params is self.params else 1, heads, states, taus)
+
+    def _act_host_many(self, which, heads, states, taus):
+        """Greedy actions (host int64 array [n]) of n <= 32 host states, state i on head ``heads[i]`` with the fractions
+        ``taus[i]`` [N]: ONE ``idqn_iqn_act_host_many`` call, or -- after that entry has refused this handle once -- the loop
+        of ``_act_host`` calls; the Q rows are left in ``self._q_out[:n]`` either way."""
+        heads = np.ascontiguousarray(np.asarray(heads, np.int32).reshape(-1))
+        n, N = int(heads.size), self._n_quantiles
+        if not 1 <= n <= 32 or len(states) != n:
+            raise ValueError(f"best_actions takes 1..32 states and as many heads, got {len(states)} and {n}")
+        if heads.min() < 0 or heads.max() >= self._K:
+            raise ValueError(f"best_actions: heads {heads.tolist()} outside [0, {self._K})")
+        taus = np.ascontiguousarray(taus, np.float32)
+        if taus.shape != (n, N):
+            raise ValueError(f"best_actions: fractions of shape {taus.shape}, expected {(n, N)}")
+        pending = getattr(self, "_act_in_flight", None)
+        if pending is not None:  # (a lazy single-state action nobody collected, as in _best_actions)
+            pending.item()
+        size = int(np.prod(self._obs))
+        srcs = [np.asarray(getattr(s, "tensor", s)) for s in states]
+        assert all(a.size == size for a in srcs), "best_actions takes single states"
+        self._ensure_handle(32)
+        if getattr(self, "_iqn_act_many_ok", True):
+            if not hasattr(self, "_iacts_pin"):
+                self._iacts_pin = torch.empty((32, size), dtype=torch.uint8).pin_memory()
+                self._iacts_pin_np = self._iacts_pin.numpy()
+                self._iacts_tau_pin = torch.empty((32, N), dtype=torch.float32).pin_memory()
+                self._iacts_tau_np = self._iacts_tau_pin.numpy()
+                self._iacts_out = torch.zeros(32, dtype=torch.int32).pin_memory()
+                self._iacts_out_np = self._iacts_out.numpy()
+            for i, a in enumerate(srcs):
+                self._iacts_pin_np[i] = a.reshape(-1)
+            self._iacts_tau_np[:n] = taus
+            rc = self._iqn_act_many_call(which, heads, n)
+            if rc != _hip.E_INVALID or self.__dict__.get("_iqn_act_many_ok") is not None:
+                _hip.check(rc, "idqn_iqn_act_host_many")
+                self._iqn_act_many_ok = True
+                return self._iacts_out_np[:n].astype(np.int64)
+            self._iqn_act_many_ok = False  # this handle acts one state at a time, from now on
+        actions, rows = np.empty(n, np.int64), []
+        for i in range(n):
+            actions[i] = int(self._act_host(which, int(heads[i]), srcs[i], taus[i], None).item())
+            rows.append(self._q_out[0].clone())
+        self._q_out[:n] = torch.stack(rows)
+        return actions
+
+    def _iqn_act_many_call(self, which, heads, n):
+        """The one C call of ``best_actions`` on the staged blocks: the library's return code."""
+        return _hip.lib().idqn_iqn_act_host_many(self._handle, int(which), heads.ctypes.data, C.c_void_p(self._iacts_pin.data_ptr()),
+                                                 C.c_void_p(self._iacts_tau_pin.data_ptr()), n, _hip.ptr(self._q_out),
+                                                 C.c_void_p(self._iacts_out.data_ptr()), _hip.current_stream())

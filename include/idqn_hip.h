@@ -290,6 +290,22 @@ int idqn_iqn_act_host_begin(idqn_handle_t h, int32_t which, int32_t head, const 
 int idqn_act_host_many(idqn_handle_t h, int32_t which, const int32_t* heads_host, const void* states_host_pinned, int32_t n,
                        float* q_out_dev, int32_t* actions_host_pinned, void* stream);
 
+/* The same for the i-IQN heads: the acting rule of idqn_iqn_act_host for n <= 32 host states at once, one head and N
+ * fractions each.  heads_host [n] (ordinary host memory, read before the call returns), n uint8 states and the fractions
+ * taus [n][N] in (0, 1) in PINNED host memory.  BYTE IDENTITY: row e of q_out_dev [n][A] and actions_host_pinned[e] are,
+ * byte for byte, what idqn_iqn_act_host gives for (which, heads_host[e], state e, taus[e]) -- the same kernels'
+ * arithmetic, operation for operation and in the same order, with a state dimension (csrc/iqn_act_many_kernels.h).
+ * States that share a head share one stream of that head's Dense_0 kernel.  Blocking; one linear hipGraph per (n, buffers)
+ * serves every head assignment, both parameter sets and every set of fractions (they travel as data); mailbox, counters
+ * and sequence number of its own; IDQN_ACT_GRAPH=0 and IDQN_ACT_POLL=0 as for idqn_act_host.
+ * IDQN_E_INVALID, before anything is enqueued: a null pointer, n outside [1, 32], which not 0 / 1, a head outside
+ * [0, K), a handle without quantile heads, an acting launch still pending (idqn_act_host_begin / idqn_iqn_act_host_begin),
+ * shapes outside the single-state i-IQN kernels (odd F, J not 32 m <= 512, A > 32, N > 64) or outside the acting conv
+ * kernels' plan.                                                                                                      */
+int idqn_iqn_act_host_many(idqn_handle_t h, int32_t which, const int32_t* heads_host, const void* states_host_pinned,
+                           const float* taus_host_pinned /* [n][N] */, int32_t n,
+                           float* q_out_dev /* [n][A] */, int32_t* actions_host_pinned /* [n] */, void* stream);
+
 /* Test / debug access to internal activation buffers by name (device pointer + byte size).        */
 int idqn_debug_buffer(idqn_handle_t h, const char* name, void** ptr_dev, int64_t* nbytes);
 /* Mean duration (ms) and launch count of the dominant kernel over the IDQN_F_PROFILE calls since
