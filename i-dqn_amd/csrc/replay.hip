@@ -206,3 +206,90 @@ extern "C" int replay_ring_regrow(const void* old_ring_dev, int64_t old_n, void*
     }
     return IDQN_OK;
 }
+
+// One vector-environment step of the segmented frame ring (VectorReplayBuffer: E time lines, each in a segment of its own
+// with its last stack-1 frames mirrored below the segment's first main slot, so that every stack is `stack` CONSECUTIVE slots
+// and the gathers above read it as they are): ONE pinned block -> ONE asynchronous copy -> ONE launch that scatters every new
+// frame to its one or two ring slots and every new element row to rows_dev.  Block layout (host and device staging alike):
+//   int32 [2 * REPLAY_STEP_MAX_WRITES]   (source frame index, destination ring slot) pairs, n_writes used
+//   int32 [REPLAY_STEP_MAX_ROWS]         destination element slots, n_rows used
+//   int32 [REPLAY_STEP_MAX_ROWS][8]      the new rows
+//   uint8 [n_in][frame_bytes]            the new frames (byte offset REPLAY_STEP_HEADER_BYTES, a multiple of 16)
+// Frame workgroups follow the tiers of k_replay_gather_stacked: 16 B per lane, else 4 B, else bytes.  Row workgroups are their
+// own (blockIdx.x >= n_writes * chunks).  Plain vector stores, no atomics; destinations are distinct (checked by the host
+// entry), and the kernel skips a pair or a row whose index is out of range rather than trusting the staged table.
+#define REPLAY_STEP_MAX_IN 32
+#define REPLAY_STEP_MAX_WRITES 64
+#define REPLAY_STEP_MAX_ROWS 128
+#define REPLAY_STEP_HEADER_BYTES ((2 * REPLAY_STEP_MAX_WRITES + REPLAY_STEP_MAX_ROWS + 8 * REPLAY_STEP_MAX_ROWS) * 4)
+
+__global__ __launch_bounds__(256) void k_replay_add_step(const uint8_t* __restrict__ block, uint8_t* __restrict__ ring,
+                                                         long n_frames, long frame_bytes, int32_t* __restrict__ rows_out,
+                                                         long capacity, int n_in, int n_writes, int n_rows, int chunks) {
+    const int32_t* table = reinterpret_cast<const int32_t*>(block);
+    const int frame_blocks = n_writes * chunks;
+    if ((int)blockIdx.x >= frame_blocks) {  // the element rows: one int32 per lane
+        const int i = ((int)blockIdx.x - frame_blocks) * 256 + threadIdx.x;
+        if (i >= n_rows * 8) return;
+        const long slot = table[2 * REPLAY_STEP_MAX_WRITES + (i >> 3)];
+        if (slot < 0 || slot >= capacity) return;
+        rows_out[slot * 8 + (i & 7)] = table[2 * REPLAY_STEP_MAX_WRITES + REPLAY_STEP_MAX_ROWS + i];
+        return;
+    }
+    const int w = blockIdx.x / chunks, c = blockIdx.x - w * chunks;
+    const long src_i = table[2 * w], dst_i = table[2 * w + 1];
+    if (src_i < 0 || src_i >= n_in || dst_i < 0 || dst_i >= n_frames) return;
+    const uint8_t* src = block + REPLAY_STEP_HEADER_BYTES + src_i * frame_bytes;
+    uint8_t* dst = ring + dst_i * frame_bytes;
+    const long tid = (long)c * 256 + threadIdx.x, nthr = (long)chunks * 256;
+    if ((frame_bytes & 15) == 0 && (((uintptr_t)block | (uintptr_t)ring) & 15) == 0) {
+        const uint4* s4 = reinterpret_cast<const uint4*>(src);
+        uint4* d4 = reinterpret_cast<uint4*>(dst);
+        for (long i = tid; i < (frame_bytes >> 4); i += nthr) d4[i] = s4[i];
+    } else if ((frame_bytes & 3) == 0 && (((uintptr_t)block | (uintptr_t)ring) & 3) == 0) {
+        const uint32_t* s1 = reinterpret_cast<const uint32_t*>(src);
+        uint32_t* d1 = reinterpret_cast<uint32_t*>(dst);
+        for (long i = tid; i < (frame_bytes >> 2); i += nthr) d1[i] = s1[i];
+    } else {
+        for (long i = tid; i < frame_bytes; i += nthr) dst[i] = src[i];
+    }
+}
+
+extern "C" int replay_add_step(void* frame_ring_dev, int64_t n_frames, int64_t frame_bytes, int32_t* rows_dev, int64_t capacity,
+                               const void* block_host_pinned, void* block_staging_dev, int32_t n_in, int32_t n_writes,
+                               int32_t n_rows, void* stream) {
+    IDQN_REQUIRE(frame_ring_dev && rows_dev && block_host_pinned && block_staging_dev, "replay_add_step: null pointer");
+    IDQN_REQUIRE(n_frames >= 1 && frame_bytes >= 1 && capacity >= 1 && n_in >= 0 && n_in <= REPLAY_STEP_MAX_IN && n_writes >= 0 &&
+                     n_writes <= REPLAY_STEP_MAX_WRITES && n_rows >= 0 && n_rows <= REPLAY_STEP_MAX_ROWS && n_writes + n_rows >= 1 &&
+                     (n_writes == 0 || n_in >= 1),
+                 "replay_add_step: n_frames = %ld, frame_bytes = %ld, capacity = %ld, n_in = %d (<= %d), n_writes = %d (<= %d), "
+                 "n_rows = %d (<= %d)", (long)n_frames, (long)frame_bytes, (long)capacity, n_in, REPLAY_STEP_MAX_IN, n_writes,
+                 REPLAY_STEP_MAX_WRITES, n_rows, REPLAY_STEP_MAX_ROWS);
+    IDQN_REQUIRE(((uintptr_t)block_host_pinned & 3) == 0 && ((uintptr_t)block_staging_dev & 3) == 0 && ((uintptr_t)rows_dev & 3) == 0,
+                 "replay_add_step: the blocks and rows_dev must be 4-byte aligned");
+    const int32_t* table = (const int32_t*)block_host_pinned;
+    for (int w = 0; w < n_writes; ++w) {
+        const int32_t src = table[2 * w], dst = table[2 * w + 1];
+        IDQN_REQUIRE(src >= 0 && src < n_in && dst >= 0 && dst < n_frames,
+                     "replay_add_step: write %d = (source %d, slot %d) outside n_in = %d / n_frames = %ld", w, src, dst, n_in,
+                     (long)n_frames);
+        for (int v = 0; v < w; ++v)
+            IDQN_REQUIRE(table[2 * v + 1] != dst, "replay_add_step: ring slot %d is written twice", dst);
+    }
+    const int32_t* row_slots = table + 2 * REPLAY_STEP_MAX_WRITES;
+    for (int r = 0; r < n_rows; ++r) {
+        IDQN_REQUIRE(row_slots[r] >= 0 && row_slots[r] < capacity, "replay_add_step: row %d goes to slot %d outside capacity = %ld", r,
+                     row_slots[r], (long)capacity);
+        for (int v = 0; v < r; ++v) IDQN_REQUIRE(row_slots[v] != row_slots[r], "replay_add_step: element slot %d is written twice", row_slots[r]);
+    }
+    IDQN_HIP_CHECK(hipMemcpyAsync(block_staging_dev, block_host_pinned, (size_t)REPLAY_STEP_HEADER_BYTES + (size_t)n_in * frame_bytes,
+                                  hipMemcpyHostToDevice, (hipStream_t)stream));
+    // a lane moves 16 B per iteration on the wide tier: two chunks cover an 84 x 84 frame in one iteration per lane
+    const int chunks = (int)std::min<long>(8, std::max<long>(1, (frame_bytes + 16 * 256 - 1) / (16 * 256)));
+    const int blocks = n_writes * chunks + cdiv((long)n_rows * 8, 256);
+    hipLaunchKernelGGL(k_replay_add_step, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)block_staging_dev,
+                       (uint8_t*)frame_ring_dev, (long)n_frames, (long)frame_bytes, rows_dev, (long)capacity, n_in, n_writes, n_rows,
+                       chunks);
+    IDQN_HIP_CHECK(hipGetLastError());
+    return IDQN_OK;
+}

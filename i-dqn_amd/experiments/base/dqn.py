@@ -81,3 +81,81 @@ class Trainer:
 def train(key, p: dict, agent, env, rb, save_fn=None):
     """Same call as the reference's ``train`` (``experiments/base/dqn.py:12``); returns (returns, lengths) per epoch."""
     return Trainer(key, p, agent, env, rb, save_fn).run()
+
+
+from slimdqn.sample_collection.utils import collect_vector_samples  # noqa: E402
+
+
+class VectorTrainer:
+    """``Trainer`` over a list of E environments stepped together: one vectorised acting call and one replay call per
+    vector step.  Every environment step still counts as one step of the schedule: ``total_steps`` advances once per
+    environment that stepped and ``update_online_params`` / ``update_target_params`` run at every one of those values
+    (after ``n_initial_samples``), so the gradient-step and target-update schedule per environment step is the single
+    trainer's.  Once an epoch's budget is spent, an environment that ends its episode waits (it is passed to the buffer as
+    ``None``) until all have: an epoch ends with every environment on an episode boundary."""
+
+    def __init__(self, key, p, agent, envs, rb, save_fn=None):
+        self.key, self.p, self.agent, self.envs, self.rb, self.save_fn = key, p, agent, list(envs), rb, save_fn
+        self.epsilon = linear_schedule(1.0, p["epsilon_end"], p["epsilon_duration"])
+        self.total_steps = 0
+        self.history = []  # one list of per-environment EpochStats per epoch
+
+    def _environment_step(self, active):
+        keys = []
+        for _ in range(sum(active)):  # the key is split once per environment that steps
+            self.key, explore_key = prng.split(self.key)
+            keys.append(explore_key)
+        return collect_vector_samples(keys, self.envs, self.agent, self.rb, self.p, self.epsilon, self.total_steps, active)
+
+    def _gradient_step(self):
+        self.agent.update_online_params(self.total_steps, self.rb)
+        updated, logs = self.agent.update_target_params(self.total_steps)
+        if updated:
+            self.p["wandb"].log({"n_training_steps": self.total_steps, **logs})
+
+    def run_epoch(self, index):
+        n_envs, budget, done = len(self.envs), self.p["n_training_steps_per_epoch"], 0
+        stats, active = [EpochStats() for _ in range(n_envs)], [True] * n_envs
+        self.history.append(stats)
+        while any(active):
+            rewards, ended = self._environment_step(active)
+            stepped = sum(active)
+            done += stepped
+            for i in range(n_envs):
+                if not active[i]:
+                    continue
+                stats[i].record(rewards[i])
+                if ended[i]:
+                    if done < budget:
+                        stats[i].open_episode()
+                    else:
+                        active[i] = False
+            for _ in range(stepped):
+                self.total_steps += 1
+                if self.total_steps > self.p["n_initial_samples"]:
+                    self._gradient_step()
+        if hasattr(self.rb, "flush_deferred"):
+            self.rb.flush_deferred()
+        returns, lengths = [r for s in stats for r in s.returns], [n for s in stats for n in s.lengths]
+        avg_return, avg_length = float(np.mean(returns)), float(np.mean(lengths))
+        print(f"\nEpoch {index}: Return {avg_return} averaged on {len(lengths)} episodes.\n", flush=True)
+        self.p["wandb"].log({"epoch": index, "n_training_steps": self.total_steps, "avg_return": avg_return,
+                             "avg_length_episode": avg_length})
+        if self.save_fn is not None:
+            self.save_fn(self.p, self._per_epoch("returns"), self._per_epoch("lengths"), self.agent.get_model())
+
+    def _per_epoch(self, field):
+        return [[x for s in epoch for x in getattr(s, field)] for epoch in self.history]
+
+    def run(self):
+        for env in self.envs:
+            env.reset()
+        for index in range(self.p["n_epochs"]):
+            self.run_epoch(index)
+        return self._per_epoch("returns"), self._per_epoch("lengths")
+
+
+def train_vector(key, p: dict, agent, envs, rb, save_fn=None):
+    """``train`` for a list of environments and a ``VectorReplayBuffer``; returns (returns, lengths) per epoch, the
+    environments' episodes concatenated in environment order."""
+    return VectorTrainer(key, p, agent, envs, rb, save_fn).run()

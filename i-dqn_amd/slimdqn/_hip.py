@@ -17,6 +17,9 @@ FACTORED_DENSE0, FACTORED_REST = 1, 2
 DP_SIDE_STREAM, DP_UNIQUE_ID_BYTES = 1, 128
 E_INVALID, E_HIP, E_RANGE, E_ASSERT = -1, -2, -3, -4
 ACT_MANY_MAX, IQN_ACT_MANY_SC = 32, 4  # csrc/act_many_kernels.h, csrc/iqn_act_many_kernels.h: states per call / per Dense_0 chunk
+# csrc/replay.hip, replay_add_step: frames in / ring writes / rows per call, and the byte offset of the frames in its block
+REPLAY_STEP_MAX_IN, REPLAY_STEP_MAX_WRITES, REPLAY_STEP_MAX_ROWS = 32, 64, 128
+REPLAY_STEP_HEADER_BYTES = 4 * (2 * REPLAY_STEP_MAX_WRITES + REPLAY_STEP_MAX_ROWS + 8 * REPLAY_STEP_MAX_ROWS)
 
 
 class HipExtensionError(RuntimeError):
@@ -103,6 +106,7 @@ SYMBOLS = {
                                        _P, _P]),
     "replay_gather": (C.c_int, [_P, C.c_int64, _P, C.c_int32, _P, _P, _P]),
     "replay_add_frame": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P]),
+    "replay_add_step": (C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
     "replay_ring_regrow": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P]),
     "replay_gather_scalars": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, _P, _P, _P]),
 }

@@ -79,3 +79,37 @@ def collect_single_sample(key, env, agent, rb: ReplayBuffer, p, epsilon_schedule
     if ended:
         env.reset()
     return reward, ended
+
+
+def _best_actions_fn(agent):
+    """``agent.best_actions``; an agent without one (no vectorised acting path) acts one state at a time: same actions."""
+    if hasattr(agent, "best_actions"):
+        return agent.best_actions
+    return lambda params, states, keys: [int(agent.best_action(params, s, key=k).item()) for s, k in zip(states, keys)]
+
+
+def collect_vector_samples(keys, envs, agent, rb, p, epsilon_schedule, n_training_steps: int, active=None):
+    """One step of every active environment into a ``VectorReplayBuffer``: ONE ``select_actions`` call, the E host steps, ONE
+    ``rb.add_many``; returns ``(rewards, ended)``, lists over all environments (``None`` / ``False`` for an inactive one, which
+    neither acts nor steps and is passed to ``add_many`` as ``None``).  ``keys`` holds one key per ACTIVE environment, in
+    order; environment ``i`` sees exactly what ``collect_single_sample(keys[i], envs[i], ...)`` would show it."""
+    idx = [i for i in range(len(envs)) if active is None or active[i]]
+    assert len(keys) == len(idx), "one key per active environment"
+    rewards, ended, transitions = [None] * len(envs), [False] * len(envs), [None] * len(envs)
+    if not idx:
+        return rewards, ended
+    observations = [envs[i].observation for i in idx]  # the frame BEFORE the action goes with it (utils.py:27-35)
+    actions = select_actions(_best_actions_fn(agent), agent.params, [envs[i].state for i in idx], keys, envs[idx[0]].n_actions,
+                             epsilon_schedule, n_training_steps)
+    for i, observation, action in zip(idx, observations, actions):
+        env = envs[i]
+        reward, absorbing = env.step(int(action))
+        ended[i] = bool(absorbing) or env.n_steps >= p["horizon"]
+        rewards[i] = reward
+        stored_reward = rb._clipping(reward) if rb._clipping is not None else reward
+        transitions[i] = TransitionElement(observation, int(action), stored_reward, absorbing, ended[i])
+    rb.add_many(transitions)
+    for i in idx:
+        if ended[i]:
+            envs[i].reset()
+    return rewards, ended

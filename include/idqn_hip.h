@@ -430,6 +430,25 @@ int replay_gather_scalars(const int32_t* action_store_dev, const float* reward_s
  * reused once the stream has passed this copy.  The host mirror also sends the new element rows and the sampled slot
  * indices this way (slot 0 of a byte range: frame_ring_dev = destination, frame_bytes = length).                      */
 int replay_add_frame(void* frame_ring_dev, int64_t slot, int64_t frame_bytes, const void* frame_host_pinned, void* stream);
+/* One vector-environment step of the SEGMENTED frame ring (VectorReplayBuffer; no reference counterpart: the reference collects
+ * from one environment): E time lines share one allocation [E * L][frame_bytes], L = S + stack - 1; frame t of environment e goes
+ * to slot e * L + (stack - 1) + t % S and, when t % S >= S - (stack - 1), also to the mirror slot e * L + t % S - (S - (stack - 1)),
+ * so that every stack is `stack` consecutive slots of one segment and replay_gather_stacked / idqn_learn_on_replay read the ring
+ * as they are (n_frames = E * L).  This call replaces E replay_add_frame calls and the row uploads: the caller fills ONE PINNED
+ * block, the call copies it asynchronously into block_staging_dev (same size, caller-owned) and ONE launch scatters every frame
+ * to its one or two slots and every row to rows_dev.  Block layout, both sides:
+ *   int32 [2 * 64]    (source frame index in the block, destination ring slot) pairs, n_writes <= 64 used
+ *   int32 [128]       destination element slots, n_rows <= 128 used (the row cap: a step with more rows is split by the caller)
+ *   int32 [128][8]    the new rows (replay_gather_stacked documents the row)
+ *   uint8 [n_in][frame_bytes] the n_in <= 32 new frames, from byte 5120 on
+ * so the block holds 5120 + 32 * frame_bytes bytes and 5120 + n_in * frame_bytes travel.  n_writes + n_rows >= 1.  Frames move
+ * 16 B per lane when frame_bytes % 16 == 0 and both buffers are 16-byte aligned, else 4 B, else bytes.  IDQN_E_INVALID before
+ * anything is enqueued: a null pointer, a count outside its limit, a source index outside [0, n_in), a ring slot outside
+ * [0, n_frames), an element slot outside [0, capacity), a destination named twice.  The pinned block may be refilled once the
+ * stream has passed this call.                                                                                               */
+int replay_add_step(void* frame_ring_dev, int64_t n_frames, int64_t frame_bytes, int32_t* rows_dev, int64_t capacity,
+                    const void* block_host_pinned, void* block_staging_dev, int32_t n_in, int32_t n_writes, int32_t n_rows,
+                    void* stream);
 /* Growth of the frame ring (no reference counterpart: the reference's host dict grows by itself,
  * replay_buffer.py:206-213): the live frames, transition indices [first_t, first_t + count), are copied from slot
  * t % old_n of the old ring to slot t % new_n of the new one (count <= old_n <= new_n, distinct buffers).             */
