@@ -29,6 +29,7 @@
 #include "fc_par_kernels.h"
 #include "iqn_kernels.h"
 #include "gcnn_kernels.h"
+#include "fc_act_many_kernels.h"
 #include "dp_internal.h"
 
 namespace {
@@ -310,6 +311,8 @@ struct idqn_handle_s {
     unsigned* many_ctr = nullptr;       // device side: {sequence number, finished workgroups}
     unsigned many_expected = 0;         // sequence number the next idqn_act_host_many call waits for
     std::map<std::tuple<int, void*, void*>, hipGraphExec_t> many_graphs;  // (n, q out, host actions)
+    // idqn_act_host_many_fc (fc_act_many_kernels.h) uses the same fields -- no handle is in both domains: f32 states in the
+    // block for fc; many_a = the conv activations of the general-shape cnn; many_part = the dense ping-pong rows [32][2][dmax]
     // idqn_iqn_act_host_many (iqn_act_many_kernels.h): buffers, mailbox and counters of its own, as above.
     uint8_t* imany_pin = nullptr;       // pinned block {IqnActManyBlock, states [32][state bytes]} (hipHostMalloc)
     uint8_t* imany_block = nullptr;     // its device copy
@@ -3061,6 +3064,133 @@ extern "C" int idqn_act_host_many(idqn_handle_t h, int32_t which, const int32_t*
         IDQN_HIP_CHECK(hipMemcpy(&h->many_expected, h->many_ctr, 4, hipMemcpyDeviceToHost));
         IDQN_HIP_CHECK(hipMemset(h->many_ctr + 1, 0, 4));
         IDQN_REQUIRE(false, "idqn_act_host_many: the acting launch finished without delivering its actions");
+    }
+    for (int e = 0; e < n; ++e) actions_host_pinned[e] = mail[e];
+    return IDQN_OK;
+}
+
+// idqn_act_host_many for the handles it refuses (fc_act_many_kernels.h): MLP handles run ONE launch behind the copy node
+// (k_fc_act_many1 when every width fits its LDS rows, as the single-state path picks k_fc_q1; k_fc_act_many otherwise);
+// general-shape cnn handles run three k_gconv_fwd_many launches and k_fc_act_many on the flattened features.
+static int fc_act_many_chain(idqn_handle_t h, int n, size_t state_bytes, float* q_out_dev, bool poll, int32_t* actions_host_pinned,
+                             hipStream_t q) {
+    IDQN_HIP_CHECK(hipMemcpyAsync(h->many_block, h->many_pin, sizeof(ActManyTable) + (size_t)n * state_bytes, hipMemcpyHostToDevice, q));
+    ActManyNets nets;
+    nets.tab = (const ActManyTable*)h->many_block; nets.online = h->online; nets.target = h->target; nets.pstride = h->L.head_stride;
+    const uint8_t* states = h->many_block + sizeof(ActManyTable);
+    FcActManyArgs a;
+    a.net = h->fc; a.nets = nets; a.s = (const float*)states; a.s_ld = h->fc.d[0]; a.ws = h->many_part; a.q_out = q_out_dev;
+    a.action = h->many_action; a.mail = poll ? h->many_mail_dev : nullptr; a.ctr = h->many_ctr; a.n = n;
+    if (h->gc.on) {
+        for (int i = 0; i < 3; ++i) {
+            const ConvL& l = h->conv[i];
+            GConvManyArgs g;
+            g.nets = nets; g.in_u8 = i == 0 ? states : nullptr; g.in = i == 0 ? nullptr : h->many_a[i - 1]; g.out = h->many_a[i];
+            g.w_off = l.w_off; g.b_off = l.b_off; g.IH = l.IH; g.IW = l.IW; g.CI = l.CI; g.OH = l.OH; g.OW = l.OW; g.CO = l.CO;
+            g.KS = l.K; g.S = l.S; g.PLh = l.PLh; g.PLw = l.PLw;
+            hipLaunchKernelGGL(k_gconv_fwd_many, dim3(ggrid((long)l.OH * l.OW * l.CO), n), dim3(256), 0, q, g);
+        }
+        a.s = h->many_a[2];  // row stride = flattened feature count = d[0]
+        hipLaunchKernelGGL(k_fc_act_many, dim3(n), dim3(256), 0, q, a);
+    } else if (h->fc.dmax <= FC_MAX_WIDTH) {
+        hipLaunchKernelGGL(k_fc_act_many1, dim3(n), dim3(512), 0, q, a);
+    } else {
+        hipLaunchKernelGGL(k_fc_act_many, dim3(n), dim3(256), 0, q, a);
+    }
+    IDQN_HIP_CHECK(hipGetLastError());
+    if (!poll) IDQN_HIP_CHECK(hipMemcpyAsync(actions_host_pinned, h->many_action, (size_t)n * 4, hipMemcpyDeviceToHost, q));
+    return IDQN_OK;
+}
+
+extern "C" int idqn_act_host_many_fc(idqn_handle_t h, int32_t which, const int32_t* heads_host, const void* states_host_pinned, int32_t n,
+                                     float* q_out_dev, int32_t* actions_host_pinned, void* stream) {
+    IDQN_REQUIRE(h && heads_host && states_host_pinned && q_out_dev && actions_host_pinned, "idqn_act_host_many_fc: null pointer");
+    IDQN_REQUIRE(n >= 1 && n <= ACT_MANY_MAX, "idqn_act_host_many_fc: n = %d, must be in [1, %d]", n, ACT_MANY_MAX);
+    IDQN_REQUIRE(which == 0 || which == 1, "idqn_act_host_many_fc: which = %d", which);
+    const int K = h->cfg.n_heads;
+    for (int e = 0; e < n; ++e) IDQN_REQUIRE(heads_host[e] >= 0 && heads_host[e] < K, "idqn_act_host_many_fc: head %d of state %d", heads_host[e], e);
+    IDQN_REQUIRE(h->act_pending == 0, "idqn_act_host_many_fc: an idqn_act_host_begin is still waiting for its _end");
+    IDQN_REQUIRE(h->iqn.N == 0, "idqn_act_host_many_fc: the handle was created with quantile heads");
+    const bool cnn = h->cfg.arch == IDQN_ARCH_CNN;
+    IDQN_REQUIRE(h->cfg.arch == IDQN_ARCH_FC || (cnn && h->gc.on),
+                 "idqn_act_host_many_fc: the handle runs the MFMA cnn path (idqn_act_host_many serves it)");
+    hipStream_t q = (hipStream_t)stream;
+    // bytes of one state: uint8 pixels (general-shape cnn) or float32 features (fc)
+    const size_t sb = cnn ? (size_t)h->cfg.obs_h * h->cfg.obs_w * h->cfg.obs_c : (size_t)h->fc.d[0] * 4;
+    static const bool no_poll = getenv("IDQN_ACT_POLL") && atoi(getenv("IDQN_ACT_POLL")) == 0;
+    static const bool use_graph = !(getenv("IDQN_ACT_GRAPH") && atoi(getenv("IDQN_ACT_GRAPH")) == 0);
+    const bool poll = !no_poll;
+    if (!h->many_block) {
+        const size_t block = sizeof(ActManyTable) + ACT_MANY_MAX * sb + 64;
+        long fl[4] = {0, 0, 0, (long)ACT_MANY_MAX * 2 * h->fc.dmax};
+        if (cnn)
+            for (int i = 0; i < 3; ++i) fl[i] = (long)ACT_MANY_MAX * h->conv[i].OH * h->conv[i].OW * h->conv[i].CO;
+        uint8_t *pin = nullptr, *dev = nullptr;
+        float* f = nullptr;
+        int32_t *act = nullptr, *mail = nullptr;
+        IDQN_HIP_CHECK(hipHostMalloc((void**)&pin, block, hipHostMallocDefault));
+        h->many_pin = pin;
+        IDQN_HIP_CHECK(hipHostMalloc((void**)&mail, 256, hipHostMallocMapped | hipHostMallocCoherent));
+        h->many_mail = mail;
+        memset(mail, 0, 256);
+        IDQN_HIP_CHECK(hipHostGetDevicePointer((void**)&h->many_mail_dev, mail, 0));
+        IDQN_HIP_CHECK(hipMalloc((void**)&f, (size_t)(fl[0] + fl[1] + fl[2] + fl[3]) * 4));
+        h->owned.push_back((void*)f);
+        IDQN_HIP_CHECK(hipMalloc((void**)&act, 256));  // actions [32], then the two counters
+        h->owned.push_back((void*)act);
+        IDQN_HIP_CHECK(hipMemset(act, 0, 256));
+        IDQN_HIP_CHECK(hipMalloc((void**)&dev, block));
+        h->owned.push_back((void*)dev);
+        IDQN_HIP_CHECK(hipStreamSynchronize(nullptr));  // (the memset runs on the null stream, which does not order against q)
+        h->many_a[0] = f; h->many_a[1] = f + fl[0]; h->many_a[2] = h->many_a[1] + fl[1]; h->many_part = h->many_a[2] + fl[2];
+        h->many_action = act; h->many_ctr = (unsigned*)(act + ACT_MANY_MAX);
+        h->many_block = dev;
+    }
+    ActManyTable* tb = (ActManyTable*)h->many_pin;  // (no groups here: every state is a workgroup of its own)
+    tb->n = n; tb->n_groups = 0; tb->which = which; tb->pad = 0;
+    for (int e = 0; e < n; ++e) tb->head[e] = heads_host[e];
+    memcpy(h->many_pin + sizeof(ActManyTable), states_host_pinned, (size_t)n * sb);
+    int rc = IDQN_OK;
+    if (use_graph) {
+        auto key = std::make_tuple((int)n, (void*)q_out_dev, (void*)actions_host_pinned);
+        auto it = h->many_graphs.find(key);
+        if (it == h->many_graphs.end()) {
+            hipGraph_t graph = nullptr;
+            hipGraphExec_t exec = nullptr;
+            if (!h->act_stream) IDQN_HIP_CHECK(hipStreamCreateWithFlags(&h->act_stream, hipStreamNonBlocking));
+            IDQN_HIP_CHECK(hipStreamBeginCapture(h->act_stream, hipStreamCaptureModeRelaxed));
+            rc = fc_act_many_chain(h, n, sb, q_out_dev, poll, actions_host_pinned, h->act_stream);
+            const hipError_t e = hipStreamEndCapture(h->act_stream, &graph);
+            if (rc) return rc;
+            IDQN_HIP_CHECK(e);
+            IDQN_HIP_CHECK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+            IDQN_HIP_CHECK(hipGraphDestroy(graph));
+            it = h->many_graphs.emplace(key, exec).first;
+        }
+        IDQN_HIP_CHECK(hipGraphLaunch(it->second, q));
+    } else if ((rc = fc_act_many_chain(h, n, sb, q_out_dev, poll, actions_host_pinned, q))) {
+        return rc;
+    }
+    if (!poll) {
+        IDQN_HIP_CHECK(hipStreamSynchronize(q));
+        return IDQN_OK;
+    }
+    const unsigned want = ++h->many_expected;
+    volatile int32_t* mail = h->many_mail;
+    bool seen = false;
+    for (long spin = 0; spin < (1L << 34); ++spin) {  // as act_host_wait
+        if ((unsigned)mail[ACT_MANY_MAX] == want) { seen = true; break; }
+        __builtin_ia32_pause();
+        if ((spin & 0xfffff) == 0xfffff && hipStreamQuery(q) != hipErrorNotReady) {
+            seen = (unsigned)mail[ACT_MANY_MAX] == want;
+            break;
+        }
+    }
+    if (!seen) {  // resynchronise the counters, then report
+        IDQN_HIP_CHECK(hipStreamSynchronize(q));
+        IDQN_HIP_CHECK(hipMemcpy(&h->many_expected, h->many_ctr, 4, hipMemcpyDeviceToHost));
+        IDQN_HIP_CHECK(hipMemset(h->many_ctr + 1, 0, 4));
+        IDQN_REQUIRE(false, "idqn_act_host_many_fc: the acting launch finished without delivering its actions");
     }
     for (int e = 0; e < n; ++e) actions_host_pinned[e] = mail[e];
     return IDQN_OK;

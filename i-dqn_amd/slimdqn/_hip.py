@@ -93,6 +93,7 @@ SYMBOLS = {
     "idqn_act_host_begin": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "idqn_act_host_end": (C.c_int, [_P, _P, _P]),
     "idqn_act_host_many": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _P, _P, _P]),
+    "idqn_act_host_many_fc": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _P, _P, _P]),
     "idqn_iqn_act_host": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     "idqn_iqn_act_host_begin": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     "idqn_iqn_act_host_many": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P]),

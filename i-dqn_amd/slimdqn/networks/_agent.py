@@ -311,11 +311,12 @@ class DeviceAgent:
 
     def _best_actions(self, which, heads, states):
         """Greedy actions (host int array [n], first maximum on ties) of n <= 32 host states, state i on head ``heads[i]``:
-        the states are staged into one pinned block and ONE C call (``idqn_act_host_many``) uploads them, runs the
-        single-state arithmetic per state with the Dense_0 stream shared among the states of a head and brings the n
-        actions back; the Q rows are left in ``self._q_out[:n]``.  A handle outside that call's domain (MLP, general-shape
-        cnn, quantile heads, ...) answers ``E_INVALID`` once, and from then on this is a loop of ``_best_action``: same
-        actions, same Q rows."""
+        the states are staged into one pinned block and ONE C call uploads them, runs the single-state arithmetic per state
+        and brings the n actions back; the Q rows are left in ``self._q_out[:n]``.  ``idqn_act_host_many`` serves the MFMA
+        cnn handles (the Dense_0 stream shared among the states of a head); a handle outside its domain answers
+        ``E_INVALID`` once and ``idqn_act_host_many_fc`` (MLP, general-shape cnn) is tried under a flag of its own.  A
+        handle both refuse (quantile heads, ...) acts through a loop of ``_best_action`` from then on: same actions, same
+        Q rows."""
         heads = np.ascontiguousarray(np.asarray(heads, np.int32).reshape(-1))
         n = int(heads.size)
         if not 1 <= n <= 32 or len(states) != n:
@@ -329,22 +330,27 @@ class DeviceAgent:
         srcs = [np.asarray(getattr(s, "tensor", s)) for s in states]
         assert all(a.size == size for a in srcs), "best_actions takes single states"
         self._ensure_handle(32)
-        if getattr(self, "_act_many_ok", True):
-            if not hasattr(self, "_acts_pin"):
-                dt = torch.uint8 if self._arch == "cnn" else torch.float32
-                self._acts_pin = torch.empty((32, size), dtype=dt).pin_memory()
-                self._acts_pin_np = self._acts_pin.numpy()
-                self._acts_out = torch.zeros(32, dtype=torch.int32).pin_memory()
-                self._acts_out_np = self._acts_out.numpy()
-            for i, a in enumerate(srcs):
-                self._acts_pin_np[i] = a.reshape(-1)  # casts like the array conversion of the reference's jit would
-            rc = _hip.lib().idqn_act_host_many(self._handle, int(which), heads.ctypes.data, C.c_void_p(self._acts_pin.data_ptr()), n,
-                                               _hip.ptr(self._q_out), C.c_void_p(self._acts_out.data_ptr()), _hip.current_stream())
-            if rc != _hip.E_INVALID or self.__dict__.get("_act_many_ok") is not None:
-                _hip.check(rc, "idqn_act_host_many")
-                self._act_many_ok = True
+        staged = False
+        for flag, entry in (("_act_many_ok", "idqn_act_host_many"), ("_act_many_fc_ok", "idqn_act_host_many_fc")):
+            if not getattr(self, flag, True):
+                continue
+            if not staged:
+                if not hasattr(self, "_acts_pin"):
+                    dt = torch.uint8 if self._arch == "cnn" else torch.float32  # the arch's dtype: pixels or features
+                    self._acts_pin = torch.empty((32, size), dtype=dt).pin_memory()
+                    self._acts_pin_np = self._acts_pin.numpy()
+                    self._acts_out = torch.zeros(32, dtype=torch.int32).pin_memory()
+                    self._acts_out_np = self._acts_out.numpy()
+                for i, a in enumerate(srcs):
+                    self._acts_pin_np[i] = a.reshape(-1)  # casts like the array conversion of the reference's jit would
+                staged = True
+            rc = getattr(_hip.lib(), entry)(self._handle, int(which), heads.ctypes.data, C.c_void_p(self._acts_pin.data_ptr()), n,
+                                            _hip.ptr(self._q_out), C.c_void_p(self._acts_out.data_ptr()), _hip.current_stream())
+            if rc != _hip.E_INVALID or self.__dict__.get(flag) is not None:
+                _hip.check(rc, entry)
+                setattr(self, flag, True)
                 return self._acts_out_np[:n].astype(np.int64)
-            self._act_many_ok = False  # this handle acts one state at a time, from now on
+            setattr(self, flag, False)  # this entry does not serve the handle, from now on
         actions, rows = np.empty(n, np.int64), []
         for i in range(n):
             actions[i] = int(self._best_action(which, int(heads[i]), srcs[i]).item())

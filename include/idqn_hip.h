@@ -290,6 +290,20 @@ int idqn_iqn_act_host_begin(idqn_handle_t h, int32_t which, int32_t head, const 
 int idqn_act_host_many(idqn_handle_t h, int32_t which, const int32_t* heads_host, const void* states_host_pinned, int32_t n,
                        float* q_out_dev, int32_t* actions_host_pinned, void* stream);
 
+/* The same call for the handles idqn_act_host_many refuses: arch == IDQN_ARCH_FC with any widths, and general-shape cnn
+ * handles (reference ops: idqn.py:126-131 best_action, utils.py:8-21 select_action -- the LunarLander experiment is fc,
+ * [100, 100], K = 3).  Signature and contract of idqn_act_host_many; the n states in PINNED host memory are float32 rows
+ * [n][obs] for fc and uint8 pixels for the cnn.  Row e of q_out_dev [n][A] and actions_host_pinned[e] are, byte for byte,
+ * what idqn_act_host gives for (which, heads_host[e], state e): one workgroup per state runs that path's arithmetic in its
+ * order (csrc/fc_act_many_kernels.h), one launch for fc, four for the general-shape cnn.  Blocking; one linear hipGraph
+ * per (n, buffers), heads and `which` travel as data; a mailbox and sequence counter that are not the single-state
+ * path's; IDQN_ACT_GRAPH=0 and IDQN_ACT_POLL=0 as for idqn_act_host.  IDQN_E_INVALID, before anything is enqueued or
+ * allocated on the device: a null pointer, n outside [1, 32], which not 0 / 1, a head outside [0, K), an
+ * idqn_act_host_begin still pending, a handle with quantile heads, a handle of the MFMA cnn path (idqn_act_host_many
+ * serves those).                                                                                                        */
+int idqn_act_host_many_fc(idqn_handle_t h, int32_t which, const int32_t* heads_host, const void* states_host_pinned, int32_t n,
+                          float* q_out_dev, int32_t* actions_host_pinned, void* stream);
+
 /* The same for the i-IQN heads: the acting rule of idqn_iqn_act_host for n <= 32 host states at once, one head and N
  * fractions each.  heads_host [n] (ordinary host memory, read before the call returns), n uint8 states and the fractions
  * taus [n][N] in (0, 1) in PINNED host memory.  BYTE IDENTITY: row e of q_out_dev [n][A] and actions_host_pinned[e] are,
