@@ -16,6 +16,7 @@
 //
 // Heads, groups and the parameter set are DATA: ActManyTable sits at the head of the pinned block whose tail holds the
 // states and is uploaded by the chain's one copy node, so a captured chain serves every head assignment and both sets.
+// The actions reach the host through act_many_deliver below, shared with iqn_act_many_kernels.h and fc_act_many_kernels.h.
 #pragma once
 #include "common.h"
 
@@ -40,6 +41,24 @@ struct ActManyNets {
 };
 __device__ __forceinline__ const float* act_many_params(const ActManyNets& m, int head) {
     return (m.tab->which ? m.target : m.online) + (long)head * m.pstride;
+}
+
+// The end of every many-state chain, called by ONE thread of each of the n final workgroups after it has stored its state's
+// action.  mail: {action[ACT_MANY_MAX], sequence number} in mapped, coherent host memory; ctr: the device counters behind it,
+// ctr[0] the sequence number, ctr[1] the workgroups that have finished.  The workgroup that finishes last (an atomic count of
+// the finished ones) copies the n actions into the mailbox, then the sequence number that announces them, and clears the count.
+__device__ __forceinline__ void act_many_deliver(int32_t* action, volatile int32_t* mail, unsigned* ctr, int n) {
+    __threadfence();  // this workgroup's action is visible device-wide before it is counted
+    const unsigned done = atomicAdd(&ctr[1], 1u);
+    if (done == (unsigned)n - 1u) {
+        __threadfence();
+        for (int i = 0; i < n; ++i) mail[i] = __hip_atomic_load(&action[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        ctr[1] = 0u;
+        const unsigned sq = ctr[0] + 1u;
+        ctr[0] = sq;
+        __threadfence_system();  // the actions are visible to the host before the number that announces them
+        mail[ACT_MANY_MAX] = (int32_t)sq;
+    }
 }
 
 struct ActManyConvArgs {
@@ -185,13 +204,10 @@ struct ActManyHeadArgs {
     int NP, J, A, n;
     float* q_out;       // [n][A]
     int32_t* action;    // [n]
-    // host mailbox of idqn_act_host_many or nullptr: {action[ACT_MANY_MAX], sequence number} in mapped, coherent host
-    // memory, and the device counters behind it: ctr[0] the sequence number, ctr[1] the workgroups that have finished.
-    volatile int32_t* mail;
+    volatile int32_t* mail;  // host mailbox or nullptr, and its device counters: act_many_deliver
     unsigned* ctr;
 };
-// k_act_head, one workgroup of 1024 per state.  The workgroup that finishes last (an atomic count of the finished ones)
-// copies the n actions into the mailbox, then the sequence number that announces them, and clears the count.
+// k_act_head, one workgroup of 1024 per state; the actions leave through act_many_deliver.
 __global__ __launch_bounds__(1024) void k_act_many_head(ActManyHeadArgs a) {
     __shared__ float hp[4][512];
     __shared__ float hs[512];
@@ -238,18 +254,6 @@ __global__ __launch_bounds__(1024) void k_act_many_head(ActManyHeadArgs a) {
         for (int ac = 1; ac < a.A; ++ac)
             if (qs[ac] > bv) { bv = qs[ac]; best = ac; }
         a.action[e] = best;
-        if (a.mail) {
-            __threadfence();  // this workgroup's action is visible device-wide before it is counted
-            const unsigned done = atomicAdd(&a.ctr[1], 1u);
-            if (done == (unsigned)a.n - 1u) {
-                __threadfence();
-                for (int i = 0; i < a.n; ++i) a.mail[i] = __hip_atomic_load(&a.action[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                a.ctr[1] = 0u;
-                const unsigned sq = a.ctr[0] + 1u;
-                a.ctr[0] = sq;
-                __threadfence_system();  // the actions are visible to the host before the number that announces them
-                a.mail[ACT_MANY_MAX] = (int32_t)sq;
-            }
-        }
+        if (a.mail) act_many_deliver(a.action, a.mail, a.ctr, a.n);
     }
 }

@@ -18,6 +18,7 @@
 // Heads and the parameter set are DATA: ActManyTable (act_many_kernels.h; n, which and head[] are used) sits at the head of
 // the pinned block whose tail holds the states -- f32 rows for fc, uint8 pixels for the general-shape cnn -- and is
 // uploaded by the chain's one copy node, so a captured chain serves every head assignment and both sets.
+// The actions reach the host through act_many_deliver (act_many_kernels.h).
 #pragma once
 #include "act_many_kernels.h"
 #include "fc_kernels.h"
@@ -30,16 +31,13 @@ struct FcActManyArgs {
     float* ws;           // k_fc_act_many only: [n][2][dmax]
     float* q_out;        // [n][A]
     int32_t* action;     // [n]
-    // host mailbox {action[ACT_MANY_MAX], sequence number} or nullptr, and ctr[0] the sequence number, ctr[1] the
-    // workgroups that have finished: as ActManyHeadArgs
-    volatile int32_t* mail;
+    volatile int32_t* mail;  // host mailbox or nullptr, and its device counters: act_many_deliver
     unsigned* ctr;
     int n;
 };
 
 // Thread 0 of workgroup e, after the A outputs of its state are in q (LDS or global, written before a barrier): the first
-// maximum by the rule of k_argmax_rows, then the tail of k_act_many_head -- the workgroup that finishes last copies the n
-// actions into the mailbox, then the sequence number that announces them, and clears the count.
+// maximum by the rule of k_argmax_rows, then act_many_deliver (act_many_kernels.h).
 __device__ __forceinline__ void fc_act_many_tail(const FcActManyArgs& a, int e, const float* q, int A) {
     int best = 0;
     float bv = q[0];
@@ -48,19 +46,7 @@ __device__ __forceinline__ void fc_act_many_tail(const FcActManyArgs& a, int e, 
         if (v > bv) { bv = v; best = ac; }
     }
     a.action[e] = best;
-    if (a.mail) {
-        __threadfence();  // this workgroup's action is visible device-wide before it is counted
-        const unsigned done = atomicAdd(&a.ctr[1], 1u);
-        if (done == (unsigned)a.n - 1u) {
-            __threadfence();
-            for (int i = 0; i < a.n; ++i) a.mail[i] = __hip_atomic_load(&a.action[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            a.ctr[1] = 0u;
-            const unsigned sq = a.ctr[0] + 1u;
-            a.ctr[0] = sq;
-            __threadfence_system();  // the actions are visible to the host before the number that announces them
-            a.mail[ACT_MANY_MAX] = (int32_t)sq;
-        }
-    }
+    if (a.mail) act_many_deliver(a.action, a.mail, a.ctr, a.n);
 }
 
 // k_fc_q1 per state: grid (n), every layer width <= FC_MAX_WIDTH

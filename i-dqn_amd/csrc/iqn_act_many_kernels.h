@@ -18,6 +18,7 @@
 //
 // Heads, groups, the parameter set and the fractions are DATA: the pinned block {ActManyTable, tau [32][64], states} is
 // uploaded by the chain's one copy node, so a captured chain serves every head assignment, both sets and every tau.
+// The actions reach the host through act_many_deliver (act_many_kernels.h).
 #pragma once
 #include "act_many_kernels.h"
 #include "iqn_act_kernels.h"
@@ -178,14 +179,10 @@ struct IqnActManyHeadArgs {
     int NRG, J, A, N, NP, n;
     float* q_out;       // [n][A]
     int32_t* action;    // [n]
-    // host mailbox of idqn_iqn_act_host_many or nullptr: {action[ACT_MANY_MAX], sequence number} in mapped, coherent host
-    // memory, and the device counters behind it: ctr[0] the sequence number, ctr[1] the workgroups that have finished.
-    volatile int32_t* mail;
+    volatile int32_t* mail;  // host mailbox or nullptr, and its device counters: act_many_deliver
     unsigned* ctr;
 };
-// k_iqn_act_head, one workgroup of 16 waves per state.  The workgroup that finishes last (an atomic count of the finished
-// ones) copies the n actions into the mailbox, then the sequence number that announces them, and clears the count -- as
-// k_act_many_head.
+// k_iqn_act_head, one workgroup of 16 waves per state; the actions leave through act_many_deliver (act_many_kernels.h).
 template <int MT>
 __global__ __launch_bounds__(1024) void k_iqn_act_many_head(IqnActManyHeadArgs a) {
     __shared__ float sl[8][16][64];
@@ -273,18 +270,6 @@ __global__ __launch_bounds__(1024) void k_iqn_act_many_head(IqnActManyHeadArgs a
         for (int ac = 1; ac < a.A; ++ac)
             if (qs[ac] > bv) { bv = qs[ac]; best = ac; }
         a.action[e] = best;
-        if (a.mail) {
-            __threadfence();  // this workgroup's action is visible device-wide before it is counted
-            const unsigned done = atomicAdd(&a.ctr[1], 1u);
-            if (done == (unsigned)a.n - 1u) {
-                __threadfence();
-                for (int i = 0; i < a.n; ++i) a.mail[i] = __hip_atomic_load(&a.action[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                a.ctr[1] = 0u;
-                const unsigned sq = a.ctr[0] + 1u;
-                a.ctr[0] = sq;
-                __threadfence_system();  // the actions are visible to the host before the number that announces them
-                a.mail[ACT_MANY_MAX] = (int32_t)sq;
-            }
-        }
+        if (a.mail) act_many_deliver(a.action, a.mail, a.ctr, a.n);
     }
 }

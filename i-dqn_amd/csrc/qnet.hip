@@ -44,6 +44,10 @@ struct ConvL {
 // the few run-time switches of the shipped library (INTEGRATION.md lists them)
 bool plan_print() { static const bool on = getenv("IDQN_PLAN_PRINT") != nullptr; return on; }  // launch plans to stderr
 bool act_generic() { static const bool on = getenv("IDQN_ACT_GENERIC") != nullptr; return on; }  // acting through the batched forward
+// the acting entries' two switches, read once per process: IDQN_ACT_POLL=0 collects actions with a device-to-host copy and a
+// stream synchronisation instead of the polled mailbox, IDQN_ACT_GRAPH=0 launches eagerly instead of replaying a hipGraph
+bool act_no_poll() { static const bool on = getenv("IDQN_ACT_POLL") && atoi(getenv("IDQN_ACT_POLL")) == 0; return on; }
+bool act_use_graph() { static const bool on = !(getenv("IDQN_ACT_GRAPH") && atoi(getenv("IDQN_ACT_GRAPH")) == 0); return on; }
 
 int cu_budget() { return 256; }  // CUs a launch plan may fill
 
@@ -264,6 +268,27 @@ struct GcnnWs {
 
 }  // namespace
 
+// Buffers, mailbox and counters of the many-state acting entries: idqn_act_host_many (act_many_kernels.h), idqn_act_host_many_fc
+// (fc_act_many_kernels.h) and idqn_iqn_act_host_many (iqn_act_many_kernels.h).  A handle is in the domain of exactly one of the
+// three, so it carries ONE slot, filled by act_many_alloc on that entry's first call.  Nothing here is shared with the
+// single-state path but the capture stream.
+struct ActManySlot {
+    uint8_t* pin = nullptr;    // pinned block {head, states [32][state bytes]} (hipHostMalloc)
+    uint8_t* block = nullptr;  // its device copy, uploaded by the chain's one copy node
+    size_t head_bytes = 0;     // sizeof(ActManyTable), or sizeof(IqnActManyBlock): the table and tau [32][64]
+    float* ws = nullptr;       // ONE allocation, carved into:
+    float* a[3] = {nullptr, nullptr, nullptr};  // conv activations [32][..] (cnn handles)
+    // cnn: Dense_0 partials [32][NRG][J]; fc: the dense ping-pong rows [32][2][dmax]; i-IQN: [32][NRG][J / 32][2][NP][16]
+    float* part = nullptr;
+    float *cos = nullptr, *x = nullptr;  // i-IQN only: [32][64][64], [32][F][NP]
+    int32_t* action = nullptr;    // [32]
+    int32_t* mail = nullptr;      // host mailbox {action[32], sequence} (mapped + coherent)
+    int32_t* mail_dev = nullptr;  // its device address
+    unsigned* ctr = nullptr;      // device side: {sequence number, finished workgroups}
+    unsigned expected = 0;        // sequence number the next call waits for
+    std::map<std::tuple<int, void*, void*>, hipGraphExec_t> graphs;  // (n, q out, host actions)
+};
+
 struct idqn_handle_s {
     idqn_config_t cfg;
     Layout L;
@@ -301,29 +326,7 @@ struct idqn_handle_s {
     // idqn_iqn_act_host (iqn_act_kernels.h): fractions, their cosines [N][64], x [F][NP], Dense_0 partials [NRG][J / 32][2][NP][16]
     float *iact_tau = nullptr, *iact_cos = nullptr, *iact_x = nullptr, *iact_part = nullptr;
     std::map<std::tuple<int, const void*, const void*, void*, void*>, hipGraphExec_t> iact_graphs;  // (net, state, fractions, q out, action)
-    // idqn_act_host_many (act_many_kernels.h).  Nothing here is shared with the single-state path but the capture stream.
-    uint8_t* many_pin = nullptr;        // pinned block {ActManyTable, states [32][state bytes]} (hipHostMalloc)
-    uint8_t* many_block = nullptr;      // its device copy, uploaded by the chain's one copy node
-    float *many_a[3] = {nullptr, nullptr, nullptr}, *many_part = nullptr;  // activations [32][..], Dense_0 partials [32][NRG][J]
-    int32_t* many_action = nullptr;     // [32]
-    int32_t* many_mail = nullptr;       // host mailbox {action[32], sequence} (mapped + coherent)
-    int32_t* many_mail_dev = nullptr;   // its device address
-    unsigned* many_ctr = nullptr;       // device side: {sequence number, finished workgroups}
-    unsigned many_expected = 0;         // sequence number the next idqn_act_host_many call waits for
-    std::map<std::tuple<int, void*, void*>, hipGraphExec_t> many_graphs;  // (n, q out, host actions)
-    // idqn_act_host_many_fc (fc_act_many_kernels.h) uses the same fields -- no handle is in both domains: f32 states in the
-    // block for fc; many_a = the conv activations of the general-shape cnn; many_part = the dense ping-pong rows [32][2][dmax]
-    // idqn_iqn_act_host_many (iqn_act_many_kernels.h): buffers, mailbox and counters of its own, as above.
-    uint8_t* imany_pin = nullptr;       // pinned block {IqnActManyBlock, states [32][state bytes]} (hipHostMalloc)
-    uint8_t* imany_block = nullptr;     // its device copy
-    float *imany_a[3] = {nullptr, nullptr, nullptr};  // activations [32][..]
-    float *imany_cos = nullptr, *imany_x = nullptr, *imany_part = nullptr;  // [32][64][64], [32][F][NP], [32][NRG][J / 32][2][NP][16]
-    int32_t* imany_action = nullptr;    // [32]
-    int32_t* imany_mail = nullptr;      // host mailbox {action[32], sequence} (mapped + coherent)
-    int32_t* imany_mail_dev = nullptr;
-    unsigned* imany_ctr = nullptr;      // device side: {sequence number, finished workgroups}
-    unsigned imany_expected = 0;
-    std::map<std::tuple<int, void*, void*>, hipGraphExec_t> imany_graphs;  // (n, q out, host actions)
+    ActManySlot many;  // the handle's many-state acting entry
     const float* infer_pbase = nullptr;  // parameter base of the net the last idqn_q_values call evaluated
     float *infer_hbuf = nullptr, *infer_qpart = nullptr;  // k_hidden outputs of the single inference net
     float* wt[3] = {nullptr, nullptr, nullptr};  // transformed weights of the Conv_1 / Conv_2 data gradients
@@ -2032,20 +2035,38 @@ extern "C" int idqn_destroy(idqn_handle_t h) {
         if (e) (void)hipEventDestroy(e);
     for (auto& g : h->act_graphs) (void)hipGraphExecDestroy(g.second);
     for (auto& g : h->iact_graphs) (void)hipGraphExecDestroy(g.second);
-    for (auto& g : h->many_graphs) (void)hipGraphExecDestroy(g.second);
-    for (auto& g : h->imany_graphs) (void)hipGraphExecDestroy(g.second);
+    for (auto& g : h->many.graphs) (void)hipGraphExecDestroy(g.second);
     for (auto& g : h->step_graphs)
         if (g.second.second) (void)hipGraphExecDestroy(g.second.second);
     if (h->act_stream) (void)hipStreamDestroy(h->act_stream);
     if (h->act_mail) (void)hipHostFree(h->act_mail);
-    if (h->many_mail) (void)hipHostFree(h->many_mail);
-    if (h->many_pin) (void)hipHostFree(h->many_pin);
-    if (h->imany_mail) (void)hipHostFree(h->imany_mail);
-    if (h->imany_pin) (void)hipHostFree(h->imany_pin);
+    if (h->many.mail) (void)hipHostFree(h->many.mail);
+    if (h->many.pin) (void)hipHostFree(h->many.pin);
     if (h->fact_planes) (void)hipFree(h->fact_planes);
     for (int32_t* p : h->iqn.bwd_items)
         if (p) (void)hipFree(p);
     delete h;
+    return IDQN_OK;
+}
+
+// What issue(stream) enqueues, captured on a stream of the handle's own (the caller's may be the legacy default stream, which
+// cannot capture) and instantiated; the graph is then launched on the caller's stream like any other work.  Nothing of a failed
+// capture is kept: hipStreamEndCapture is always called, the hipGraph_t is destroyed on every path, and *exec is written only
+// once instantiation has succeeded.
+template <class Issue>
+static int capture_exec(idqn_handle_t h, Issue&& issue, hipGraphExec_t* exec) {
+    if (!h->act_stream) IDQN_HIP_CHECK(hipStreamCreateWithFlags(&h->act_stream, hipStreamNonBlocking));
+    IDQN_HIP_CHECK(hipStreamBeginCapture(h->act_stream, hipStreamCaptureModeRelaxed));
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t ex = nullptr;
+    const int rc = issue(h->act_stream);
+    const hipError_t e = hipStreamEndCapture(h->act_stream, &graph);
+    const hipError_t ei = rc == IDQN_OK && e == hipSuccess ? hipGraphInstantiate(&ex, graph, nullptr, nullptr, 0) : hipSuccess;
+    if (graph) (void)hipGraphDestroy(graph);
+    if (rc) return rc;
+    IDQN_HIP_CHECK(e);
+    IDQN_HIP_CHECK(ei);
+    *exec = ex;
     return IDQN_OK;
 }
 
@@ -2108,21 +2129,9 @@ extern "C" int idqn_learn_on_batch(idqn_handle_t h, const void* state_dev, const
             }
             auto& ent = h->step_graphs[key];
             if (ent.first++ == 0) return issue(q);
-            if (!ent.second) {
-                hipGraph_t graph = nullptr;
-                if (!h->act_stream) IDQN_HIP_CHECK(hipStreamCreateWithFlags(&h->act_stream, hipStreamNonBlocking));
-                IDQN_HIP_CHECK(hipStreamBeginCapture(h->act_stream, hipStreamCaptureModeRelaxed));
-                rc = issue(h->act_stream);
-                const hipError_t e = hipStreamEndCapture(h->act_stream, &graph);
-                if (rc || e != hipSuccess) {  // nothing of a failed capture is kept
-                    if (graph) (void)hipGraphDestroy(graph);
-                    h->step_graphs.erase(key);
-                    if (rc) return rc;
-                    IDQN_HIP_CHECK(e);
-                }
-                const hipError_t ei = hipGraphInstantiate(&ent.second, graph, nullptr, nullptr, 0);
-                (void)hipGraphDestroy(graph);
-                if (ei != hipSuccess) { h->step_graphs.erase(key); IDQN_HIP_CHECK(ei); }
+            if (!ent.second && (rc = capture_exec(h, issue, &ent.second))) {  // nothing of a failed capture is kept
+                h->step_graphs.erase(key);
+                return rc;
             }
             IDQN_HIP_CHECK(hipGraphLaunch(ent.second, q));
             return IDQN_OK;
@@ -2759,10 +2768,9 @@ static int act_host_impl(idqn_handle_t h, int32_t which, int32_t head, const voi
     }
     // The single-state path ends in a kernel that can write the action straight into mapped host memory, followed by a
     // sequence number the host polls (IDQN_ACT_POLL=0: a device-to-host copy and a stream synchronisation instead).
-    static const bool no_poll = getenv("IDQN_ACT_POLL") && atoi(getenv("IDQN_ACT_POLL")) == 0;
     // (the i-IQN chain always ends in k_iqn_act_head, which writes the mailbox: it never takes the generic route, so
     // IDQN_ACT_GENERIC has no say in it)
-    const bool poll = !no_poll && (iqn || ((cnn && !h->gc.on) ? (!act_generic() && h->J <= 512 && h->cfg.n_actions <= 32) : true));
+    const bool poll = !act_no_poll() && (iqn || ((cnn && !h->gc.on) ? (!act_generic() && h->J <= 512 && h->cfg.n_actions <= 32) : true));
     if (iqn && !h->iact_tau) {
         const long NP = h->iqn.N > 32 ? 64 : 32;
         float* p = nullptr;
@@ -2798,30 +2806,15 @@ static int act_host_impl(idqn_handle_t h, int32_t which, int32_t head, const voi
         if (!poll) IDQN_HIP_CHECK(hipMemcpyAsync(action_host_pinned, h->act_action, 4, hipMemcpyDeviceToHost, qs));
         return IDQN_OK;
     };
-    static const bool use_graph = !(getenv("IDQN_ACT_GRAPH") && atoi(getenv("IDQN_ACT_GRAPH")) == 0);
     int rc = IDQN_OK;
-    if (use_graph) {
-        // (captured on a stream of the handle's own: the caller's may be the legacy default stream, which cannot
-        // capture; the instantiated graph is then launched on the caller's stream like any other work)
-        auto capture = [&](hipGraphExec_t* exec) -> int {
-            hipGraph_t graph = nullptr;
-            if (!h->act_stream) IDQN_HIP_CHECK(hipStreamCreateWithFlags(&h->act_stream, hipStreamNonBlocking));
-            IDQN_HIP_CHECK(hipStreamBeginCapture(h->act_stream, hipStreamCaptureModeRelaxed));
-            const int rc2 = issue(h->act_stream);
-            const hipError_t e = hipStreamEndCapture(h->act_stream, &graph);
-            if (rc2) return rc2;
-            IDQN_HIP_CHECK(e);
-            IDQN_HIP_CHECK(hipGraphInstantiate(exec, graph, nullptr, nullptr, 0));
-            IDQN_HIP_CHECK(hipGraphDestroy(graph));
-            return IDQN_OK;
-        };
+    if (act_use_graph()) {
         const int net = which * h->cfg.n_heads + head;
         hipGraphExec_t exec = nullptr;
         if (iqn) {
             auto key = std::make_tuple(net, state_host_pinned, (const void*)tau_host_pinned, (void*)q_out_dev, (void*)action_host_pinned);
             auto it = h->iact_graphs.find(key);
             if (it == h->iact_graphs.end()) {
-                if ((rc = capture(&exec))) return rc;
+                if ((rc = capture_exec(h, issue, &exec))) return rc;
                 it = h->iact_graphs.emplace(key, exec).first;
             }
             exec = it->second;
@@ -2829,7 +2822,7 @@ static int act_host_impl(idqn_handle_t h, int32_t which, int32_t head, const voi
             auto key = std::make_tuple(net, state_host_pinned, (void*)q_out_dev, (void*)action_host_pinned);
             auto it = h->act_graphs.find(key);
             if (it == h->act_graphs.end()) {
-                if ((rc = capture(&exec))) return rc;
+                if ((rc = capture_exec(h, issue, &exec))) return rc;
                 it = h->act_graphs.emplace(key, exec).first;
             }
             exec = it->second;
@@ -2844,23 +2837,25 @@ static int act_host_impl(idqn_handle_t h, int32_t which, int32_t head, const voi
     return act_host_wait(h, action_host_pinned, q);
 }
 
+// The host side of an acting mailbox: spins until mail[seq_index] shows the sequence number `want` -- far longer than any step
+// queued in front of the launch takes -- and asks every 2^20 spins whether q ran dry (or failed) without the number, reading
+// once more if so.  false: the launch finished without delivering.
+static bool mailbox_wait(volatile int32_t* mail, int seq_index, unsigned want, hipStream_t q) {
+    for (long spin = 0; spin < (1L << 34); ++spin) {
+        if ((unsigned)mail[seq_index] == want) return true;
+        __builtin_ia32_pause();
+        if ((spin & 0xfffff) == 0xfffff && hipStreamQuery(q) != hipErrorNotReady) return (unsigned)mail[seq_index] == want;
+    }
+    return false;
+}
+
 static int act_host_wait(idqn_handle_t h, int32_t* action_host_pinned, hipStream_t q) {
     IDQN_REQUIRE(h->act_pending != 0, "idqn_act_host_end: no acting launch is pending");
     const bool poll = h->act_pending == 1;
     h->act_pending = 0;
     if (poll) {
-        const unsigned want = ++h->act_expected;
         volatile int32_t* mail = h->act_mail;
-        bool seen = false;
-        for (long spin = 0; spin < (1L << 34); ++spin) {  // far longer than any step queued in front of the launch
-            if ((unsigned)mail[1] == want) { seen = true; break; }
-            __builtin_ia32_pause();
-            if ((spin & 0xfffff) == 0xfffff && hipStreamQuery(q) != hipErrorNotReady) {  // the stream ran dry (or failed) without the number
-                seen = (unsigned)mail[1] == want;
-                break;
-            }
-        }
-        if (!seen) {  // resynchronise the two counters, then report
+        if (!mailbox_wait(mail, 1, ++h->act_expected, q)) {  // resynchronise the two counters, then report
             IDQN_HIP_CHECK(hipStreamSynchronize(q));
             IDQN_HIP_CHECK(hipMemcpy(&h->act_expected, h->act_seq, 4, hipMemcpyDeviceToHost));
             IDQN_REQUIRE(false, "idqn_act_host: the acting launch finished without delivering its action");
@@ -2912,10 +2907,12 @@ extern "C" int idqn_act_host_end(idqn_handle_t h, int32_t* action_host_pinned, v
     return act_host_wait(h, action_host_pinned, (hipStream_t)stream);
 }
 
-// select_action's greedy branch for n <= 32 host states, one head each (act_many_kernels.h): the states are copied behind
-// the head / group table in the handle's pinned block, ONE copy node uploads the block, five launches follow (three conv
-// layers, Dense_0 per group of states with one head, the head kernel per state), and the n actions come back through a
-// mailbox of their own.  One linear hipGraph per (n, buffers) serves every head assignment and both parameter sets.
+// Acting for n <= 32 host states in one call: idqn_act_host_many (MFMA cnn handles), idqn_act_host_many_fc (MLP and
+// general-shape cnn handles) and idqn_iqn_act_host_many (quantile heads).  The states are copied behind a head (the head /
+// group table; for i-IQN the fractions too) in the handle's pinned block, ONE copy node uploads the block, the entry's
+// launches follow, and the n actions come back through the slot's mailbox.  One linear hipGraph per (n, buffers) serves every
+// head assignment, both parameter sets and every set of fractions.  Each entry checks its own arguments and domain, fills the
+// block and hands its launches to act_many_run; everything else is shared.
 static int act_many_conv_plan(idqn_handle_t h, int i, int* KS, int* upt) {
     const ConvL& l = h->conv[i];
     *KS = i == 0 ? 8 : 16;  // as act_trunk
@@ -2924,18 +2921,89 @@ static int act_many_conv_plan(idqn_handle_t h, int i, int* KS, int* upt) {
     IDQN_REQUIRE(l.CI % 32 == 0 ? *upt <= 4 : (l.CI == 4 && *upt <= 8), "idqn_act_host_many: Conv_%d is outside the acting kernels' shapes", i);
     return IDQN_OK;
 }
+static int act_many_conv_plans(idqn_handle_t h) {  // the entries' check, before anything is enqueued
+    for (int i = 0; i < 3; ++i) {
+        int ks = 0, upt = 0;
+        int rc = act_many_conv_plan(h, i, &ks, &upt);
+        if (rc) return rc;
+    }
+    return IDQN_OK;
+}
 
-static int act_many_chain(idqn_handle_t h, int n, size_t state_bytes, float* q_out_dev, bool poll, int32_t* actions_host_pinned,
-                          hipStream_t q) {
-    IDQN_HIP_CHECK(hipMemcpyAsync(h->many_block, h->many_pin, sizeof(ActManyTable) + (size_t)n * state_bytes, hipMemcpyHostToDevice, q));
+// The slot of the handle's entry, on its first call: the pinned block and its device copy for a head of head_bytes and 32
+// states, ONE float workspace of floats[0 .. n_floats) carved in that order into a[0], a[1], a[2], (n_floats == 6: cos, x,)
+// part, action[32] plus the two counters, and the mapped mailbox.  Everything goes into locals first: a failure part-way
+// frees what it got and leaves every field of the slot null.
+static int act_many_alloc(idqn_handle_t h, size_t head_bytes, size_t state_bytes, const long* floats, int n_floats) {
+    const size_t block = head_bytes + ACT_MANY_MAX * state_bytes + 64;
+    long total = 0;
+    for (int i = 0; i < n_floats; ++i) total += floats[i];
+    uint8_t *pin = nullptr, *dev = nullptr;
+    float* f = nullptr;
+    int32_t *act = nullptr, *mail = nullptr, *mail_dev = nullptr;
+    auto alloc = [&]() -> int {
+        IDQN_HIP_CHECK(hipHostMalloc((void**)&pin, block, hipHostMallocDefault));
+        IDQN_HIP_CHECK(hipHostMalloc((void**)&mail, 256, hipHostMallocMapped | hipHostMallocCoherent));
+        memset(mail, 0, 256);
+        IDQN_HIP_CHECK(hipHostGetDevicePointer((void**)&mail_dev, mail, 0));
+        IDQN_HIP_CHECK(hipMalloc((void**)&f, (size_t)total * 4));
+        IDQN_HIP_CHECK(hipMalloc((void**)&act, 256));  // actions [32], then the two counters
+        IDQN_HIP_CHECK(hipMemset(act, 0, 256));
+        IDQN_HIP_CHECK(hipMalloc((void**)&dev, block));
+        IDQN_HIP_CHECK(hipStreamSynchronize(nullptr));  // (the memset runs on the null stream, which does not order against q)
+        return IDQN_OK;
+    };
+    if (const int rc = alloc()) {
+        if (pin) (void)hipHostFree(pin);
+        if (mail) (void)hipHostFree(mail);
+        if (f) (void)hipFree(f);
+        if (act) (void)hipFree(act);
+        if (dev) (void)hipFree(dev);
+        return rc;
+    }
+    h->owned.push_back((void*)f);
+    h->owned.push_back((void*)act);
+    h->owned.push_back((void*)dev);
+    ActManySlot& s = h->many;
+    s.pin = pin; s.head_bytes = head_bytes; s.mail = mail; s.mail_dev = mail_dev; s.ws = f;
+    float* sub[6];
+    for (int i = 0; i < n_floats; ++i) { sub[i] = f; f += floats[i]; }
+    s.a[0] = sub[0]; s.a[1] = sub[1]; s.a[2] = sub[2]; s.part = sub[n_floats - 1];
+    if (n_floats == 6) { s.cos = sub[3]; s.x = sub[4]; }
+    s.action = act; s.ctr = (unsigned*)(act + ACT_MANY_MAX);
+    s.block = dev;
+    return IDQN_OK;
+}
+
+// grouped: the states sorted into groups by head, in state order within a group (the Dense_0 kernels of the cnn and i-IQN
+// chains walk them); otherwise n, which and head[] only -- every state is a workgroup of its own
+static void act_many_fill_table(ActManyTable* tb, int which, const int32_t* heads, int n, int K, bool grouped) {
+    tb->n = n; tb->which = which; tb->pad = 0;
+    int ng = 0, pos = 0;
+    for (int k = 0; grouped && k < K && pos < n; ++k) {
+        const int start = pos;
+        for (int e = 0; e < n; ++e)
+            if (heads[e] == k) tb->order[pos++] = e;
+        if (pos > start) { tb->g_head[ng] = k; tb->g_start[ng] = start; tb->g_count[ng] = pos - start; ++ng; }
+    }
+    tb->n_groups = ng;
+    for (int e = 0; e < n; ++e) tb->head[e] = heads[e];
+}
+
+static ActManyNets act_many_nets(idqn_handle_t h) {  // (an IqnActManyBlock begins with its table)
     ActManyNets nets;
-    nets.tab = (const ActManyTable*)h->many_block; nets.online = h->online; nets.target = h->target; nets.pstride = h->L.head_stride;
+    nets.tab = (const ActManyTable*)h->many.block; nets.online = h->online; nets.target = h->target; nets.pstride = h->L.head_stride;
+    return nets;
+}
+
+// the three k_act_many_conv launches of the cnn and i-IQN chains: uint8 states [n][..] -> out[0] -> out[1] -> out[2]
+static int act_many_convs(idqn_handle_t h, const ActManyNets& nets, const uint8_t* states_u8, float* const out[3], int n, hipStream_t q) {
     const float* in = nullptr;
     int ih = h->cfg.obs_h, iw = h->cfg.obs_w;
     for (int i = 0; i < 3; ++i) {
         const ConvL& l = h->conv[i];
         ActManyConvArgs a;
-        a.nets = nets; a.in_u8 = i == 0 ? h->many_block + sizeof(ActManyTable) : nullptr; a.in = in; a.out = h->many_a[i];
+        a.nets = nets; a.in_u8 = i == 0 ? states_u8 : nullptr; a.in = in; a.out = out[i];
         a.w_off = l.w_off; a.b_off = l.b_off; a.IH = ih; a.IW = iw; a.CI = l.CI; a.OH = l.OH; a.OW = l.OW; a.CO = l.CO;
         a.K = l.K; a.S = l.S; a.PLh = l.PLh; a.PLw = l.PLw;
         int upt = 0;
@@ -2946,19 +3014,72 @@ static int act_many_chain(idqn_handle_t h, int n, size_t state_bytes, float* q_o
         else if (upt <= 1) hipLaunchKernelGGL((k_act_many_conv<32, 1>), grid, dim3(256), 0, q, a);
         else if (upt <= 2) hipLaunchKernelGGL((k_act_many_conv<32, 2>), grid, dim3(256), 0, q, a);
         else hipLaunchKernelGGL((k_act_many_conv<32, 4>), grid, dim3(256), 0, q, a);
-        in = h->many_a[i]; ih = l.OH; iw = l.OW;
+        in = out[i]; ih = l.OH; iw = l.OW;
     }
+    return IDQN_OK;
+}
+
+// What the three entries do once the block is filled: the copy node that uploads head and n states, chain(stream, mail) --
+// the entry's launches, whose last kernel delivers to `mail` unless it is null -- as a replayed graph per (n, buffers) or
+// eagerly (IDQN_ACT_GRAPH=0), then the wait on the slot's mailbox (IDQN_ACT_POLL=0: a device-to-host copy of the actions and a
+// stream synchronisation instead) and the n actions into the caller's buffer.
+template <class Chain>
+static int act_many_run(idqn_handle_t h, const char* fn_name, int n, size_t state_bytes, float* q_out_dev, int32_t* actions_host_pinned,
+                        hipStream_t q, Chain&& chain) {
+    ActManySlot& s = h->many;
+    const bool poll = !act_no_poll();
+    auto issue = [&](hipStream_t qs) -> int {
+        IDQN_HIP_CHECK(hipMemcpyAsync(s.block, s.pin, s.head_bytes + (size_t)n * state_bytes, hipMemcpyHostToDevice, qs));
+        const int rc = chain(qs, poll ? s.mail_dev : nullptr);
+        if (rc) return rc;
+        IDQN_HIP_CHECK(hipGetLastError());
+        if (!poll) IDQN_HIP_CHECK(hipMemcpyAsync(actions_host_pinned, s.action, (size_t)n * 4, hipMemcpyDeviceToHost, qs));
+        return IDQN_OK;
+    };
+    int rc = IDQN_OK;
+    if (act_use_graph()) {
+        auto key = std::make_tuple(n, (void*)q_out_dev, (void*)actions_host_pinned);
+        auto it = s.graphs.find(key);
+        if (it == s.graphs.end()) {
+            hipGraphExec_t exec = nullptr;
+            if ((rc = capture_exec(h, issue, &exec))) return rc;
+            it = s.graphs.emplace(key, exec).first;
+        }
+        IDQN_HIP_CHECK(hipGraphLaunch(it->second, q));
+    } else if ((rc = issue(q))) {
+        return rc;
+    }
+    if (!poll) {
+        IDQN_HIP_CHECK(hipStreamSynchronize(q));
+        return IDQN_OK;
+    }
+    volatile int32_t* mail = s.mail;
+    if (!mailbox_wait(mail, ACT_MANY_MAX, ++s.expected, q)) {  // resynchronise the counters, then report
+        IDQN_HIP_CHECK(hipStreamSynchronize(q));
+        IDQN_HIP_CHECK(hipMemcpy(&s.expected, s.ctr, 4, hipMemcpyDeviceToHost));
+        IDQN_HIP_CHECK(hipMemset(s.ctr + 1, 0, 4));
+        IDQN_REQUIRE(false, "%s: the acting launch finished without delivering its actions", fn_name);
+    }
+    for (int e = 0; e < n; ++e) actions_host_pinned[e] = mail[e];
+    return IDQN_OK;
+}
+
+// select_action's greedy branch on the MFMA cnn path (act_many_kernels.h): five launches behind the copy node -- three conv
+// layers, Dense_0 per group of states with one head, the head kernel per state.
+static int act_many_chain(idqn_handle_t h, int n, float* q_out_dev, int32_t* mail_dev, hipStream_t q) {
+    const ActManySlot& s = h->many;
+    const ActManyNets nets = act_many_nets(h);
+    int rc = act_many_convs(h, nets, s.block + s.head_bytes, s.a, n, q);
+    if (rc) return rc;
     ActManyDenseArgs d;
-    d.nets = nets; d.a3 = h->many_a[2]; d.part = h->many_part; d.w_off = h->off_w0; d.F = h->F; d.J = h->J;
+    d.nets = nets; d.a3 = s.a[2]; d.part = s.part; d.w_off = h->off_w0; d.F = h->F; d.J = h->J;
     d.NRG = std::max(1, 256 / (h->J / 128));  // as the single-state path
     hipLaunchKernelGGL(k_act_many_dense0, dim3(d.NRG * (h->J / 128), std::min(n, h->cfg.n_heads)), dim3(256), 0, q, d);
     ActManyHeadArgs ha;
-    ha.nets = nets; ha.part = h->many_part; ha.b0_off = h->off_b0; ha.w1_off = h->off_w1; ha.b1_off = h->off_b1;
-    ha.NP = d.NRG; ha.J = h->J; ha.A = h->cfg.n_actions; ha.n = n; ha.q_out = q_out_dev; ha.action = h->many_action;
-    ha.mail = poll ? h->many_mail_dev : nullptr; ha.ctr = h->many_ctr;
+    ha.nets = nets; ha.part = s.part; ha.b0_off = h->off_b0; ha.w1_off = h->off_w1; ha.b1_off = h->off_b1;
+    ha.NP = d.NRG; ha.J = h->J; ha.A = h->cfg.n_actions; ha.n = n; ha.q_out = q_out_dev; ha.action = s.action;
+    ha.mail = mail_dev; ha.ctr = s.ctr;
     hipLaunchKernelGGL(k_act_many_head, dim3(n), dim3(1024), 0, q, ha);
-    IDQN_HIP_CHECK(hipGetLastError());
-    if (!poll) IDQN_HIP_CHECK(hipMemcpyAsync(actions_host_pinned, h->many_action, (size_t)n * 4, hipMemcpyDeviceToHost, q));
     return IDQN_OK;
 }
 
@@ -2973,132 +3094,48 @@ extern "C" int idqn_act_host_many(idqn_handle_t h, int32_t which, const int32_t*
     IDQN_REQUIRE(h->iqn.N == 0, "idqn_act_host_many: the handle was created with quantile heads");
     IDQN_REQUIRE(h->cfg.arch == IDQN_ARCH_CNN && !h->gc.on && !act_generic() && h->J <= 512 && h->J % 128 == 0 && h->cfg.n_actions <= 32,
                  "idqn_act_host_many: the handle is outside the single-state cnn acting path (fc, general shapes, IDQN_ACT_GENERIC, J > 512, A > 32)");
-    for (int i = 0; i < 3; ++i) {
-        int ks = 0, upt = 0;
-        int rc = act_many_conv_plan(h, i, &ks, &upt);
-        if (rc) return rc;
-    }
-    hipStream_t q = (hipStream_t)stream;
+    int rc = act_many_conv_plans(h);
+    if (rc) return rc;
     const size_t sb = (size_t)h->cfg.obs_h * h->cfg.obs_w * h->cfg.obs_c;  // bytes of one state
     IDQN_REQUIRE(sb % 4 == 0, "idqn_act_host_many: %zu bytes per state", sb);
-    static const bool no_poll = getenv("IDQN_ACT_POLL") && atoi(getenv("IDQN_ACT_POLL")) == 0;
-    static const bool use_graph = !(getenv("IDQN_ACT_GRAPH") && atoi(getenv("IDQN_ACT_GRAPH")) == 0);
-    const bool poll = !no_poll;
-    if (!h->many_block) {
-        const size_t block = sizeof(ActManyTable) + ACT_MANY_MAX * sb + 64;
+    if (!h->many.block) {
         const long NRG = std::max(1, 256 / (h->J / 128));
         long fl[4] = {0, 0, 0, ACT_MANY_MAX * NRG * h->J};
         for (int i = 0; i < 3; ++i) fl[i] = (long)ACT_MANY_MAX * h->conv[i].OH * h->conv[i].OW * h->conv[i].CO;
-        uint8_t *pin = nullptr, *dev = nullptr;
-        float* f = nullptr;
-        int32_t *act = nullptr, *mail = nullptr;
-        IDQN_HIP_CHECK(hipHostMalloc((void**)&pin, block, hipHostMallocDefault));
-        h->many_pin = pin;
-        IDQN_HIP_CHECK(hipHostMalloc((void**)&mail, 256, hipHostMallocMapped | hipHostMallocCoherent));
-        h->many_mail = mail;
-        memset(mail, 0, 256);
-        IDQN_HIP_CHECK(hipHostGetDevicePointer((void**)&h->many_mail_dev, mail, 0));
-        IDQN_HIP_CHECK(hipMalloc((void**)&f, (size_t)(fl[0] + fl[1] + fl[2] + fl[3]) * 4));
-        h->owned.push_back((void*)f);
-        IDQN_HIP_CHECK(hipMalloc((void**)&act, 256));  // actions [32], then the two counters
-        h->owned.push_back((void*)act);
-        IDQN_HIP_CHECK(hipMemset(act, 0, 256));
-        IDQN_HIP_CHECK(hipMalloc((void**)&dev, block));
-        h->owned.push_back((void*)dev);
-        IDQN_HIP_CHECK(hipStreamSynchronize(nullptr));  // (the memset runs on the null stream, which does not order against q)
-        h->many_a[0] = f; h->many_a[1] = f + fl[0]; h->many_a[2] = h->many_a[1] + fl[1]; h->many_part = h->many_a[2] + fl[2];
-        h->many_action = act; h->many_ctr = (unsigned*)(act + ACT_MANY_MAX);
-        h->many_block = dev;
+        if ((rc = act_many_alloc(h, sizeof(ActManyTable), sb, fl, 4))) return rc;
     }
-    // the table: states grouped by head, in state order within a group
-    ActManyTable* tb = (ActManyTable*)h->many_pin;
-    tb->n = n; tb->which = which; tb->pad = 0;
-    int ng = 0, pos = 0;
-    for (int k = 0; k < K && pos < n; ++k) {
-        const int start = pos;
-        for (int e = 0; e < n; ++e)
-            if (heads_host[e] == k) tb->order[pos++] = e;
-        if (pos > start) { tb->g_head[ng] = k; tb->g_start[ng] = start; tb->g_count[ng] = pos - start; ++ng; }
-    }
-    tb->n_groups = ng;
-    for (int e = 0; e < n; ++e) tb->head[e] = heads_host[e];
-    memcpy(h->many_pin + sizeof(ActManyTable), states_host_pinned, (size_t)n * sb);
-    int rc = IDQN_OK;
-    if (use_graph) {
-        auto key = std::make_tuple((int)n, (void*)q_out_dev, (void*)actions_host_pinned);
-        auto it = h->many_graphs.find(key);
-        if (it == h->many_graphs.end()) {
-            hipGraph_t graph = nullptr;
-            hipGraphExec_t exec = nullptr;
-            if (!h->act_stream) IDQN_HIP_CHECK(hipStreamCreateWithFlags(&h->act_stream, hipStreamNonBlocking));
-            IDQN_HIP_CHECK(hipStreamBeginCapture(h->act_stream, hipStreamCaptureModeRelaxed));
-            rc = act_many_chain(h, n, sb, q_out_dev, poll, actions_host_pinned, h->act_stream);
-            const hipError_t e = hipStreamEndCapture(h->act_stream, &graph);
-            if (rc) return rc;
-            IDQN_HIP_CHECK(e);
-            IDQN_HIP_CHECK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-            IDQN_HIP_CHECK(hipGraphDestroy(graph));
-            it = h->many_graphs.emplace(key, exec).first;
-        }
-        IDQN_HIP_CHECK(hipGraphLaunch(it->second, q));
-    } else if ((rc = act_many_chain(h, n, sb, q_out_dev, poll, actions_host_pinned, q))) {
-        return rc;
-    }
-    if (!poll) {
-        IDQN_HIP_CHECK(hipStreamSynchronize(q));
-        return IDQN_OK;
-    }
-    const unsigned want = ++h->many_expected;
-    volatile int32_t* mail = h->many_mail;
-    bool seen = false;
-    for (long spin = 0; spin < (1L << 34); ++spin) {  // as act_host_wait
-        if ((unsigned)mail[ACT_MANY_MAX] == want) { seen = true; break; }
-        __builtin_ia32_pause();
-        if ((spin & 0xfffff) == 0xfffff && hipStreamQuery(q) != hipErrorNotReady) {
-            seen = (unsigned)mail[ACT_MANY_MAX] == want;
-            break;
-        }
-    }
-    if (!seen) {  // resynchronise the counters, then report
-        IDQN_HIP_CHECK(hipStreamSynchronize(q));
-        IDQN_HIP_CHECK(hipMemcpy(&h->many_expected, h->many_ctr, 4, hipMemcpyDeviceToHost));
-        IDQN_HIP_CHECK(hipMemset(h->many_ctr + 1, 0, 4));
-        IDQN_REQUIRE(false, "idqn_act_host_many: the acting launch finished without delivering its actions");
-    }
-    for (int e = 0; e < n; ++e) actions_host_pinned[e] = mail[e];
-    return IDQN_OK;
+    act_many_fill_table((ActManyTable*)h->many.pin, which, heads_host, n, K, true);
+    memcpy(h->many.pin + sizeof(ActManyTable), states_host_pinned, (size_t)n * sb);
+    return act_many_run(h, "idqn_act_host_many", n, sb, q_out_dev, actions_host_pinned, (hipStream_t)stream,
+                        [&](hipStream_t qs, int32_t* mail_dev) { return act_many_chain(h, n, q_out_dev, mail_dev, qs); });
 }
 
 // idqn_act_host_many for the handles it refuses (fc_act_many_kernels.h): MLP handles run ONE launch behind the copy node
 // (k_fc_act_many1 when every width fits its LDS rows, as the single-state path picks k_fc_q1; k_fc_act_many otherwise);
 // general-shape cnn handles run three k_gconv_fwd_many launches and k_fc_act_many on the flattened features.
-static int fc_act_many_chain(idqn_handle_t h, int n, size_t state_bytes, float* q_out_dev, bool poll, int32_t* actions_host_pinned,
-                             hipStream_t q) {
-    IDQN_HIP_CHECK(hipMemcpyAsync(h->many_block, h->many_pin, sizeof(ActManyTable) + (size_t)n * state_bytes, hipMemcpyHostToDevice, q));
-    ActManyNets nets;
-    nets.tab = (const ActManyTable*)h->many_block; nets.online = h->online; nets.target = h->target; nets.pstride = h->L.head_stride;
-    const uint8_t* states = h->many_block + sizeof(ActManyTable);
+static int fc_act_many_chain(idqn_handle_t h, int n, float* q_out_dev, int32_t* mail_dev, hipStream_t q) {
+    const ActManySlot& s = h->many;
+    const ActManyNets nets = act_many_nets(h);
+    const uint8_t* states = s.block + s.head_bytes;
     FcActManyArgs a;
-    a.net = h->fc; a.nets = nets; a.s = (const float*)states; a.s_ld = h->fc.d[0]; a.ws = h->many_part; a.q_out = q_out_dev;
-    a.action = h->many_action; a.mail = poll ? h->many_mail_dev : nullptr; a.ctr = h->many_ctr; a.n = n;
+    a.net = h->fc; a.nets = nets; a.s = (const float*)states; a.s_ld = h->fc.d[0]; a.ws = s.part; a.q_out = q_out_dev;
+    a.action = s.action; a.mail = mail_dev; a.ctr = s.ctr; a.n = n;
     if (h->gc.on) {
         for (int i = 0; i < 3; ++i) {
             const ConvL& l = h->conv[i];
             GConvManyArgs g;
-            g.nets = nets; g.in_u8 = i == 0 ? states : nullptr; g.in = i == 0 ? nullptr : h->many_a[i - 1]; g.out = h->many_a[i];
+            g.nets = nets; g.in_u8 = i == 0 ? states : nullptr; g.in = i == 0 ? nullptr : s.a[i - 1]; g.out = s.a[i];
             g.w_off = l.w_off; g.b_off = l.b_off; g.IH = l.IH; g.IW = l.IW; g.CI = l.CI; g.OH = l.OH; g.OW = l.OW; g.CO = l.CO;
             g.KS = l.K; g.S = l.S; g.PLh = l.PLh; g.PLw = l.PLw;
             hipLaunchKernelGGL(k_gconv_fwd_many, dim3(ggrid((long)l.OH * l.OW * l.CO), n), dim3(256), 0, q, g);
         }
-        a.s = h->many_a[2];  // row stride = flattened feature count = d[0]
+        a.s = s.a[2];  // row stride = flattened feature count = d[0]
         hipLaunchKernelGGL(k_fc_act_many, dim3(n), dim3(256), 0, q, a);
     } else if (h->fc.dmax <= FC_MAX_WIDTH) {
         hipLaunchKernelGGL(k_fc_act_many1, dim3(n), dim3(512), 0, q, a);
     } else {
         hipLaunchKernelGGL(k_fc_act_many, dim3(n), dim3(256), 0, q, a);
     }
-    IDQN_HIP_CHECK(hipGetLastError());
-    if (!poll) IDQN_HIP_CHECK(hipMemcpyAsync(actions_host_pinned, h->many_action, (size_t)n * 4, hipMemcpyDeviceToHost, q));
     return IDQN_OK;
 }
 
@@ -3114,138 +3151,47 @@ extern "C" int idqn_act_host_many_fc(idqn_handle_t h, int32_t which, const int32
     const bool cnn = h->cfg.arch == IDQN_ARCH_CNN;
     IDQN_REQUIRE(h->cfg.arch == IDQN_ARCH_FC || (cnn && h->gc.on),
                  "idqn_act_host_many_fc: the handle runs the MFMA cnn path (idqn_act_host_many serves it)");
-    hipStream_t q = (hipStream_t)stream;
     // bytes of one state: uint8 pixels (general-shape cnn) or float32 features (fc)
     const size_t sb = cnn ? (size_t)h->cfg.obs_h * h->cfg.obs_w * h->cfg.obs_c : (size_t)h->fc.d[0] * 4;
-    static const bool no_poll = getenv("IDQN_ACT_POLL") && atoi(getenv("IDQN_ACT_POLL")) == 0;
-    static const bool use_graph = !(getenv("IDQN_ACT_GRAPH") && atoi(getenv("IDQN_ACT_GRAPH")) == 0);
-    const bool poll = !no_poll;
-    if (!h->many_block) {
-        const size_t block = sizeof(ActManyTable) + ACT_MANY_MAX * sb + 64;
+    if (!h->many.block) {
         long fl[4] = {0, 0, 0, (long)ACT_MANY_MAX * 2 * h->fc.dmax};
         if (cnn)
             for (int i = 0; i < 3; ++i) fl[i] = (long)ACT_MANY_MAX * h->conv[i].OH * h->conv[i].OW * h->conv[i].CO;
-        uint8_t *pin = nullptr, *dev = nullptr;
-        float* f = nullptr;
-        int32_t *act = nullptr, *mail = nullptr;
-        IDQN_HIP_CHECK(hipHostMalloc((void**)&pin, block, hipHostMallocDefault));
-        h->many_pin = pin;
-        IDQN_HIP_CHECK(hipHostMalloc((void**)&mail, 256, hipHostMallocMapped | hipHostMallocCoherent));
-        h->many_mail = mail;
-        memset(mail, 0, 256);
-        IDQN_HIP_CHECK(hipHostGetDevicePointer((void**)&h->many_mail_dev, mail, 0));
-        IDQN_HIP_CHECK(hipMalloc((void**)&f, (size_t)(fl[0] + fl[1] + fl[2] + fl[3]) * 4));
-        h->owned.push_back((void*)f);
-        IDQN_HIP_CHECK(hipMalloc((void**)&act, 256));  // actions [32], then the two counters
-        h->owned.push_back((void*)act);
-        IDQN_HIP_CHECK(hipMemset(act, 0, 256));
-        IDQN_HIP_CHECK(hipMalloc((void**)&dev, block));
-        h->owned.push_back((void*)dev);
-        IDQN_HIP_CHECK(hipStreamSynchronize(nullptr));  // (the memset runs on the null stream, which does not order against q)
-        h->many_a[0] = f; h->many_a[1] = f + fl[0]; h->many_a[2] = h->many_a[1] + fl[1]; h->many_part = h->many_a[2] + fl[2];
-        h->many_action = act; h->many_ctr = (unsigned*)(act + ACT_MANY_MAX);
-        h->many_block = dev;
+        if (const int rc = act_many_alloc(h, sizeof(ActManyTable), sb, fl, 4)) return rc;
     }
-    ActManyTable* tb = (ActManyTable*)h->many_pin;  // (no groups here: every state is a workgroup of its own)
-    tb->n = n; tb->n_groups = 0; tb->which = which; tb->pad = 0;
-    for (int e = 0; e < n; ++e) tb->head[e] = heads_host[e];
-    memcpy(h->many_pin + sizeof(ActManyTable), states_host_pinned, (size_t)n * sb);
-    int rc = IDQN_OK;
-    if (use_graph) {
-        auto key = std::make_tuple((int)n, (void*)q_out_dev, (void*)actions_host_pinned);
-        auto it = h->many_graphs.find(key);
-        if (it == h->many_graphs.end()) {
-            hipGraph_t graph = nullptr;
-            hipGraphExec_t exec = nullptr;
-            if (!h->act_stream) IDQN_HIP_CHECK(hipStreamCreateWithFlags(&h->act_stream, hipStreamNonBlocking));
-            IDQN_HIP_CHECK(hipStreamBeginCapture(h->act_stream, hipStreamCaptureModeRelaxed));
-            rc = fc_act_many_chain(h, n, sb, q_out_dev, poll, actions_host_pinned, h->act_stream);
-            const hipError_t e = hipStreamEndCapture(h->act_stream, &graph);
-            if (rc) return rc;
-            IDQN_HIP_CHECK(e);
-            IDQN_HIP_CHECK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-            IDQN_HIP_CHECK(hipGraphDestroy(graph));
-            it = h->many_graphs.emplace(key, exec).first;
-        }
-        IDQN_HIP_CHECK(hipGraphLaunch(it->second, q));
-    } else if ((rc = fc_act_many_chain(h, n, sb, q_out_dev, poll, actions_host_pinned, q))) {
-        return rc;
-    }
-    if (!poll) {
-        IDQN_HIP_CHECK(hipStreamSynchronize(q));
-        return IDQN_OK;
-    }
-    const unsigned want = ++h->many_expected;
-    volatile int32_t* mail = h->many_mail;
-    bool seen = false;
-    for (long spin = 0; spin < (1L << 34); ++spin) {  // as act_host_wait
-        if ((unsigned)mail[ACT_MANY_MAX] == want) { seen = true; break; }
-        __builtin_ia32_pause();
-        if ((spin & 0xfffff) == 0xfffff && hipStreamQuery(q) != hipErrorNotReady) {
-            seen = (unsigned)mail[ACT_MANY_MAX] == want;
-            break;
-        }
-    }
-    if (!seen) {  // resynchronise the counters, then report
-        IDQN_HIP_CHECK(hipStreamSynchronize(q));
-        IDQN_HIP_CHECK(hipMemcpy(&h->many_expected, h->many_ctr, 4, hipMemcpyDeviceToHost));
-        IDQN_HIP_CHECK(hipMemset(h->many_ctr + 1, 0, 4));
-        IDQN_REQUIRE(false, "idqn_act_host_many_fc: the acting launch finished without delivering its actions");
-    }
-    for (int e = 0; e < n; ++e) actions_host_pinned[e] = mail[e];
-    return IDQN_OK;
+    act_many_fill_table((ActManyTable*)h->many.pin, which, heads_host, n, K, false);
+    memcpy(h->many.pin + sizeof(ActManyTable), states_host_pinned, (size_t)n * sb);
+    return act_many_run(h, "idqn_act_host_many_fc", n, sb, q_out_dev, actions_host_pinned, (hipStream_t)stream,
+                        [&](hipStream_t qs, int32_t* mail_dev) { return fc_act_many_chain(h, n, q_out_dev, mail_dev, qs); });
 }
 
-// The i-IQN acting rule for n <= 32 host states, one head and N fractions each (iqn_act_many_kernels.h): table, fractions
-// and states sit in the handle's pinned block, ONE copy node uploads it, seven launches follow (three conv layers,
-// cosines, embedding, Dense_0 per group of states with one head, the head kernel per state) and the n actions come back
-// through a mailbox of this path's own.  One linear hipGraph per (n, buffers) serves every head assignment, both
-// parameter sets and every set of fractions.  NRG as iqn_act_chain.
-static int iqn_act_many_chain(idqn_handle_t h, int n, size_t state_bytes, float* q_out_dev, bool poll, int32_t* actions_host_pinned,
-                              hipStream_t q) {
-    IDQN_HIP_CHECK(hipMemcpyAsync(h->imany_block, h->imany_pin, sizeof(IqnActManyBlock) + (size_t)n * state_bytes, hipMemcpyHostToDevice, q));
-    const IqnActManyBlock* blk = (const IqnActManyBlock*)h->imany_block;
-    ActManyNets nets;
-    nets.tab = &blk->tab; nets.online = h->online; nets.target = h->target; nets.pstride = h->L.head_stride;
-    const float* in = nullptr;
-    int ih = h->cfg.obs_h, iw = h->cfg.obs_w;
-    for (int i = 0; i < 3; ++i) {
-        const ConvL& l = h->conv[i];
-        ActManyConvArgs a;
-        a.nets = nets; a.in_u8 = i == 0 ? h->imany_block + sizeof(IqnActManyBlock) : nullptr; a.in = in; a.out = h->imany_a[i];
-        a.w_off = l.w_off; a.b_off = l.b_off; a.IH = ih; a.IW = iw; a.CI = l.CI; a.OH = l.OH; a.OW = l.OW; a.CO = l.CO;
-        a.K = l.K; a.S = l.S; a.PLh = l.PLh; a.PLw = l.PLw;
-        int upt = 0;
-        int rc = act_many_conv_plan(h, i, &a.KS, &upt);
-        if (rc) return rc;
-        const dim3 grid(cdiv((long)l.OH * l.OW * l.CO, 256 / a.KS), n);
-        if (l.CI % 32 != 0) hipLaunchKernelGGL((k_act_many_conv<4, 8>), grid, dim3(256), 0, q, a);
-        else if (upt <= 1) hipLaunchKernelGGL((k_act_many_conv<32, 1>), grid, dim3(256), 0, q, a);
-        else if (upt <= 2) hipLaunchKernelGGL((k_act_many_conv<32, 2>), grid, dim3(256), 0, q, a);
-        else hipLaunchKernelGGL((k_act_many_conv<32, 4>), grid, dim3(256), 0, q, a);
-        in = h->imany_a[i]; ih = l.OH; iw = l.OW;
-    }
+// The i-IQN acting rule, N fractions per state (iqn_act_many_kernels.h): seven launches behind the copy node -- three conv
+// layers, cosines, embedding, Dense_0 per group of states with one head, the head kernel per state.  NRG as iqn_act_chain.
+static int iqn_act_many_chain(idqn_handle_t h, int n, float* q_out_dev, int32_t* mail_dev, hipStream_t q) {
+    const ActManySlot& s = h->many;
+    const IqnActManyBlock* blk = (const IqnActManyBlock*)s.block;
+    const ActManyNets nets = act_many_nets(h);
+    int rc = act_many_convs(h, nets, s.block + s.head_bytes, s.a, n, q);
+    if (rc) return rc;
     const int N = h->iqn.N, MT = N > 32 ? 2 : 1, NP = 32 * MT, NRG = 512 / NP;
     IqnActManyCosArgs ca;
-    ca.tau = &blk->tau[0][0]; ca.cosv = h->imany_cos;
+    ca.tau = &blk->tau[0][0]; ca.cosv = s.cos;
     hipLaunchKernelGGL(k_iqn_act_many_cos, dim3((unsigned)N, (unsigned)n), dim3(64), 0, q, ca);
     IqnActManyEmbedArgs ea;
-    ea.nets = nets; ea.cosv = h->imany_cos; ea.psi = h->imany_a[2]; ea.x = h->imany_x; ea.we_off = h->iqn.off_we;
+    ea.nets = nets; ea.cosv = s.cos; ea.psi = s.a[2]; ea.x = s.x; ea.we_off = h->iqn.off_we;
     ea.be_off = h->iqn.off_be; ea.F = h->F; ea.N = N; ea.NP = NP;
     hipLaunchKernelGGL(k_iqn_act_many_embed, dim3((unsigned)cdiv(h->F, 64), (unsigned)MT, (unsigned)n), dim3(256), 0, q, ea);
     IqnActManyDenseArgs d;
-    d.nets = nets; d.x = h->imany_x; d.part = h->imany_part; d.w_off = h->off_w0; d.F = h->F; d.J = h->J; d.NP = NP; d.NRG = NRG;
+    d.nets = nets; d.x = s.x; d.part = s.part; d.w_off = h->off_w0; d.F = h->F; d.J = h->J; d.NP = NP; d.NRG = NRG;
     const dim3 dgrid((unsigned)(NRG * (h->J / 32)), (unsigned)std::min(n, h->cfg.n_heads));
     if (MT == 1) hipLaunchKernelGGL(k_iqn_act_many_dense0<1>, dgrid, dim3(512), 0, q, d);
     else hipLaunchKernelGGL(k_iqn_act_many_dense0<2>, dgrid, dim3(512), 0, q, d);
     IqnActManyHeadArgs ha;
-    ha.nets = nets; ha.part = h->imany_part; ha.b0_off = h->off_b0; ha.w1_off = h->off_w1; ha.b1_off = h->off_b1;
+    ha.nets = nets; ha.part = s.part; ha.b0_off = h->off_b0; ha.w1_off = h->off_w1; ha.b1_off = h->off_b1;
     ha.NRG = NRG; ha.J = h->J; ha.A = h->cfg.n_actions; ha.N = N; ha.NP = NP; ha.n = n; ha.q_out = q_out_dev;
-    ha.action = h->imany_action; ha.mail = poll ? h->imany_mail_dev : nullptr; ha.ctr = h->imany_ctr;
+    ha.action = s.action; ha.mail = mail_dev; ha.ctr = s.ctr;
     if (MT == 1) hipLaunchKernelGGL(k_iqn_act_many_head<1>, dim3(n), dim3(1024), 0, q, ha);
     else hipLaunchKernelGGL(k_iqn_act_many_head<2>, dim3(n), dim3(1024), 0, q, ha);
-    IDQN_HIP_CHECK(hipGetLastError());
-    if (!poll) IDQN_HIP_CHECK(hipMemcpyAsync(actions_host_pinned, h->imany_action, (size_t)n * 4, hipMemcpyDeviceToHost, q));
     return IDQN_OK;
 }
 
@@ -3263,120 +3209,22 @@ extern "C" int idqn_iqn_act_host_many(idqn_handle_t h, int32_t which, const int3
     IDQN_REQUIRE(h->cfg.arch == IDQN_ARCH_CNN && !h->gc.on && h->F % 2 == 0 && h->J % 32 == 0 && h->J <= 512 &&
                      h->cfg.n_actions <= 32 && N <= 64,
                  "idqn_iqn_act_host_many: the single-state kernels take even F, J = 32 m <= 512, <= 32 actions, <= 64 fractions");
-    for (int i = 0; i < 3; ++i) {
-        int ks = 0, upt = 0;
-        int rc = act_many_conv_plan(h, i, &ks, &upt);
-        if (rc) return rc;
-    }
-    hipStream_t q = (hipStream_t)stream;
+    int rc = act_many_conv_plans(h);
+    if (rc) return rc;
     const size_t sb = (size_t)h->cfg.obs_h * h->cfg.obs_w * h->cfg.obs_c;  // bytes of one state
     IDQN_REQUIRE(sb % 4 == 0, "idqn_iqn_act_host_many: %zu bytes per state", sb);
-    static const bool no_poll = getenv("IDQN_ACT_POLL") && atoi(getenv("IDQN_ACT_POLL")) == 0;
-    static const bool use_graph = !(getenv("IDQN_ACT_GRAPH") && atoi(getenv("IDQN_ACT_GRAPH")) == 0);
-    const bool poll = !no_poll;
-    if (!h->imany_block) {
-        const size_t block = sizeof(IqnActManyBlock) + ACT_MANY_MAX * sb + 64;
+    if (!h->many.block) {
         const long NP = N > 32 ? 64 : 32;
         long fl[6] = {0, 0, 0, (long)ACT_MANY_MAX * 64 * IQN_ACT_EMBED, (long)ACT_MANY_MAX * h->F * NP, (long)ACT_MANY_MAX * 512 * h->J};
         for (int i = 0; i < 3; ++i) fl[i] = (long)ACT_MANY_MAX * h->conv[i].OH * h->conv[i].OW * h->conv[i].CO;
-        uint8_t *pin = nullptr, *dev = nullptr;
-        float* f = nullptr;
-        int32_t *act = nullptr, *mail = nullptr, *mail_dev = nullptr;
-        // everything into locals first: a failure part-way frees what it got and leaves the handle as it was
-        auto alloc = [&]() -> int {
-            IDQN_HIP_CHECK(hipHostMalloc((void**)&pin, block, hipHostMallocDefault));
-            IDQN_HIP_CHECK(hipHostMalloc((void**)&mail, 256, hipHostMallocMapped | hipHostMallocCoherent));
-            memset(mail, 0, 256);
-            IDQN_HIP_CHECK(hipHostGetDevicePointer((void**)&mail_dev, mail, 0));
-            IDQN_HIP_CHECK(hipMalloc((void**)&f, (size_t)(fl[0] + fl[1] + fl[2] + fl[3] + fl[4] + fl[5]) * 4));
-            IDQN_HIP_CHECK(hipMalloc((void**)&act, 256));  // actions [32], then the two counters
-            IDQN_HIP_CHECK(hipMemset(act, 0, 256));
-            IDQN_HIP_CHECK(hipMalloc((void**)&dev, block));
-            IDQN_HIP_CHECK(hipStreamSynchronize(nullptr));  // (the memset runs on the null stream, which does not order against q)
-            return IDQN_OK;
-        };
-        if (const int arc = alloc()) {
-            if (pin) (void)hipHostFree(pin);
-            if (mail) (void)hipHostFree(mail);
-            if (f) (void)hipFree(f);
-            if (act) (void)hipFree(act);
-            if (dev) (void)hipFree(dev);
-            return arc;
-        }
-        h->owned.push_back((void*)f);
-        h->owned.push_back((void*)act);
-        h->owned.push_back((void*)dev);
-        h->imany_pin = pin; h->imany_mail = mail; h->imany_mail_dev = mail_dev;
-        h->imany_a[0] = f; h->imany_a[1] = f + fl[0]; h->imany_a[2] = h->imany_a[1] + fl[1]; h->imany_cos = h->imany_a[2] + fl[2];
-        h->imany_x = h->imany_cos + fl[3]; h->imany_part = h->imany_x + fl[4];
-        h->imany_action = act; h->imany_ctr = (unsigned*)(act + ACT_MANY_MAX);
-        h->imany_block = dev;
+        if ((rc = act_many_alloc(h, sizeof(IqnActManyBlock), sb, fl, 6))) return rc;
     }
-    // the table (states grouped by head, in state order within a group), the fractions, the states
-    IqnActManyBlock* blk = (IqnActManyBlock*)h->imany_pin;
-    ActManyTable* tb = &blk->tab;
-    tb->n = n; tb->which = which; tb->pad = 0;
-    int ng = 0, pos = 0;
-    for (int k = 0; k < K && pos < n; ++k) {
-        const int start = pos;
-        for (int e = 0; e < n; ++e)
-            if (heads_host[e] == k) tb->order[pos++] = e;
-        if (pos > start) { tb->g_head[ng] = k; tb->g_start[ng] = start; tb->g_count[ng] = pos - start; ++ng; }
-    }
-    tb->n_groups = ng;
-    for (int e = 0; e < n; ++e) {
-        tb->head[e] = heads_host[e];
-        memcpy(blk->tau[e], taus_host_pinned + (size_t)e * N, (size_t)N * 4);
-    }
-    memcpy(h->imany_pin + sizeof(IqnActManyBlock), states_host_pinned, (size_t)n * sb);
-    int rc = IDQN_OK;
-    if (use_graph) {
-        auto key = std::make_tuple((int)n, (void*)q_out_dev, (void*)actions_host_pinned);
-        auto it = h->imany_graphs.find(key);
-        if (it == h->imany_graphs.end()) {
-            hipGraph_t graph = nullptr;
-            hipGraphExec_t exec = nullptr;
-            if (!h->act_stream) IDQN_HIP_CHECK(hipStreamCreateWithFlags(&h->act_stream, hipStreamNonBlocking));
-            IDQN_HIP_CHECK(hipStreamBeginCapture(h->act_stream, hipStreamCaptureModeRelaxed));
-            rc = iqn_act_many_chain(h, n, sb, q_out_dev, poll, actions_host_pinned, h->act_stream);
-            const hipError_t e = hipStreamEndCapture(h->act_stream, &graph);
-            if (rc) {  // (the graph of a chain that reported an error is not kept)
-                if (graph) (void)hipGraphDestroy(graph);
-                return rc;
-            }
-            IDQN_HIP_CHECK(e);
-            const hipError_t ei = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(graph);
-            IDQN_HIP_CHECK(ei);
-            it = h->imany_graphs.emplace(key, exec).first;
-        }
-        IDQN_HIP_CHECK(hipGraphLaunch(it->second, q));
-    } else if ((rc = iqn_act_many_chain(h, n, sb, q_out_dev, poll, actions_host_pinned, q))) {
-        return rc;
-    }
-    if (!poll) {
-        IDQN_HIP_CHECK(hipStreamSynchronize(q));
-        return IDQN_OK;
-    }
-    const unsigned want = ++h->imany_expected;
-    volatile int32_t* mail = h->imany_mail;
-    bool seen = false;
-    for (long spin = 0; spin < (1L << 34); ++spin) {  // as act_host_wait
-        if ((unsigned)mail[ACT_MANY_MAX] == want) { seen = true; break; }
-        __builtin_ia32_pause();
-        if ((spin & 0xfffff) == 0xfffff && hipStreamQuery(q) != hipErrorNotReady) {
-            seen = (unsigned)mail[ACT_MANY_MAX] == want;
-            break;
-        }
-    }
-    if (!seen) {  // resynchronise the counters, then report
-        IDQN_HIP_CHECK(hipStreamSynchronize(q));
-        IDQN_HIP_CHECK(hipMemcpy(&h->imany_expected, h->imany_ctr, 4, hipMemcpyDeviceToHost));
-        IDQN_HIP_CHECK(hipMemset(h->imany_ctr + 1, 0, 4));
-        IDQN_REQUIRE(false, "idqn_iqn_act_host_many: the acting launch finished without delivering its actions");
-    }
-    for (int e = 0; e < n; ++e) actions_host_pinned[e] = mail[e];
-    return IDQN_OK;
+    IqnActManyBlock* blk = (IqnActManyBlock*)h->many.pin;  // the table, the fractions, the states
+    act_many_fill_table(&blk->tab, which, heads_host, n, K, true);
+    for (int e = 0; e < n; ++e) memcpy(blk->tau[e], taus_host_pinned + (size_t)e * N, (size_t)N * 4);
+    memcpy(h->many.pin + sizeof(IqnActManyBlock), states_host_pinned, (size_t)n * sb);
+    return act_many_run(h, "idqn_iqn_act_host_many", n, sb, q_out_dev, actions_host_pinned, (hipStream_t)stream,
+                        [&](hipStream_t qs, int32_t* mail_dev) { return iqn_act_many_chain(h, n, q_out_dev, mail_dev, qs); });
 }
 
 extern "C" int idqn_debug_buffer(idqn_handle_t h, const char* name, void** ptr_dev, int64_t* nbytes) {
