@@ -26,6 +26,7 @@
 #pragma once
 #include "dense0_update.h"
 #include "fc_kernels.h"
+#include "replay_src_kernels.h"
 
 #define FCP_NPT 24   // parameters per thread of the flat (Adam) view: heads of up to 512 x 24 = 12,288 arena floats
 #define FCP_LDS_BUDGET (160 * 1024 - 256)
@@ -58,7 +59,10 @@ static inline FcParPlan fc_par_plan(const FcNet& n, long P) {
     return p;
 }
 
-__global__ __launch_bounds__(FCM_T) void k_fc_step_par(FcArgs a, FcParPlan p, AdamConsts ad, float* theta, float* mu, float* nu, int do_adam, int prof) {
+// `src` is the minibatch source (replay_src_kernels.h): FcBatchSrc, the caller's contiguous batch (the step as it always was), or
+// FcRingSrc, the replay frame ring (idqn_learn_on_replay_fc / _dev) -- the same single launch either way.
+template <class Src>
+__global__ __launch_bounds__(FCM_T) void k_fc_step_par(FcArgs a, FcParPlan p, AdamConsts ad, float* theta, float* mu, float* nu, int do_adam, int prof, Src src) {
     extern __shared__ __attribute__((aligned(16))) float fl[];
     const int k = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6, bl = lane & 31, h = lane >> 5;
     const int half = wave >> 2, wsub = wave & 3;  // waves 0-3: the online net, waves 4-7: the target net
@@ -90,16 +94,37 @@ __global__ __launch_bounds__(FCM_T) void k_fc_step_par(FcArgs a, FcParPlan p, Ad
         tt4[j] = e < P ? *reinterpret_cast<const float4*>(pt + e) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
     float xin[8], xin2[8];  // the minibatch: element e = t + 512 j of [32][d0] (d0 <= 128)
+    if constexpr (!Src::replay) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int e = t + FCM_T * j;
-        const bool in = e < B * n.d[0];
-        xin[j] = in ? a.s[e] : 0.f;
-        xin2[j] = in ? a.s2[e] : 0.f;
+        for (int j = 0; j < 8; ++j) {
+            const int e = t + FCM_T * j;
+            const bool in = e < B * n.d[0];
+            xin[j] = in ? a.s[e] : 0.f;
+            xin2[j] = in ? a.s2[e] : 0.f;
+        }
     }
     float r_b = 0.f;
     int a_b = 0, t_b = 1;
-    if (t < 32 && t < B) { r_b = a.reward[t]; a_b = a.action[t]; t_b = (int)a.terminal[t]; }
+    if constexpr (!Src::replay) {
+        if (t < 32 && t < B) { r_b = a.reward[t]; a_b = a.action[t]; t_b = (int)a.terminal[t]; }
+    } else {
+        // slot -> element row -> frame: two dependent loads ahead of the minibatch's, behind the parameter loads issued above
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int e = t + FCM_T * j;
+            xin[j] = xin2[j] = 0.f;
+            if (e < B * n.d[0]) {
+                const int b = e / n.d[0], i = e - b * n.d[0];
+                const int32_t* m = src.row(b);
+                xin[j] = src.feature(m, 0, i);
+                xin2[j] = src.feature(m, 1, i);
+            }
+        }
+        if (t < 32 && t < B) {
+            const int32_t* m = src.row(t);
+            a_b = m[4]; r_b = __int_as_float(m[5]); t_b = (int)(uint8_t)m[6];
+        }
+    }
     const float w_b = (t < 32 && t < B && a.is_weight) ? a.is_weight[t] : 1.0f;
     // nothing but finite numbers ever lives in this LDS (edge tiles multiply junk rows by zeros / their results are dropped)
     for (long e = t; e < p.wo_off / 4; e += FCM_T) reinterpret_cast<float4*>(fl)[e] = make_float4(0.f, 0.f, 0.f, 0.f);

@@ -377,6 +377,12 @@ struct idqn_handle_s {
     int32_t* rp_action = nullptr;   // [max_batch] scalars of the sampled rows, written by the staging launch
     float* rp_reward = nullptr;
     uint8_t* rp_terminal = nullptr;
+    // replay-sourced step of the fc / general-shape cnn handles (idqn_learn_on_replay_fc; replay_src_kernels.h): the staging
+    // launch's stacked minibatches [max_batch][obs], and -- set for the duration of a call whose batch runs k_fc_step_par --
+    // the ring as that kernel's minibatch source (slots_dev != nullptr: read from that device array, `slots` unused)
+    void *rp_state = nullptr, *rp_next = nullptr;
+    struct FcReplaySrc { const float* frames; const int32_t* rows; long n_frames, frame_elems; int stack; const int32_t* slots_dev; RpsSlotsPar slots; };
+    const FcReplaySrc* rpf = nullptr;
     const float* is_weight = nullptr;  // prioritized-replay extension (idqn_set_per_buffers)
     float* td_abs = nullptr;
     bool d0_rows = false;  // the last fused Dense_0 launch (pairs of column tiles) finished dL/da3 itself
@@ -930,8 +936,12 @@ int fc_setup(idqn_handle_s* h) {
     h->fcp_plan_ = fc_par_plan(n, h->L.head_stride);
     // IDQN_FC_PAR=0: the two-launch path (k_fc_step_mfma / k_fc_step_lds + k_adam) for every batch size
     if ((getenv("IDQN_FC_PAR") && atoi(getenv("IDQN_FC_PAR")) == 0) || n.dmax > FC_MAX_WIDTH) h->fcp_plan_.floats = 0;
-    if (h->fcp_plan_.floats)
-        IDQN_HIP_CHECK(hipFuncSetAttribute((const void*)k_fc_step_par, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(h->fcp_plan_.floats * 4)));
+    if (h->fcp_plan_.floats) {
+        const int bytes = (int)(h->fcp_plan_.floats * 4);
+        IDQN_HIP_CHECK(hipFuncSetAttribute((const void*)k_fc_step_par<FcBatchSrc>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        IDQN_HIP_CHECK(hipFuncSetAttribute((const void*)k_fc_step_par<FcRingSrc<RpsSlotsPar>>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        IDQN_HIP_CHECK(hipFuncSetAttribute((const void*)k_fc_step_par<FcRingSrc<RpsSlotsDev>>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    }
     h->fcm_plan_ = fc_mfma_plan(n);
     if (n.dmax > FC_MAX_WIDTH) h->fcm_plan_.floats = 0;
     h->fcm_global_ = false;
@@ -2152,8 +2162,18 @@ extern "C" int idqn_learn_on_batch(idqn_handle_t h, const void* state_dev, const
         const size_t lds = (size_t)fp.floats * 4;
         const FcMfmaPlan& fm = h->fcm_plan_;
         const bool par = h->fcp_plan_.floats && batch <= 32;  // one launch: forwards side by side, Adam in the gradient epilogues
-        if (par) hipLaunchKernelGGL(k_fc_step_par, dim3(h->cfg.n_heads), dim3(FCM_T), (size_t)h->fcp_plan_.floats * 4, q, a, h->fcp_plan_, h->ad,
-                                    h->online, h->mu, h->nu, grads_only ? 0 : 1, debug_on("IDQN_FC_PROF") ? 1 : 0);
+        if (par && h->rpf) {  // the minibatch comes from the replay frame ring (idqn_learn_on_replay_fc): the same single launch
+            const idqn_handle_s::FcReplaySrc& r = *h->rpf;
+            const size_t lds_par = (size_t)h->fcp_plan_.floats * 4;
+            const int adam = grads_only ? 0 : 1, prof = debug_on("IDQN_FC_PROF") ? 1 : 0;
+            if (r.slots_dev)
+                hipLaunchKernelGGL(k_fc_step_par<FcRingSrc<RpsSlotsDev>>, dim3(h->cfg.n_heads), dim3(FCM_T), lds_par, q, a, h->fcp_plan_, h->ad, h->online, h->mu,
+                                   h->nu, adam, prof, FcRingSrc<RpsSlotsDev>{r.frames, r.rows, r.n_frames, r.frame_elems, r.stack, RpsSlotsDev{r.slots_dev}});
+            else
+                hipLaunchKernelGGL(k_fc_step_par<FcRingSrc<RpsSlotsPar>>, dim3(h->cfg.n_heads), dim3(FCM_T), lds_par, q, a, h->fcp_plan_, h->ad, h->online, h->mu,
+                                   h->nu, adam, prof, FcRingSrc<RpsSlotsPar>{r.frames, r.rows, r.n_frames, r.frame_elems, r.stack, r.slots});
+        } else if (par) hipLaunchKernelGGL(k_fc_step_par<FcBatchSrc>, dim3(h->cfg.n_heads), dim3(FCM_T), (size_t)h->fcp_plan_.floats * 4, q, a, h->fcp_plan_, h->ad,
+                                    h->online, h->mu, h->nu, grads_only ? 0 : 1, debug_on("IDQN_FC_PROF") ? 1 : 0, FcBatchSrc{});
         else if (fm.floats && h->fcm_global_) hipLaunchKernelGGL(k_fc_step_mfma<true>, dim3(h->cfg.n_heads), dim3(FCM_T), (size_t)fm.floats * 4, q, a, fm.ldw, fm.drows, fm.w_floats);
         else if (fm.floats) hipLaunchKernelGGL(k_fc_step_mfma<false>, dim3(h->cfg.n_heads), dim3(FCM_T), (size_t)fm.floats * 4, q, a, fm.ldw, fm.drows, fm.w_floats);
         else if (fp.BS == 32) hipLaunchKernelGGL(k_fc_step_lds<32>, dim3(h->cfg.n_heads), dim3(FC_T), lds, q, a, fp.tw, fp.wfl);
@@ -2291,6 +2311,107 @@ extern "C" int idqn_learn_on_replay_dev(idqn_handle_t h, const uint8_t* frame_ri
     IDQN_REQUIRE(slots_dev, "idqn_learn_on_replay_dev: null pointer");
     return learn_on_replay(h, "idqn_learn_on_replay_dev", frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, slots_dev, batch,
                            stack, nullptr, batch_mean_divisor, flags, stream);
+}
+
+// update_online_params on the frame ring for the handles learn_on_replay refuses: MLP ("fc") handles over float32 frames and
+// general-shape cnn handles (h->gc.on) over uint8 frames.  Exactly one of slots_host / slots_dev is set.
+//   * a batch that runs k_fc_step_par (<= 32 samples, a net that fits it): the ring is that launch's minibatch source
+//     (k_fc_step_par) -- the one-launch step stays one launch.  IDQN_FC_REPLAY_STAGE=1 sends these batches through the
+//     staging launch as well (the A/B of tools/bench_fc_learn_on_replay.py).
+//   * everything else: ONE staging launch (k_rps_stage; per RPS_ARG_SLOTS samples when the slots travel as kernel arguments)
+//     writes the stacked minibatches and the rows' scalars into buffers the handle owns and the plain step runs on those.
+// Either way only that first launch reads the ring, the rows and the slots: the source is a stack local dropped on return.
+// Every refusal comes before anything is enqueued.
+static int learn_on_replay_fc(idqn_handle_t h, const char* fn, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
+                              const int32_t* rows_dev, const int32_t* slots_host, const int32_t* slots_dev, int32_t batch, int32_t stack,
+                              int32_t batch_mean_divisor, uint32_t flags, void* stream) {
+    IDQN_REQUIRE(h && frame_ring_dev && rows_dev && (slots_host || slots_dev), "%s: null pointer", fn);
+    const bool fc = h->cfg.arch == IDQN_ARCH_FC, gc = h->cfg.arch == IDQN_ARCH_CNN && h->gc.on;
+    IDQN_REQUIRE((fc || gc) && h->cfg.n_quantiles == 0 && h->iqn.N == 0,
+                 "%s: serves MLP handles and general-shape cnn handles (plane-path cnn handles: idqn_learn_on_replay; the f32 MFMA "
+                 "conv mode and quantile heads: gather, then learn on the batch)", fn);
+    IDQN_REQUIRE(batch >= 1 && batch <= h->cfg.max_batch, "%s: batch %d not in [1, %d]", fn, batch, h->cfg.max_batch);
+    IDQN_REQUIRE(batch_mean_divisor >= batch, "%s: mean divisor %d < batch %d", fn, batch_mean_divisor, batch);
+    IDQN_REQUIRE(!(flags & (IDQN_F_STOP_AFTER_DENSE0 | IDQN_F_STOP_BEFORE_DENSE0_WGRAD)), "%s: the IDQN_F_STOP_* flags belong to the MFMA cnn path", fn);
+    IDQN_REQUIRE(n_frames >= 1 && frame_bytes >= 1, "%s: n_frames = %ld, frame_bytes = %ld", fn, (long)n_frames, (long)frame_bytes);
+    long obs_elems;
+    if (fc) {
+        obs_elems = h->fc.d[0];
+        IDQN_REQUIRE(stack >= 1 && stack <= 8 && frame_bytes % 4 == 0 && frame_bytes * stack == 4L * obs_elems && ((uintptr_t)frame_ring_dev & 3) == 0,
+                     "%s: an MLP handle takes float32 frames with frame_bytes * stack == 4 * %ld and stack in 1..8 (got frame_bytes %ld, stack %d)",
+                     fn, obs_elems, (long)frame_bytes, stack);
+    } else {
+        obs_elems = (long)h->cfg.obs_h * h->cfg.obs_w * h->cfg.obs_c;
+        IDQN_REQUIRE(stack == h->cfg.obs_c && frame_bytes == (int64_t)h->cfg.obs_h * h->cfg.obs_w,
+                     "%s: a general-shape cnn handle takes uint8 frames of obs_h x obs_w bytes, stack == obs_c (got stack %d, frame_bytes %ld, "
+                     "obs %d x %d x %d)", fn, stack, (long)frame_bytes, h->cfg.obs_h, h->cfg.obs_w, h->cfg.obs_c);
+    }
+    if (!h->rp_state) {
+        const long mb = h->cfg.max_batch, words = (mb * obs_elems * (fc ? 4 : 1) + 3) / 4;
+        float *f = nullptr, *s = nullptr, *s2 = nullptr;
+        int rc;
+        if ((rc = alloc_zero(&f, 3L * mb + 64, h, "replay scalars"))) return rc;
+        if ((rc = alloc_zero(&s, words, h, "replay state"))) return rc;
+        if ((rc = alloc_zero(&s2, words, h, "replay next_state"))) return rc;
+        IDQN_HIP_CHECK(hipStreamSynchronize(nullptr));  // (the zero-fill runs on the null stream)
+        h->rp_action = (int32_t*)f; h->rp_reward = f + mb; h->rp_terminal = (uint8_t*)(f + 2L * mb);
+        h->rp_state = s; h->rp_next = s2;
+    }
+    static const bool always_stage = getenv("IDQN_FC_REPLAY_STAGE") && atoi(getenv("IDQN_FC_REPLAY_STAGE")) != 0;
+    if (fc && h->fcp_plan_.floats && batch <= RPS_PAR_SLOTS && !always_stage) {
+        idqn_handle_s::FcReplaySrc src;
+        src.frames = (const float*)frame_ring_dev; src.rows = rows_dev; src.n_frames = n_frames; src.frame_elems = frame_bytes / 4;
+        src.stack = stack; src.slots_dev = slots_dev;
+        memset(&src.slots, 0, sizeof(src.slots));
+        if (!slots_dev) memcpy(src.slots.slot, slots_host, (size_t)batch * 4);
+        h->rpf = &src;
+        // (the batch pointers only pass the null checks: k_fc_step_par reads the ring and the rows instead)
+        const int rc = idqn_learn_on_batch(h, h->rp_state, h->rp_next, h->rp_action, h->rp_reward, h->rp_terminal, batch, batch_mean_divisor,
+                                           flags, stream);
+        h->rpf = nullptr;
+        return rc;
+    }
+    RpsStageArgs a;
+    a.frames = frame_ring_dev; a.rows = rows_dev; a.n_frames = n_frames; a.frame_elems = fc ? frame_bytes / 4 : frame_bytes;
+    a.stack = stack; a.B = batch; a.first = 0;
+    a.s_out = h->rp_state; a.n_out = h->rp_next; a.a_out = h->rp_action; a.r_out = h->rp_reward; a.t_out = h->rp_terminal;
+    hipStream_t q = (hipStream_t)stream;
+    const long bytes = obs_elems * (fc ? 4 : 1);
+    const unsigned chunks = (unsigned)std::min<long>(16, std::max<long>(1, (bytes + 4 * 256 - 1) / (4 * 256)));  // one iteration per lane up to 16 KB
+    if (slots_dev) {
+        const dim3 grid((unsigned)batch, 2, chunks);
+        if (fc) hipLaunchKernelGGL((k_rps_stage<float, RpsSlotsDev>), grid, dim3(256), 0, q, a, RpsSlotsDev{slots_dev});
+        else hipLaunchKernelGGL((k_rps_stage<uint8_t, RpsSlotsDev>), grid, dim3(256), 0, q, a, RpsSlotsDev{slots_dev});
+    } else {
+        for (int first = 0; first < batch; first += RPS_ARG_SLOTS) {  // (one launch for batches of <= 256 samples)
+            const int n = std::min<int>(RPS_ARG_SLOTS, batch - first);
+            RpsSlots sl;
+            memset(&sl, 0, sizeof(sl));
+            memcpy(sl.slot, slots_host + first, (size_t)n * 4);
+            a.first = first;
+            const dim3 grid((unsigned)n, 2, chunks);
+            if (fc) hipLaunchKernelGGL((k_rps_stage<float, RpsSlots>), grid, dim3(256), 0, q, a, sl);
+            else hipLaunchKernelGGL((k_rps_stage<uint8_t, RpsSlots>), grid, dim3(256), 0, q, a, sl);
+        }
+    }
+    IDQN_HIP_CHECK(hipGetLastError());
+    return idqn_learn_on_batch(h, h->rp_state, h->rp_next, h->rp_action, h->rp_reward, h->rp_terminal, batch, batch_mean_divisor, flags, stream);
+}
+
+extern "C" int idqn_learn_on_replay_fc(idqn_handle_t h, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
+                                       const int32_t* rows_dev, const int32_t* slots_host, int32_t batch, int32_t stack,
+                                       int32_t batch_mean_divisor, uint32_t flags, void* stream) {
+    IDQN_REQUIRE(slots_host, "idqn_learn_on_replay_fc: null pointer");
+    return learn_on_replay_fc(h, "idqn_learn_on_replay_fc", frame_ring_dev, n_frames, frame_bytes, rows_dev, slots_host, nullptr, batch, stack,
+                              batch_mean_divisor, flags, stream);
+}
+
+extern "C" int idqn_learn_on_replay_fc_dev(idqn_handle_t h, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
+                                           const int32_t* rows_dev, const int32_t* slots_dev, int32_t batch, int32_t stack,
+                                           int32_t batch_mean_divisor, uint32_t flags, void* stream) {
+    IDQN_REQUIRE(slots_dev, "idqn_learn_on_replay_fc_dev: null pointer");
+    return learn_on_replay_fc(h, "idqn_learn_on_replay_fc_dev", frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, slots_dev, batch,
+                              stack, batch_mean_divisor, flags, stream);
 }
 
 // iIQN.update_online_params on the HBM frame ring: the same helper, the quantile step behind the staging launch (k_iqn_loss reads

@@ -207,7 +207,8 @@ class DeviceAgent:
     # ``update_online_params`` = ``replay_buffer.sample()`` + ``learn_on_batch`` (idqn.py:65-72, dqn.py:41-47).  On this package's
     # ReplayBuffer with Atari-shaped uint8 frames the two halves are ONE C call (``idqn_learn_on_replay``): the sampler draws the
     # same keys from the same generator, the stacked gather happens inside the step's staging launch and the minibatch is never
-    # materialised.  Anything else (other buffers, shapes, the f32 conv mode) samples, gathers and learns as two calls.
+    # materialised.  MLP agents and the general-shape cnn take ``idqn_learn_on_replay_fc`` the same way (below).  Anything else
+    # (other buffers, other frame dtypes, the f32 conv mode) samples, gathers and learns as two calls.
     fuse_replay_sampling = True
 
     def _replay_fusable(self, rb):
@@ -221,27 +222,78 @@ class DeviceAgent:
         return (stack == 4 and self._obs[2] == 4 and tuple(fshape) == tuple(self._obs[:2]) and np.dtype(fdt) == np.uint8
                 and frame_bytes % 16 == 0)
 
+    # MLP ("fc") agents, and cnn agents whose handle the plane entry refused (the general shapes), take the same one-call route
+    # through ``idqn_learn_on_replay_fc`` under a flag of their own, ``_replay_fc_ok`` (unset: not tried yet; False: this handle or
+    # this buffer's ring is outside the entry's domain, gather and learn from then on; True: it served).
+    def _replay_fc_route(self, rb):
+        """Buffer-side conditions of ``idqn_learn_on_replay_fc``, read on every call (the switches included)."""
+        return (self.fuse_replay_sampling and hasattr(rb, "sample_slots") and hasattr(rb, "ring_view")
+                and getattr(self, "_replay_fc_ok", True) and os.environ.get("IDQN_LEARN_ON_REPLAY", "1") != "0"
+                and (self._arch == "fc" or (self._arch == "cnn" and self.__dict__.get("_replay_fused_ok") is False)))
+
+    def _ring_fc_fusable(self, ring_view):
+        _, _, frame_bytes, _, stack, fshape, fdt = ring_view
+        if self._arch == "fc":
+            return (np.dtype(fdt) == np.float32 and 1 <= stack <= 8 and int(np.prod(fshape, dtype=np.int64)) * stack == self._obs[0]
+                    and frame_bytes * stack == 4 * self._obs[0])
+        return np.dtype(fdt) == np.uint8 and tuple(fshape) == tuple(self._obs[:2]) and stack == self._obs[2]
+
+    def _learn_on_replay_fc(self, rb, view, slots=None, slots_dev=None, gather=None):
+        """One step through ``idqn_learn_on_replay_fc`` (host ``slots``) or ``_dev`` (``slots_dev``); ``gather()`` is the batch
+        of the same slots for the two-call form this falls back to when the entry answers "not this handle" the first time."""
+        frames, n_frames, frame_bytes, rows, stack = view[:5]
+        if not self._ring_fc_fusable(view):
+            self._replay_fc_ok = False
+            return self._learn(gather())
+        B = int(slots.size if slots_dev is None else slots_dev.numel())
+        self._ensure_handle(B)
+        lib = _hip.lib()
+        if slots_dev is None:
+            name = "idqn_learn_on_replay_fc"
+            rc = lib.idqn_learn_on_replay_fc(self._handle, _hip.ptr(frames), int(n_frames), int(frame_bytes), _hip.ptr(rows),
+                                             slots.ctypes.data, B, int(stack), B, 0, _hip.current_stream())
+        else:
+            name = "idqn_learn_on_replay_fc_dev"
+            rc = lib.idqn_learn_on_replay_fc_dev(self._handle, _hip.ptr(frames), int(n_frames), int(frame_bytes), _hip.ptr(rows),
+                                                 _hip.ptr(slots_dev), B, int(stack), B, 0, _hip.current_stream())
+        if rc == _hip.E_INVALID and self.__dict__.get("_replay_fc_ok") is None:
+            self._replay_fc_ok = False  # not this handle (the f32 conv mode, ...): same slots, two calls, from now on
+            return self._learn(gather())
+        _hip.check(rc, name)
+        self._replay_fc_ok = True
+        return self._losses
+
     def _sample_and_learn(self, replay_buffer):
         rb = replay_buffer
-        if not (type(self)._learn is DeviceAgent._learn and self._replay_fusable(rb)):
+        if type(self)._learn is not DeviceAgent._learn:
             return self._learn(rb.sample())
-        slots = rb.sample_slots()
-        frames, n_frames, frame_bytes, rows, stack, fshape, fdt = view = rb.ring_view()
-        if not self._ring_fusable(view):
-            self._replay_fused_ok = False
-            return self._learn(rb._gather(slots))
-        B = int(slots.size)
-        self._ensure_handle(B)
+        if self._replay_fusable(rb):
+            slots = rb.sample_slots()
+            frames, n_frames, frame_bytes, rows, stack, fshape, fdt = view = rb.ring_view()
+            if not self._ring_fusable(view):
+                self._replay_fused_ok = False
+            else:
+                B = int(slots.size)
+                self._ensure_handle(B)
+                slots = np.ascontiguousarray(slots, np.int32)
+                rc = _hip.lib().idqn_learn_on_replay(self._handle, _hip.ptr(frames), int(n_frames), int(frame_bytes), _hip.ptr(rows),
+                                                     slots.ctypes.data, B, int(stack), B, 0, _hip.current_stream())
+                if rc == _hip.E_INVALID and self.__dict__.get("_replay_fused_ok") is None:
+                    # this handle runs another conv path (IDQN_CONV=f32 / the general shapes): not the plane entry, from now on
+                    self._replay_fused_ok = False
+                else:
+                    _hip.check(rc, "idqn_learn_on_replay")
+                    self._replay_fused_ok = True
+                    return self._losses
+            if not self._replay_fc_route(rb):
+                return self._learn(rb._gather(slots))
+        elif self._replay_fc_route(rb):
+            slots = rb.sample_slots()
+            view = rb.ring_view()
+        else:
+            return self._learn(rb.sample())
         slots = np.ascontiguousarray(slots, np.int32)
-        rc = _hip.lib().idqn_learn_on_replay(self._handle, _hip.ptr(frames), int(n_frames), int(frame_bytes), _hip.ptr(rows),
-                                             slots.ctypes.data, B, int(stack), B, 0, _hip.current_stream())
-        if rc == _hip.E_INVALID and self.__dict__.get("_replay_fused_ok") is None:
-            # this handle runs another conv path (IDQN_CONV=f32 / the general shapes): same slots, two calls, from now on
-            self._replay_fused_ok = False
-            return self._learn(rb._gather(slots))
-        _hip.check(rc, "idqn_learn_on_replay")
-        self._replay_fused_ok = True
-        return self._losses
+        return self._learn_on_replay_fc(rb, view, slots=slots, gather=lambda: rb._gather(slots))
 
     def _local_target_update(self):
         """target <- online (real copy), then online[k] <- online[k+1] over THIS agent's heads (idqn.py:78-80)."""

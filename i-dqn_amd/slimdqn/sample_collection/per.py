@@ -17,11 +17,13 @@ Design (Schaul et al. 2016, proportional variant), all on the GPU, no host synch
   -> ``sumtree_set`` on the same leaves.
 * An ``iIQN`` agent takes the same loop: the quantile loss is weighted per sample and emits the mean absolute pairwise TD
   error per head and sample as its |TD| (``iIQN._learn``).  On a buffer with Atari-shaped uint8 frames the gather is
-  skipped: the leaves go straight to ``idqn_iqn_learn_on_replay_dev``, bit-identical to the gathered step.
+  skipped: the leaves go straight to ``idqn_iqn_learn_on_replay_dev``, bit-identical to the gathered step.  MLP agents (and
+  general-shape cnn agents) skip it the same way through ``idqn_learn_on_replay_fc_dev``.
 """
 import numpy as np
 
 from slimdqn import _hip
+from slimdqn.networks._agent import DeviceAgent
 from slimdqn.sample_collection import sum_tree
 
 
@@ -127,12 +129,17 @@ class PrioritizedLearner:
                    "per_importance_weights")
         # i-IQN on a fused-capable buffer: the leaves (== replay slots, already in device memory) go to the replay-sourced step
         view = self._replay_sourced()
-        batch = rb._gather_device(self._leaves) if view is None else None
+        # ... and so do those of an MLP / general-shape cnn agent (DeviceAgent._learn_on_replay_fc, its own flag and switches)
+        fc_route = view is None and type(agent)._learn is DeviceAgent._learn and agent._replay_fc_route(rb)
+        batch = rb._gather_device(self._leaves) if view is None and not fc_route else None
         agent._ensure_handle(B)
         _hip.check(lib.idqn_set_per_buffers(agent._handle, _hip.ptr(self._weights), _hip.ptr(self._td_abs)),
                    "idqn_set_per_buffers")
         try:
-            if view is None:
+            if fc_route:
+                losses = agent._learn_on_replay_fc(rb, rb.ring_view(), slots_dev=self._leaves,
+                                                   gather=lambda: rb._gather_device(self._leaves))
+            elif view is None:
                 losses = agent._learn(batch)
             else:
                 taus = agent.sample_fractions(B)

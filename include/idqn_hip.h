@@ -147,6 +147,25 @@ int idqn_learn_on_replay(idqn_handle_t h, const uint8_t* frame_ring_dev, int64_t
 int idqn_learn_on_replay_dev(idqn_handle_t h, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
                              const int32_t* rows_dev, const int32_t* slots_dev, int32_t batch, int32_t stack,
                              int32_t batch_mean_divisor, uint32_t flags, void* stream);
+/* The same ONE call (idqn.py:65-72, replay_buffer.py:215-230) for the handles idqn_learn_on_replay refuses; arguments as
+ * idqn_learn_on_replay, results bit for bit those of replay_gather_stacked followed by idqn_learn_on_batch on its outputs.
+ *   MLP ("fc") handles: float32 frames, frame_bytes * stack == 4 * obs dim, stack in 1..8; feature order as replay_gather_stacked
+ *     stacks frame_shape + (stack,): element-major, stack index innermost.  A batch that runs the one-launch step (<= 32 samples,
+ *     a net that fits it) reads its minibatch from the ring inside that launch; other batches go through one staging launch.
+ *   general-shape cnn handles (the conv path of geometries the plane path does not serve): uint8 frames, frame_bytes ==
+ *     obs_h * obs_w (any size), stack == obs_c (any depth); one staging launch, then the step.
+ * Restrictions (IDQN_E_INVALID otherwise, nothing enqueued; callers then gather and call idqn_learn_on_batch): not a plane-path
+ * cnn handle (idqn_learn_on_replay serves those), not the f32 MFMA conv mode, no quantile heads, batch in [1, max_batch],
+ * batch_mean_divisor >= batch, flags as idqn_learn_on_batch accepts them for these handles (no IDQN_F_STOP_*).  Only the first
+ * launch reads the ring, the rows and the slots: nothing of them has to outlive this call.                                   */
+int idqn_learn_on_replay_fc(idqn_handle_t h, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
+                            const int32_t* rows_dev, const int32_t* slots_host, int32_t batch, int32_t stack,
+                            int32_t batch_mean_divisor, uint32_t flags, void* stream);
+/* The same step with the slots in DEVICE memory (slots_dev int32 [batch], e.g. the leaves per_sample_leaves drew); bit-identical
+ * to idqn_learn_on_replay_fc with the same slots on the host.                                                                */
+int idqn_learn_on_replay_fc_dev(idqn_handle_t h, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
+                                const int32_t* rows_dev, const int32_t* slots_dev, int32_t batch, int32_t stack,
+                                int32_t batch_mean_divisor, uint32_t flags, void* stream);
 /* The i-IQN step on the HBM frame ring: replay_gather_stacked + idqn_iqn_learn_on_batch as ONE call, the way idqn_learn_on_replay
  * fuses the plain step.  Arguments frame_ring_dev .. stack as idqn_learn_on_replay (slots_host: HOST memory, read before the call
  * returns), tau_dev as idqn_iqn_learn_on_batch.  Same results, bit for bit, as the gather followed by idqn_iqn_learn_on_batch on
