@@ -27,6 +27,7 @@
 #include "cnn_kernels.h"
 #include "fc_kernels.h"
 #include "fc_par_kernels.h"
+#include "fc_steps_kernels.h"
 #include "iqn_kernels.h"
 #include "gcnn_kernels.h"
 #include "fc_act_many_kernels.h"
@@ -357,6 +358,14 @@ struct idqn_handle_s {
     FcMfmaPlan fcm_plan_;  // LDS plan of k_fc_step_mfma (floats = 0: neither the staged-weights nor the global-weights layout fits)
     bool fcm_global_ = false;  // the plan is fc_mfma_plan_g: weight operands from global memory
     FcParPlan fcp_plan_;  // LDS plan of k_fc_step_par (floats = 0: does not fit); batches of <= 32 samples run it
+    FcParPlan fcs_plan_;  // LDS plan of k_fc_steps_par (fc_steps_kernels.h; floats = 0: idqn_learn_steps_on_replay_fc loops over the single step)
+    // slot staging of idqn_learn_steps_on_replay_fc (host form): a ring of {pinned block, device block, event}; a block is
+    // rewritten only after the event recorded behind the launch that read it has passed
+    int32_t* steps_pin[IDQN_STEPS_STAGING_DEPTH] = {};
+    int32_t* steps_dev[IDQN_STEPS_STAGING_DEPTH] = {};
+    hipEvent_t steps_ev[IDQN_STEPS_STAGING_DEPTH] = {};
+    bool steps_busy[IDQN_STEPS_STAGING_DEPTH] = {};
+    int steps_next = 0;
     // timeline of a whole step (IDQN_F_PROFILE_ALL): one event after every launch; idqn_profile_table averages per name
     std::vector<hipEvent_t> tl_ev;
     std::vector<const char*> tl_name;
@@ -941,6 +950,10 @@ int fc_setup(idqn_handle_s* h) {
         IDQN_HIP_CHECK(hipFuncSetAttribute((const void*)k_fc_step_par<FcBatchSrc>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
         IDQN_HIP_CHECK(hipFuncSetAttribute((const void*)k_fc_step_par<FcRingSrc<RpsSlotsPar>>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
         IDQN_HIP_CHECK(hipFuncSetAttribute((const void*)k_fc_step_par<FcRingSrc<RpsSlotsDev>>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        h->fcs_plan_ = fc_steps_plan(n, h->L.head_stride);
+        if (h->fcs_plan_.floats)
+            IDQN_HIP_CHECK(hipFuncSetAttribute((const void*)k_fc_steps_par<FcRingSrc<RpsSlotsDev>>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               (int)(h->fcs_plan_.floats * 4)));
     }
     h->fcm_plan_ = fc_mfma_plan(n);
     if (n.dmax > FC_MAX_WIDTH) h->fcm_plan_.floats = 0;
@@ -2052,6 +2065,11 @@ extern "C" int idqn_destroy(idqn_handle_t h) {
     if (h->act_mail) (void)hipHostFree(h->act_mail);
     if (h->many.mail) (void)hipHostFree(h->many.mail);
     if (h->many.pin) (void)hipHostFree(h->many.pin);
+    for (int i = 0; i < IDQN_STEPS_STAGING_DEPTH; ++i) {
+        if (h->steps_pin[i]) (void)hipHostFree(h->steps_pin[i]);
+        if (h->steps_dev[i]) (void)hipFree(h->steps_dev[i]);
+        if (h->steps_ev[i]) (void)hipEventDestroy(h->steps_ev[i]);
+    }
     if (h->fact_planes) (void)hipFree(h->fact_planes);
     for (int32_t* p : h->iqn.bwd_items)
         if (p) (void)hipFree(p);
@@ -2313,18 +2331,10 @@ extern "C" int idqn_learn_on_replay_dev(idqn_handle_t h, const uint8_t* frame_ri
                            stack, nullptr, batch_mean_divisor, flags, stream);
 }
 
-// update_online_params on the frame ring for the handles learn_on_replay refuses: MLP ("fc") handles over float32 frames and
-// general-shape cnn handles (h->gc.on) over uint8 frames.  Exactly one of slots_host / slots_dev is set.
-//   * a batch that runs k_fc_step_par (<= 32 samples, a net that fits it): the ring is that launch's minibatch source
-//     (k_fc_step_par) -- the one-launch step stays one launch.  IDQN_FC_REPLAY_STAGE=1 sends these batches through the
-//     staging launch as well (the A/B of tools/bench_fc_learn_on_replay.py).
-//   * everything else: ONE staging launch (k_rps_stage; per RPS_ARG_SLOTS samples when the slots travel as kernel arguments)
-//     writes the stacked minibatches and the rows' scalars into buffers the handle owns and the plain step runs on those.
-// Either way only that first launch reads the ring, the rows and the slots: the source is a stack local dropped on return.
-// Every refusal comes before anything is enqueued.
-static int learn_on_replay_fc(idqn_handle_t h, const char* fn, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
-                              const int32_t* rows_dev, const int32_t* slots_host, const int32_t* slots_dev, int32_t batch, int32_t stack,
-                              int32_t batch_mean_divisor, uint32_t flags, void* stream) {
+// Everything learn_on_replay_fc refuses, before anything is enqueued or allocated (shared with idqn_learn_steps_on_replay_fc).
+static int replay_fc_check(idqn_handle_t h, const char* fn, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
+                           const int32_t* rows_dev, const int32_t* slots_host, const int32_t* slots_dev, int32_t batch, int32_t stack,
+                           int32_t batch_mean_divisor, uint32_t flags, long* obs_elems_out) {
     IDQN_REQUIRE(h && frame_ring_dev && rows_dev && (slots_host || slots_dev), "%s: null pointer", fn);
     const bool fc = h->cfg.arch == IDQN_ARCH_FC, gc = h->cfg.arch == IDQN_ARCH_CNN && h->gc.on;
     IDQN_REQUIRE((fc || gc) && h->cfg.n_quantiles == 0 && h->iqn.N == 0,
@@ -2346,6 +2356,27 @@ static int learn_on_replay_fc(idqn_handle_t h, const char* fn, const uint8_t* fr
                      "%s: a general-shape cnn handle takes uint8 frames of obs_h x obs_w bytes, stack == obs_c (got stack %d, frame_bytes %ld, "
                      "obs %d x %d x %d)", fn, stack, (long)frame_bytes, h->cfg.obs_h, h->cfg.obs_w, h->cfg.obs_c);
     }
+    *obs_elems_out = obs_elems;
+    return IDQN_OK;
+}
+
+// update_online_params on the frame ring for the handles learn_on_replay refuses: MLP ("fc") handles over float32 frames and
+// general-shape cnn handles (h->gc.on) over uint8 frames.  Exactly one of slots_host / slots_dev is set.
+//   * a batch that runs k_fc_step_par (<= 32 samples, a net that fits it): the ring is that launch's minibatch source
+//     (k_fc_step_par) -- the one-launch step stays one launch.  IDQN_FC_REPLAY_STAGE=1 sends these batches through the
+//     staging launch as well (the A/B of tools/bench_fc_learn_on_replay.py).
+//   * everything else: ONE staging launch (k_rps_stage; per RPS_ARG_SLOTS samples when the slots travel as kernel arguments)
+//     writes the stacked minibatches and the rows' scalars into buffers the handle owns and the plain step runs on those.
+// Either way only that first launch reads the ring, the rows and the slots: the source is a stack local dropped on return.
+// Every refusal comes before anything is enqueued.
+static int learn_on_replay_fc(idqn_handle_t h, const char* fn, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
+                              const int32_t* rows_dev, const int32_t* slots_host, const int32_t* slots_dev, int32_t batch, int32_t stack,
+                              int32_t batch_mean_divisor, uint32_t flags, void* stream) {
+    long obs_elems;
+    if (const int rc = replay_fc_check(h, fn, frame_ring_dev, n_frames, frame_bytes, rows_dev, slots_host, slots_dev, batch, stack, batch_mean_divisor,
+                                       flags, &obs_elems))
+        return rc;
+    const bool fc = h->cfg.arch == IDQN_ARCH_FC;
     if (!h->rp_state) {
         const long mb = h->cfg.max_batch, words = (mb * obs_elems * (fc ? 4 : 1) + 3) / 4;
         float *f = nullptr, *s = nullptr, *s2 = nullptr;
@@ -2412,6 +2443,96 @@ extern "C" int idqn_learn_on_replay_fc_dev(idqn_handle_t h, const uint8_t* frame
     IDQN_REQUIRE(slots_dev, "idqn_learn_on_replay_fc_dev: null pointer");
     return learn_on_replay_fc(h, "idqn_learn_on_replay_fc_dev", frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, slots_dev, batch,
                               stack, batch_mean_divisor, flags, stream);
+}
+
+// n_steps consecutive update_online_params on the frame ring as ONE C call (include/idqn_hip.h).  Exactly one of slots_host /
+// slots_dev is set, [n_steps][batch].
+//   * persistent route -- what learn_on_replay_fc runs through the one-launch step (an fc handle whose plan fits, batch <= 32,
+//     IDQN_FC_REPLAY_STAGE unset): ONE launch of k_fc_steps_par (fc_steps_kernels.h) reads the slots from a device block; host
+//     slots reach it through the handle's staging ring (pinned block -> asynchronous copy -> device block, each block guarded by
+//     an event that is waited on before the block is rewritten, so back-to-back calls need no synchronisation).
+//   * loop route -- every other handle and batch learn_on_replay_fc serves: its n_steps steps enqueued here, one after the other.
+//     IDQN_FC_LEARN_STEPS_LOOP=1 sends everything this way (the A/B of tools/bench_fc_learn_steps.py).
+// Every refusal comes before anything is enqueued or allocated.
+static int learn_steps_on_replay_fc(idqn_handle_t h, const char* fn, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
+                                    const int32_t* rows_dev, const int32_t* slots_host, const int32_t* slots_dev, int32_t n_steps,
+                                    int32_t batch, int32_t stack, int32_t batch_mean_divisor, uint32_t flags, void* stream) {
+    IDQN_REQUIRE(h && frame_ring_dev && rows_dev && (slots_host || slots_dev), "%s: null pointer", fn);
+    IDQN_REQUIRE(n_steps >= 1 && n_steps <= IDQN_MAX_STEPS_PER_CALL, "%s: n_steps %d not in [1, %d]", fn, n_steps, IDQN_MAX_STEPS_PER_CALL);
+    IDQN_REQUIRE(flags == 0, "%s: takes no flags (got 0x%x): profile or split a single step through idqn_learn_on_replay_fc", fn, flags);
+    IDQN_REQUIRE(!h->is_weight && !h->td_abs,
+                 "%s: the handle has prioritized-replay buffers set (idqn_set_per_buffers): weights and |TD| belong to one step", fn);
+    long obs_elems;
+    if (const int rc = replay_fc_check(h, fn, frame_ring_dev, n_frames, frame_bytes, rows_dev, slots_host, slots_dev, batch, stack, batch_mean_divisor,
+                                       flags, &obs_elems))
+        return rc;
+    static const bool always_stage = getenv("IDQN_FC_REPLAY_STAGE") && atoi(getenv("IDQN_FC_REPLAY_STAGE")) != 0;
+    const char* force_loop = getenv("IDQN_FC_LEARN_STEPS_LOOP");  // (read per call: the bench switches it between its legs)
+    const bool persistent = h->cfg.arch == IDQN_ARCH_FC && h->fcs_plan_.floats && batch <= RPS_PAR_SLOTS && !always_stage &&
+                            !(force_loop && atoi(force_loop) != 0);
+    if (!persistent) {
+        for (int i = 0; i < n_steps; ++i) {
+            const long o = (long)i * batch;
+            if (const int rc = learn_on_replay_fc(h, fn, frame_ring_dev, n_frames, frame_bytes, rows_dev, slots_host ? slots_host + o : nullptr,
+                                                  slots_dev ? slots_dev + o : nullptr, batch, stack, batch_mean_divisor, 0, stream))
+                return rc;
+        }
+        return IDQN_OK;
+    }
+    hipStream_t q = (hipStream_t)stream;
+    int blk = -1;
+    if (!slots_dev) {
+        blk = h->steps_next;
+        if (!h->steps_pin[blk]) {
+            const size_t bytes = (size_t)IDQN_MAX_STEPS_PER_CALL * RPS_PAR_SLOTS * 4;
+            IDQN_HIP_CHECK(hipHostMalloc((void**)&h->steps_pin[blk], bytes, hipHostMallocDefault));
+            IDQN_HIP_CHECK(hipMalloc((void**)&h->steps_dev[blk], bytes));
+            IDQN_HIP_CHECK(hipEventCreateWithFlags(&h->steps_ev[blk], hipEventDisableTiming));
+        }
+        if (h->steps_busy[blk]) IDQN_HIP_CHECK(hipEventSynchronize(h->steps_ev[blk]));  // the launch that read this block is done
+        h->steps_busy[blk] = false;
+        const size_t bytes = (size_t)n_steps * batch * 4;
+        memcpy(h->steps_pin[blk], slots_host, bytes);
+        IDQN_HIP_CHECK(hipMemcpyAsync(h->steps_dev[blk], h->steps_pin[blk], bytes, hipMemcpyHostToDevice, q));
+        slots_dev = h->steps_dev[blk];
+        h->steps_next = (blk + 1) % IDQN_STEPS_STAGING_DEPTH;
+    }
+    h->pend_B = 0; h->pend_stage = 0;
+    h->tl_on = false;
+    FcArgs a;
+    a.net = h->fc; a.online = h->online; a.target = h->target; a.grad = h->grad; a.P = h->L.head_stride;
+    a.s = nullptr; a.s2 = nullptr; a.action = nullptr; a.reward = nullptr; a.terminal = nullptr;  // (the ring is the minibatch source)
+    a.gamma_n = h->gamma_n; a.B = batch; a.Bdiv = batch_mean_divisor; a.K = h->cfg.n_heads;
+    a.ws = h->fc_ws; a.losses = h->losses; a.q_dbg = h->qdbg;
+    a.count = h->count; a.bcinv = h->bcinv; a.adam_b1 = h->ad.b1; a.adam_b2 = h->ad.b2;
+    a.cum = h->cum; a.finish_step = 1;
+    a.is_weight = nullptr; a.td_abs = nullptr;
+    a.s_stride = 0; a.din = nullptr; a.gm = GradMap{h->gP, h->g_w0_begin, h->g_w0_end, h->g_w0_base};
+    hipLaunchKernelGGL(k_fc_steps_par<FcRingSrc<RpsSlotsDev>>, dim3(h->cfg.n_heads), dim3(FCM_T), (size_t)h->fcs_plan_.floats * 4, q, a, h->fcs_plan_, h->ad,
+                       h->online, h->mu, h->nu, (int)n_steps,
+                       FcRingSrc<RpsSlotsDev>{(const float*)frame_ring_dev, rows_dev, n_frames, frame_bytes / 4, stack, RpsSlotsDev{slots_dev}});
+    IDQN_HIP_CHECK(hipGetLastError());
+    if (blk >= 0) {
+        IDQN_HIP_CHECK(hipEventRecord(h->steps_ev[blk], q));
+        h->steps_busy[blk] = true;
+    }
+    return IDQN_OK;
+}
+
+extern "C" int idqn_learn_steps_on_replay_fc(idqn_handle_t h, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
+                                             const int32_t* rows_dev, const int32_t* slots_host, int32_t n_steps, int32_t batch, int32_t stack,
+                                             int32_t batch_mean_divisor, uint32_t flags, void* stream) {
+    IDQN_REQUIRE(slots_host, "idqn_learn_steps_on_replay_fc: null pointer");
+    return learn_steps_on_replay_fc(h, "idqn_learn_steps_on_replay_fc", frame_ring_dev, n_frames, frame_bytes, rows_dev, slots_host, nullptr, n_steps,
+                                    batch, stack, batch_mean_divisor, flags, stream);
+}
+
+extern "C" int idqn_learn_steps_on_replay_fc_dev(idqn_handle_t h, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
+                                                 const int32_t* rows_dev, const int32_t* slots_dev, int32_t n_steps, int32_t batch, int32_t stack,
+                                                 int32_t batch_mean_divisor, uint32_t flags, void* stream) {
+    IDQN_REQUIRE(slots_dev, "idqn_learn_steps_on_replay_fc_dev: null pointer");
+    return learn_steps_on_replay_fc(h, "idqn_learn_steps_on_replay_fc_dev", frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, slots_dev, n_steps,
+                                    batch, stack, batch_mean_divisor, flags, stream);
 }
 
 // iIQN.update_online_params on the HBM frame ring: the same helper, the quantile step behind the staging launch (k_iqn_loss reads

@@ -130,10 +130,18 @@ class VectorTrainer:
                         stats[i].open_episode()
                     else:
                         active[i] = False
-            for _ in range(stepped):
-                self.total_steps += 1
-                if self.total_steps > self.p["n_initial_samples"]:
-                    self._gradient_step()
+            if hasattr(self.agent, "update_params_many") and self.p.get("fuse_gradient_steps", True):
+                # the vector step's gradient steps as one call; a target update's record follows the run that call closes
+                first = max(self.total_steps, self.p["n_initial_samples"]) + 1
+                self.total_steps += stepped
+                if self.total_steps >= first:
+                    for step, logs in self.agent.update_params_many(first, self.total_steps - first + 1, self.rb):
+                        self.p["wandb"].log({"n_training_steps": step, **logs})
+            else:
+                for _ in range(stepped):
+                    self.total_steps += 1
+                    if self.total_steps > self.p["n_initial_samples"]:
+                        self._gradient_step()
         if hasattr(self.rb, "flush_deferred"):
             self.rb.flush_deferred()
         returns, lengths = [r for s in stats for r in s.returns], [n for s in stats for n in s.lengths]

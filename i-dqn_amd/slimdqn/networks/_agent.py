@@ -26,6 +26,30 @@ def _obs_triplet(observation_dim, arch):
     return (int(np.prod(dims)), 1, 1)
 
 
+def plan_step_runs(first_step, n_steps, update_to_data, target_update_frequency, target_sync_frequency=None):
+    """Cuts the steps ``first_step .. first_step + n_steps - 1`` of the loop ``update_online_params(s, rb);
+    update_target_params(s)`` into runs ``(n_gradient_steps, target_op, last_step)``: the gradient steps of a run (steps with
+    ``s % update_to_data == 0``) may be issued together, then the target operation due at the run's last step -- ``"update"``
+    (``s % target_update_frequency == 0``), ``"sync"`` (``s % target_sync_frequency == 0`` on a step that is no update;
+    ``None`` for ``DQN``, which has no sync) or ``None`` at the end of the range.  Replaying the runs in order is the loop.
+    ``update_to_data`` may be a float, as the parser passes it.  Pure host arithmetic."""
+    runs, n_grad = [], 0
+    for s in range(int(first_step), int(first_step) + int(n_steps)):
+        if s % update_to_data == 0:
+            n_grad += 1
+        op = None
+        if s % target_update_frequency == 0:
+            op = "update"
+        elif target_sync_frequency is not None and s % target_sync_frequency == 0:
+            op = "sync"
+        if op is not None:
+            runs.append((n_grad, op, s))
+            n_grad = 0
+    if n_grad:
+        runs.append((n_grad, None, int(first_step) + int(n_steps) - 1))
+    return runs
+
+
 class _HostAction(int):
     """The greedy action as a host integer that still answers ``.item()`` like the device scalar the reference returns
     (``select_action`` calls ``.item()`` on it, slimdqn/sample_collection/utils.py:21)."""
@@ -294,6 +318,71 @@ class DeviceAgent:
             return self._learn(rb.sample())
         slots = np.ascontiguousarray(slots, np.int32)
         return self._learn_on_replay_fc(rb, view, slots=slots, gather=lambda: rb._gather(slots))
+
+    # n gradient steps of ``update_online_params`` as one C call per ``MAX_STEPS_PER_CALL`` draws (``idqn_learn_steps_on_replay_fc``):
+    # the sampler is drawn n times first -- a uniform sampler's draws do not depend on the learner, so these are the generator
+    # draws of n ``_sample_and_learn`` calls -- and the library runs the steps back to back, MLP nets of the one-launch step inside
+    # one launch.  Flag ``_learn_steps_ok`` (unset: not tried; False: the entry refused this handle / ring, single steps on the
+    # slots already drawn from then on).
+    learn_steps_min = 5  # fewer steps than this go one by one: the call's slot staging costs more than it saves (profiles/fc_learn_steps.json)
+
+    def _sample_and_learn_many(self, rb, n):
+        n = int(n)
+        if n <= 0:
+            return self._losses
+        if (type(self)._learn is not DeviceAgent._learn or type(self)._sample_and_learn is not DeviceAgent._sample_and_learn
+                or not self._replay_fc_route(rb) or n < self.learn_steps_min):
+            for _ in range(n):
+                self._sample_and_learn(rb)
+            return self._losses
+        draws = [np.ascontiguousarray(rb.sample_slots(), np.int32) for _ in range(n)]
+        view = rb.ring_view()
+        frames, n_frames, frame_bytes, rows, stack = view[:5]
+        B = int(draws[0].size)
+        i = 0
+        while i < n and getattr(self, "_learn_steps_ok", True) and self._ring_fc_fusable(view) and all(d.size == B for d in draws):
+            m = min(_hip.MAX_STEPS_PER_CALL, n - i)
+            block = np.ascontiguousarray(np.stack(draws[i : i + m]), np.int32)
+            self._ensure_handle(B)
+            rc = _hip.lib().idqn_learn_steps_on_replay_fc(self._handle, _hip.ptr(frames), int(n_frames), int(frame_bytes), _hip.ptr(rows),
+                                                          block.ctypes.data, m, B, int(stack), B, 0, _hip.current_stream())
+            if rc == _hip.E_INVALID and self.__dict__.get("_learn_steps_ok") is None:
+                self._learn_steps_ok = False  # not this handle: the drawn slots go through the single step, one set at a time
+                break
+            _hip.check(rc, "idqn_learn_steps_on_replay_fc")
+            self._learn_steps_ok = True
+            self._replay_fc_ok = True
+            i += m
+        for slots in draws[i:]:
+            if self._replay_fc_route(rb):
+                self._learn_on_replay_fc(rb, view, slots=slots, gather=lambda slots=slots: rb._gather(slots))
+            else:
+                self._learn(rb._gather(slots))
+        return self._losses
+
+    def _update_params_many(self, base, first_step, n_steps, replay_buffer, target_sync_frequency):
+        """``[(step, logs)]`` of the target updates of ``for s in steps: update_online_params(s, rb); update_target_params(s)``,
+        with the same effect, generator stream, cumulated-loss logs and order.  The gradient steps between two target operations
+        go through ``_sample_and_learn_many`` when ``type(self)`` leaves the four methods of the loop (and the target hooks) as
+        ``base`` defines them; subclasses and wrappers with a step of their own get the plain loop."""
+        cls, out = type(self), []
+        stock = (cls.update_online_params is base.update_online_params and cls.update_target_params is base.update_target_params
+                 and cls._learn is DeviceAgent._learn and cls._sample_and_learn is DeviceAgent._sample_and_learn
+                 and all(getattr(cls, h, None) is getattr(base, h, None) for h in ("_target_update", "_target_sync")))
+        if not stock:
+            for s in range(int(first_step), int(first_step) + int(n_steps)):
+                self.update_online_params(s, replay_buffer)
+                updated, logs = self.update_target_params(s)
+                if updated:
+                    out.append((s, logs))
+            return out
+        for n_grad, op, last in plan_step_runs(first_step, n_steps, self.update_to_data, self.target_update_frequency, target_sync_frequency):
+            self._sample_and_learn_many(replay_buffer, n_grad)
+            if op is not None:
+                updated, logs = self.update_target_params(last)  # (the step is due for `op`: the method does exactly that)
+                if updated:
+                    out.append((last, logs))
+        return out
 
     def _local_target_update(self):
         """target <- online (real copy), then online[k] <- online[k+1] over THIS agent's heads (idqn.py:78-80)."""

@@ -25,6 +25,12 @@ class DQN(DeviceAgent):
         if step % self.update_to_data == 0:
             self._sample_and_learn(replay_buffer)  # = learn_on_batch(.., replay_buffer.sample()), one C call where it can be
 
+    def update_params_many(self, first_step: int, n_steps: int, replay_buffer) -> list:
+        """The loop ``update_online_params(s, rb); update_target_params(s)`` over ``n_steps`` steps from ``first_step`` with the
+        gradient steps between two target updates issued together (``DeviceAgent._update_params_many``); returns
+        ``[(step, logs)]`` of the target updates."""
+        return self._update_params_many(DQN, first_step, n_steps, replay_buffer, None)
+
     def learn_on_batch(self, params, params_target, optimizer_state, batch_samples):
         """dqn.py:60-73 (in place; the state arguments must be this agent's own)."""
         assert params is self.params and params_target is self.target_params and optimizer_state is self.optimizer_state

@@ -42,6 +42,12 @@ class iDQN(DeviceAgent):
         if step % self.update_to_data == 0:
             self._sample_and_learn(replay_buffer)  # = learn_on_batch(.., replay_buffer.sample()), one C call where it can be
 
+    def update_params_many(self, first_step: int, n_steps: int, replay_buffer) -> list:
+        """The loop ``update_online_params(s, rb); update_target_params(s)`` over ``n_steps`` steps from ``first_step``, the
+        gradient steps between two target operations issued as one device call where the agent allows it
+        (``DeviceAgent._update_params_many``); returns ``[(step, logs)]`` of the steps whose target update happened."""
+        return self._update_params_many(iDQN, first_step, n_steps, replay_buffer, self.target_sync_frequency)
+
     def learn_on_batch(self, params, params_target, optimizer_state, batch_samples):
         """idqn.py:96-109.  The three state arguments must be this agent's own (in-place update)."""
         assert params is self.params and params_target is self.target_params and optimizer_state is self.optimizer_state, \

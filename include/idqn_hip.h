@@ -166,6 +166,30 @@ int idqn_learn_on_replay_fc(idqn_handle_t h, const uint8_t* frame_ring_dev, int6
 int idqn_learn_on_replay_fc_dev(idqn_handle_t h, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
                                 const int32_t* rows_dev, const int32_t* slots_dev, int32_t batch, int32_t stack,
                                 int32_t batch_mean_divisor, uint32_t flags, void* stream);
+/* n_steps consecutive replay-sourced steps of an MLP or general-shape cnn handle as ONE call: the handle's state afterwards
+ * -- online parameters, Adam moments, count (+= n_steps), losses / gradient / bias-correction scratch / Q debug rows (the last
+ * step's), cum_losses (added step by step, in order, in f64) -- equals, byte for byte, n_steps consecutive calls of
+ * idqn_learn_on_replay_fc, call i with slots_host + i * batch, the same ring, rows, batch, stack and batch_mean_divisor and
+ * flags = 0, on the same stream.  The target arena is read, never written.
+ *   slots_host: int32 [n_steps][batch], ordinary HOST memory, read before the call returns (staged through pinned blocks the
+ *     handle owns: IDQN_STEPS_STAGING_DEPTH of them, each reused only after the launch that read it has finished, so calls
+ *     may follow each other with no synchronisation between them).  Every slot index is used as it arrives.
+ *   Handles and batches idqn_learn_on_replay_fc runs through its one-launch step (an MLP whose net fits it, batch <= 32) run
+ *     all n_steps in ONE launch that keeps the parameters and moments on chip between the steps; every other handle and
+ *     batch idqn_learn_on_replay_fc serves has its n_steps steps enqueued one after the other inside this call.
+ * Restrictions (IDQN_E_INVALID otherwise, nothing enqueued or allocated): everything idqn_learn_on_replay_fc refuses; n_steps
+ * in [1, IDQN_MAX_STEPS_PER_CALL]; flags == 0; no prioritized-replay buffers set (idqn_set_per_buffers: importance weights
+ * and |TD| belong to one step).                                                                                              */
+#define IDQN_MAX_STEPS_PER_CALL 32
+#define IDQN_STEPS_STAGING_DEPTH 4
+int idqn_learn_steps_on_replay_fc(idqn_handle_t h, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
+                                  const int32_t* rows_dev, const int32_t* slots_host, int32_t n_steps, int32_t batch,
+                                  int32_t stack, int32_t batch_mean_divisor, uint32_t flags, void* stream);
+/* The same call with the slots in DEVICE memory (slots_dev int32 [n_steps][batch]; read by the launches, so it must stay
+ * unchanged until they have run); bit-identical to the host form.                                                          */
+int idqn_learn_steps_on_replay_fc_dev(idqn_handle_t h, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
+                                      const int32_t* rows_dev, const int32_t* slots_dev, int32_t n_steps, int32_t batch,
+                                      int32_t stack, int32_t batch_mean_divisor, uint32_t flags, void* stream);
 /* The i-IQN step on the HBM frame ring: replay_gather_stacked + idqn_iqn_learn_on_batch as ONE call, the way idqn_learn_on_replay
  * fuses the plain step.  Arguments frame_ring_dev .. stack as idqn_learn_on_replay (slots_host: HOST memory, read before the call
  * returns), tau_dev as idqn_iqn_learn_on_batch.  Same results, bit for bit, as the gather followed by idqn_iqn_learn_on_batch on
