@@ -32,6 +32,7 @@
 #include "gcnn_kernels.h"
 #include "fc_act_many_kernels.h"
 #include "dp_internal.h"
+#include "per_step_args.h"
 
 namespace {
 
@@ -2268,18 +2269,11 @@ int iqn_heads_forward(idqn_handle_s* h, const float* const* wbase_v, int V, int 
 }
 }  // namespace
 
-// iDQN.update_online_params (idqn.py:65-72) on the HBM frame ring: replay_buffer.py:215-230's sample() fused into the step.
-// Exactly one of slots_host / slots_dev is set.
-//
-// The replay source is read by ONE launch: the staging launch of cnn_forward (planes_stage), which writes the bf16 pixel planes
-// and the sampled rows' scalars into buffers the handle owns.  Everything after it -- the TD kernel, and on a split step
-// (IDQN_F_STOP_*) the rest that idqn_backward_rest / idqn_finish_step_factored enqueue later, Conv_0's weight gradient
-// included -- reads those handle-owned copies, never the ring, the rows or the slots.  So the source can stay a stack local
-// that is dropped on return, for split steps too: the later calls have nothing of it left to read.  (The stream order still
-// matters to the CALLER: the ring must not be overwritten before the staging launch has run.)
-static int learn_on_replay(idqn_handle_t h, const char* fn, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
-                           const int32_t* rows_dev, const int32_t* slots_host, const int32_t* slots_dev, int32_t batch, int32_t stack,
-                           const float* tau_dev, int32_t batch_mean_divisor, uint32_t flags, void* stream) {
+// Everything learn_on_replay (below) refuses on its own account, before anything is enqueued or allocated (shared with
+// idqn_per_learn_on_replay).
+static int replay_check(idqn_handle_t h, const char* fn, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
+                        const int32_t* rows_dev, const int32_t* slots_host, const int32_t* slots_dev, int32_t batch, int32_t stack,
+                        const float* tau_dev, uint32_t flags) {
     IDQN_REQUIRE(h && frame_ring_dev && rows_dev && (slots_host || slots_dev), "%s: null pointer", fn);
     if (tau_dev) {  // the quantile step (idqn_iqn_learn_on_replay*): the limits of idqn_iqn_learn_on_batch, under the caller's name
         IDQN_REQUIRE(h->iqn.N > 0, "%s: the handle was created without quantile heads (cfg.n_quantiles)", fn);
@@ -2292,6 +2286,23 @@ static int learn_on_replay(idqn_handle_t h, const char* fn, const uint8_t* frame
                      n_frames >= 1 && ((uintptr_t)frame_ring_dev & 15) == 0,
                  "%s: built for uint8 frames of obs_h x obs_w bytes (a multiple of 16), stack 4 == obs_c (got stack %d, "
                  "frame_bytes %ld, obs %d x %d x %d)", fn, stack, (long)frame_bytes, h->cfg.obs_h, h->cfg.obs_w, h->cfg.obs_c);
+    return IDQN_OK;
+}
+
+// iDQN.update_online_params (idqn.py:65-72) on the HBM frame ring: replay_buffer.py:215-230's sample() fused into the step.
+// Exactly one of slots_host / slots_dev is set.
+//
+// The replay source is read by ONE launch: the staging launch of cnn_forward (planes_stage), which writes the bf16 pixel planes
+// and the sampled rows' scalars into buffers the handle owns.  Everything after it -- the TD kernel, and on a split step
+// (IDQN_F_STOP_*) the rest that idqn_backward_rest / idqn_finish_step_factored enqueue later, Conv_0's weight gradient
+// included -- reads those handle-owned copies, never the ring, the rows or the slots.  So the source can stay a stack local
+// that is dropped on return, for split steps too: the later calls have nothing of it left to read.  (The stream order still
+// matters to the CALLER: the ring must not be overwritten before the staging launch has run.)
+static int learn_on_replay(idqn_handle_t h, const char* fn, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
+                           const int32_t* rows_dev, const int32_t* slots_host, const int32_t* slots_dev, int32_t batch, int32_t stack,
+                           const float* tau_dev, int32_t batch_mean_divisor, uint32_t flags, void* stream) {
+    if (const int rc = replay_check(h, fn, frame_ring_dev, n_frames, frame_bytes, rows_dev, slots_host, slots_dev, batch, stack, tau_dev, flags))
+        return rc;
     if (!h->rp_action) {
         const int mb = h->cfg.max_batch;
         float* f = nullptr;
@@ -2445,6 +2456,32 @@ extern "C" int idqn_learn_on_replay_fc_dev(idqn_handle_t h, const uint8_t* frame
                               stack, batch_mean_divisor, flags, stream);
 }
 
+// The handle's host-argument staging ring (idqn_learn_steps_on_replay_fc's slots, idqn_per_learn_on_replay's uniforms): `bytes`
+// <= STEPS_BLOCK_BYTES of ordinary host memory are copied into the next pinned block and their upload into the block's device
+// twin, h->steps_dev[*blk], is enqueued on q.  A block is rewritten only after the event steps_stage_guard recorded behind the
+// launch that read it has passed, so back-to-back calls need no synchronisation.
+static constexpr size_t STEPS_BLOCK_BYTES = (size_t)IDQN_MAX_STEPS_PER_CALL * RPS_PAR_SLOTS * 4;
+static int steps_stage(idqn_handle_t h, const void* host, size_t bytes, hipStream_t q, int* blk_out) {
+    const int blk = h->steps_next;
+    if (!h->steps_pin[blk]) {
+        IDQN_HIP_CHECK(hipHostMalloc((void**)&h->steps_pin[blk], STEPS_BLOCK_BYTES, hipHostMallocDefault));
+        IDQN_HIP_CHECK(hipMalloc((void**)&h->steps_dev[blk], STEPS_BLOCK_BYTES));
+        IDQN_HIP_CHECK(hipEventCreateWithFlags(&h->steps_ev[blk], hipEventDisableTiming));
+    }
+    if (h->steps_busy[blk]) IDQN_HIP_CHECK(hipEventSynchronize(h->steps_ev[blk]));  // the launch that read this block is done
+    h->steps_busy[blk] = false;
+    memcpy(h->steps_pin[blk], host, bytes);
+    IDQN_HIP_CHECK(hipMemcpyAsync(h->steps_dev[blk], h->steps_pin[blk], bytes, hipMemcpyHostToDevice, q));
+    h->steps_next = (blk + 1) % IDQN_STEPS_STAGING_DEPTH;
+    *blk_out = blk;
+    return IDQN_OK;
+}
+static int steps_stage_guard(idqn_handle_t h, int blk, hipStream_t q) {  // behind the last launch that reads block blk
+    IDQN_HIP_CHECK(hipEventRecord(h->steps_ev[blk], q));
+    h->steps_busy[blk] = true;
+    return IDQN_OK;
+}
+
 // n_steps consecutive update_online_params on the frame ring as ONE C call (include/idqn_hip.h).  Exactly one of slots_host /
 // slots_dev is set, [n_steps][batch].
 //   * persistent route -- what learn_on_replay_fc runs through the one-launch step (an fc handle whose plan fits, batch <= 32,
@@ -2482,20 +2519,8 @@ static int learn_steps_on_replay_fc(idqn_handle_t h, const char* fn, const uint8
     hipStream_t q = (hipStream_t)stream;
     int blk = -1;
     if (!slots_dev) {
-        blk = h->steps_next;
-        if (!h->steps_pin[blk]) {
-            const size_t bytes = (size_t)IDQN_MAX_STEPS_PER_CALL * RPS_PAR_SLOTS * 4;
-            IDQN_HIP_CHECK(hipHostMalloc((void**)&h->steps_pin[blk], bytes, hipHostMallocDefault));
-            IDQN_HIP_CHECK(hipMalloc((void**)&h->steps_dev[blk], bytes));
-            IDQN_HIP_CHECK(hipEventCreateWithFlags(&h->steps_ev[blk], hipEventDisableTiming));
-        }
-        if (h->steps_busy[blk]) IDQN_HIP_CHECK(hipEventSynchronize(h->steps_ev[blk]));  // the launch that read this block is done
-        h->steps_busy[blk] = false;
-        const size_t bytes = (size_t)n_steps * batch * 4;
-        memcpy(h->steps_pin[blk], slots_host, bytes);
-        IDQN_HIP_CHECK(hipMemcpyAsync(h->steps_dev[blk], h->steps_pin[blk], bytes, hipMemcpyHostToDevice, q));
+        if (const int rc = steps_stage(h, slots_host, (size_t)n_steps * batch * 4, q, &blk)) return rc;
         slots_dev = h->steps_dev[blk];
-        h->steps_next = (blk + 1) % IDQN_STEPS_STAGING_DEPTH;
     }
     h->pend_B = 0; h->pend_stage = 0;
     h->tl_on = false;
@@ -2512,10 +2537,7 @@ static int learn_steps_on_replay_fc(idqn_handle_t h, const char* fn, const uint8
                        h->online, h->mu, h->nu, (int)n_steps,
                        FcRingSrc<RpsSlotsDev>{(const float*)frame_ring_dev, rows_dev, n_frames, frame_bytes / 4, stack, RpsSlotsDev{slots_dev}});
     IDQN_HIP_CHECK(hipGetLastError());
-    if (blk >= 0) {
-        IDQN_HIP_CHECK(hipEventRecord(h->steps_ev[blk], q));
-        h->steps_busy[blk] = true;
-    }
+    if (blk >= 0) return steps_stage_guard(h, blk, q);
     return IDQN_OK;
 }
 
@@ -2551,6 +2573,54 @@ extern "C" int idqn_iqn_learn_on_replay_dev(idqn_handle_t h, const uint8_t* fram
     IDQN_REQUIRE(slots_dev && tau_dev, "idqn_iqn_learn_on_replay_dev: null pointer");
     return learn_on_replay(h, "idqn_iqn_learn_on_replay_dev", frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, slots_dev, batch,
                            stack, tau_dev, batch, flags, stream);
+}
+
+// One prioritized learner step on the frame ring as ONE C call (include/idqn_hip.h): uniforms (staging ring) -> k_per_draw -> the
+// replay-sourced step of the handle's family on the leaves, weights and |TD| in force for that step only -> k_per_write_back.
+// Every refusal -- this call's and the dispatched entry's -- comes before anything is enqueued, allocated or staged.
+extern "C" int idqn_per_learn_on_replay(idqn_handle_t h, const idqn_per_step_t* per, const uint8_t* frame_ring_dev, int64_t n_frames,
+                                        int64_t frame_bytes, const int32_t* rows_dev, int32_t batch, int32_t stack,
+                                        int32_t batch_mean_divisor, uint32_t flags, void* stream) {
+    const char* fn = "idqn_per_learn_on_replay";
+    IDQN_REQUIRE(h && per && per->weights_dev && per->td_abs_dev, "%s: null pointer", fn);
+    IDQN_REQUIRE(!(flags & ~(IDQN_F_PROFILE | IDQN_F_PROFILE_ALL)), "%s: only the profile flags are supported (got 0x%x)", fn, flags);
+    IDQN_REQUIRE(!h->is_weight && !h->td_abs,
+                 "%s: the handle has prioritized-replay buffers set (idqn_set_per_buffers): the call sets its own for its duration", fn);
+    IDQN_REQUIRE(batch >= 1 && batch <= PER_STEP_MAX_N && batch <= h->cfg.max_batch, "%s: batch %d not in [1, min(%d, %d)]", fn, batch,
+                 PER_STEP_MAX_N, h->cfg.max_batch);
+    const char* bad = per_draw_args_error(per->nodes_dev, per->depth, per->uniforms_host, batch, per->n_items, per->leaves_dev, per->weights_dev);
+    if (!bad) bad = per_write_back_args_error(per->nodes_dev, per->depth, per->leaves_dev, per->td_abs_dev, h->cfg.n_heads, batch, per->tree_scratch_dev);
+    IDQN_REQUIRE(!bad, "%s: %s (depth %d, batch %d, n_items %ld)", fn, bad, per->depth, batch, (long)per->n_items);
+    const bool quantile = h->iqn.N > 0, plane = h->cfg.arch == IDQN_ARCH_CNN && h->planes && !h->gc.on;
+    IDQN_REQUIRE(quantile == (per->tau_dev != nullptr), "%s: tau_dev goes with quantile heads (the handle has n_quantiles = %d)", fn, h->iqn.N);
+    if (quantile || plane) {
+        if (const int rc = replay_check(h, fn, frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, per->leaves_dev, batch, stack, per->tau_dev, flags))
+            return rc;
+        IDQN_REQUIRE(quantile || batch_mean_divisor >= batch, "%s: mean divisor %d < batch %d", fn, batch_mean_divisor, batch);
+    } else {
+        long obs_elems;
+        if (const int rc = replay_fc_check(h, fn, frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, per->leaves_dev, batch, stack,
+                                           batch_mean_divisor, flags, &obs_elems))
+            return rc;
+    }
+    hipStream_t q = (hipStream_t)stream;
+    int blk = -1, rc;
+    if ((rc = steps_stage(h, per->uniforms_host, (size_t)batch * 8, q, &blk))) return rc;
+    if ((rc = per_draw(per->nodes_dev, per->depth, (const double*)h->steps_dev[blk], batch, per->stratified, per->n_items, per->beta,
+                       per->leaves_dev, per->weights_dev, stream)))
+        return rc;
+    if ((rc = steps_stage_guard(h, blk, q))) return rc;
+    h->is_weight = per->weights_dev; h->td_abs = per->td_abs_dev;
+    if (quantile || plane)
+        rc = learn_on_replay(h, fn, frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, per->leaves_dev, batch, stack, per->tau_dev,
+                             quantile ? batch : batch_mean_divisor, flags, stream);
+    else
+        rc = learn_on_replay_fc(h, fn, frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, per->leaves_dev, batch, stack,
+                                batch_mean_divisor, flags, stream);
+    h->is_weight = nullptr; h->td_abs = nullptr;
+    if (rc) return rc;
+    return per_write_back(per->nodes_dev, per->depth, per->leaves_dev, per->td_abs_dev, h->cfg.n_heads, batch, per->reduce_max, per->eps,
+                          per->alpha, per->priorities_dev, per->max_priority_dev, per->tree_scratch_dev, stream);
 }
 
 // One i-IQN gradient step (include/idqn_hip.h).  With idqn_set_per_buffers the loss launch takes the importance weights and

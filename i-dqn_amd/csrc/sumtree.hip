@@ -12,7 +12,13 @@
 // array (capacity 2^20); HBM bytes are negligible (n * depth * 16 B).
 #include <stdarg.h>
 
+#include <map>
+#include <mutex>
+
 #include "common.h"
+#include "sumtree_device.h"
+#include "per_step_args.h"
+#include "per_step_kernels.h"
 
 static thread_local char g_err[512] = "";
 void idqn_set_error(const char* fmt, ...) {
@@ -24,163 +30,17 @@ void idqn_set_error(const char* fmt, ...) {
 extern "C" const char* idqn_last_error(void) { return g_err; }
 // 2: idqn_config_t.n_quantiles, the i-IQN entry points; 3: sumtree_query_host(n_live), the idqn_dp_* family; 4: idqn_learn_on_replay.
 // Still 4 after idqn_learn_on_replay_dev, idqn_dp_learn_on_replay and per_priorities_from_td_gathered, and idqn_learn_on_replay
-// accepting the IDQN_F_STOP_* flags: additions only -- no existing signature, struct or behaviour changed (backward compatible).
+// accepting the IDQN_F_STOP_* flags, and after per_draw, per_write_back and idqn_per_learn_on_replay: additions only -- no existing
+// signature, struct or behaviour changed (backward compatible).
 extern "C" int idqn_abi_version(void) { return 4; }
 
-#define ST_THREADS 1024
-#define ST_MAX_N 4096
-
-// keys: (node index << 32) | original position; padded with ~0.
 __global__ __launch_bounds__(ST_THREADS) void k_sumtree_set(double* __restrict__ nodes, int depth,
                                                             const int32_t* __restrict__ idx,
                                                             const double* __restrict__ val, int n, int m,
                                                             double* __restrict__ delta_scratch) {
     __shared__ unsigned long long key[ST_MAX_N];
     __shared__ unsigned int cur[ST_MAX_N];
-    const int tid = threadIdx.x;
-    const unsigned int first_leaf = (1u << (depth - 1)) - 1u;
-#ifdef ST_PROF
-#define ST_STAMP(i) if (tid == 0) reinterpret_cast<long long*>(delta_scratch)[6000 + (i)] = wall_clock64();
-#else
-#define ST_STAMP(i)
-#endif
-    ST_STAMP(0)
-    // 1. deltas against the CURRENT leaf values, before any de-duplication (sum_tree.py:33-34)
-    for (int i = tid; i < m; i += ST_THREADS) {
-        if (i < n) {
-            unsigned int leaf = first_leaf + (unsigned int)idx[i];
-            delta_scratch[i] = val[i] - nodes[leaf];
-            key[i] = ((unsigned long long)leaf << 32) | (unsigned int)i;
-        } else {
-            key[i] = ~0ull;
-        }
-    }
-    __syncthreads();
-    ST_STAMP(1)
-    // 2. sort by (leaf, position): ascending leaves, first occurrence first (np.unique).  Minibatch-sized sets sort by rank
-    //    counting (keys are unique; LDS broadcast reads, four barriers in all) instead of the bitonic network's 36-45.
-    if (m <= ST_THREADS / 2) {  // (n^2 comparisons: past 512 keys the bitonic network's 55 barriers are cheaper)
-        // P threads per key (P = 1024 / m, a power of two): thread (key i = tid % m, part = tid / m) counts the keys below
-        // key i among every P-th element; the partial counts meet in an LDS integer (order-free).  With one thread per
-        // key the 256-leaf write-back spent 13.8 us here: 12 of the 16 waves had nothing to count but still walked the loop.
-        const int P = ST_THREADS / m, i = tid & (m - 1), part = tid / m;
-        const unsigned long long mine = i < n ? key[i] : ~0ull;
-        if (tid < m) cur[tid] = 0u;  // (cur is free until phase 3)
-        __syncthreads();
-        if (i < n) {
-            int rank = 0;
-            for (int j0 = part; j0 < n; j0 += 8 * P) {
-                unsigned long long kk[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) kk[u] = key[min(j0 + u * P, n - 1)];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) rank += (j0 + u * P < n && kk[u] < mine) ? 1 : 0;
-            }
-            atomicAdd(&cur[i], (unsigned int)rank);
-        }
-        __syncthreads();
-        const unsigned int rk = tid < n ? cur[tid] : 0u;
-        const unsigned long long mine0 = tid < n ? key[tid] : ~0ull;
-        __syncthreads();
-        if (tid < n) key[rk] = mine0;
-        __syncthreads();
-    } else
-    for (int k = 2; k <= m; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < m; i += ST_THREADS) {
-                int p = i ^ j;
-                if (p > i) {
-                    unsigned long long a = key[i], b = key[p];
-                    bool asc = (i & k) == 0;
-                    if ((a > b) == asc) {
-                        key[i] = b;
-                        key[p] = a;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    ST_STAMP(2)
-    // 3. sorted deltas; duplicates of a leaf (every occurrence but the first) contribute exactly +0.0
-    double dl[ST_MAX_N / ST_THREADS];
-#pragma unroll
-    for (int q = 0; q < ST_MAX_N / ST_THREADS; ++q) {
-        int s = tid + q * ST_THREADS;
-        dl[q] = 0.0;
-        if (s < n) {
-            unsigned int leaf = (unsigned int)(key[s] >> 32);
-            bool dup = s > 0 && (unsigned int)(key[s - 1] >> 32) == leaf;
-            dl[q] = dup ? 0.0 : delta_scratch[(unsigned int)key[s]];
-            cur[s] = leaf;
-        }
-    }
-    __syncthreads();
-    // re-use the key array (as doubles) for the sorted deltas
-    double* sdelta = reinterpret_cast<double*>(key);
-#pragma unroll
-    for (int q = 0; q < ST_MAX_N / ST_THREADS; ++q) {
-        int s = tid + q * ST_THREADS;
-        if (s < n) sdelta[s] = dl[q];
-    }
-    __syncthreads();
-    // 4. every (level, run of equal ancestors) pair at once: a node belongs to exactly one level, so the levels are
-    //    independent and all their read-modify-writes are in flight together (one memory round trip instead of
-    //    `depth` dependent ones); the head of each run accumulates its run in ascending leaf order, which is the
-    //    order np.add.at applies the sorted deltas in (sum_tree.py:39-47).  cur[] holds the sorted leaf nodes; the
-    //    ancestor `level` levels up of 0-based heap node x is ((x + 1) >> level) - 1.
-    ST_STAMP(3)
-    const int pairs = n * depth;
-    // Eight (leaf, level) pairs per thread and round: the node reads of all eight are in flight together (one memory round
-    // trip per round instead of one per pair -- a 256-leaf write-back has 5376 pairs, i.e. 5-6 per thread).
-    for (int pr0 = tid; pr0 < pairs; pr0 += 8 * ST_THREADS) {
-        double xs[8];
-        unsigned int nd[8];
-        int st[8], lv[8];
-        bool head[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int pr = pr0 + u * ST_THREADS;
-            head[u] = false;
-            if (pr < pairs) {
-                const int s0 = pr / depth, level = pr - s0 * depth;  // the long runs near the root land on different lanes
-                const unsigned int node = ((cur[s0] + 1u) >> level) - 1u;
-                st[u] = s0; lv[u] = level; nd[u] = node;
-                head[u] = s0 == 0 || ((cur[s0 - 1] + 1u) >> level) - 1u != node;
-                if (head[u]) xs[u] = nodes[node];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            if (!head[u]) continue;
-            // The run's deltas are added strictly one after the other (that order IS the result).  The end of the run does
-            // not depend on the running sum: it is found first (ancestors of sorted leaves never decrease: a binary search,
-            // skipped for the common run of one), so the dependent chain is ONE fp64 add per element -- with the end test
-            // inside the chain the root's run cost ~100 cycles per element (13.8 us of a 256-leaf write-back).
-            const unsigned int node = nd[u];
-            const int level = lv[u];
-            double x = xs[u];
-            int e = st[u], end = e + 1;
-            if (end < n && ((cur[end] + 1u) >> level) - 1u == node) {
-                int lo = end, hi = n;  // invariant: elements [st, lo] belong to the run, element hi does not (or hi == n)
-                while (hi - lo > 1) {
-                    const int mid = (lo + hi) >> 1;
-                    if (((cur[mid] + 1u) >> level) - 1u == node) lo = mid; else hi = mid;
-                }
-                end = hi;
-            }
-            for (; e + 8 <= end; e += 8) {
-                double d[8];
-#pragma unroll
-                for (int w = 0; w < 8; ++w) d[w] = sdelta[e + w];
-#pragma unroll
-                for (int w = 0; w < 8; ++w) x = x + d[w];
-            }
-            for (; e < end; ++e) x = x + sdelta[e];
-            nodes[node] = x;
-        }
-    }
-    ST_STAMP(4)
+    sumtree_set_body(nodes, depth, idx, StValuesGlobal{val}, n, m, delta_scratch, key, cur);  // (sumtree_device.h)
 }
 
 __global__ void k_sumtree_get(const double* __restrict__ nodes, int depth, const int32_t* __restrict__ idx, int n,
@@ -214,40 +74,7 @@ __global__ void k_sumtree_query(const double* __restrict__ nodes, int depth, con
     if (bad) atomicOr(status, bad);
 }
 
-// Latency-oriented variant for minibatch-sized queries: ONE WAVE PER QUERY.  The 2^(s+1)-1 nodes of the s <= 5
-// levels below the current node are fetched by the 64 lanes in one round trip, then the wave descends those levels
-// out of registers (shuffles): depth 21 costs 4 dependent memory round trips instead of 20.  Same comparisons and
-// the same `t -= left_sum` sequence as the scalar walk, so the result is bit-identical.
-__device__ __forceinline__ unsigned int wave_descend(const double* __restrict__ nodes, int depth, double t, int& bad) {
-    const int lane = threadIdx.x & 63;
-    unsigned int node = 0;
-    int level = 0;
-    const int h = lane + 1;                 // 1-based heap number inside the sub-tree; lane 63 idles
-    const int j = 31 - __clz(h);            // its level inside the sub-tree
-    const unsigned int p = h - (1u << j);  // its position in that level
-    while (level < depth - 1) {
-        const int s = min(5, depth - 1 - level);
-        double v = 0.0;
-        if (j <= s && lane < 63) v = nodes[(size_t)(node + 1u) * (1u << j) + p - 1u];
-        int cur = 1;
-        for (int step = 0; step < s; ++step) {
-            const double here = __shfl(v, cur - 1);
-            const double ls = __shfl(v, 2 * cur - 1);
-            if (!(t < here)) bad |= 2;
-            if (t < ls) {
-                cur = 2 * cur;
-            } else {
-                t = t - ls;
-                cur = 2 * cur + 1;
-            }
-        }
-        const int jj = 31 - __clz(cur);
-        node = (node + 1u) * (1u << jj) + (cur - (1u << jj)) - 1u;
-        level += s;
-    }
-    return node;
-}
-
+// Latency-oriented variant for minibatch-sized queries: one wave per query (wave_descend, sumtree_device.h).
 __global__ __launch_bounds__(256) void k_sumtree_query_wave(const double* __restrict__ nodes, int depth,
                                                             const double* __restrict__ targets, int n,
                                                             int32_t* __restrict__ out, int32_t* __restrict__ status) {
@@ -272,11 +99,7 @@ __global__ __launch_bounds__(256) void k_per_sample(const double* __restrict__ n
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= n) return;
     const unsigned int first_leaf = (1u << (depth - 1)) - 1u;
-    const double root = nodes[0];
-    double t = stratified ? ((double)i + uniforms[i]) / (double)n * root : uniforms[i] * root;
-    t = fmin(t, nextafter(root, 0.0));
-    int bad = 0;
-    const unsigned int node = (root > 0.0) ? wave_descend(nodes, depth, t, bad) : first_leaf;
+    const unsigned int node = per_sample_node(nodes, depth, uniforms, i, n, stratified);
     if ((threadIdx.x & 63) == 0) out[i] = (int32_t)(node - first_leaf);
 }
 
@@ -328,14 +151,11 @@ __global__ __launch_bounds__(1024) void k_per_weights(const double* __restrict__
     const unsigned int first_leaf = (1u << (depth - 1)) - 1u;
     const double root = nodes[0];
     double wmax = 0.0;
-    // a descent can land on an empty leaf at or past the item count when rounding in the tree sums leaves a sliver of
-    // mass there: pull it back onto the last live leaf, so that the gather that follows stays inside the store
-    for (int i = threadIdx.x; i < n; i += 1024) leaves[i] = min(max(leaves[i], 0), (int32_t)n_items - 1);
+    for (int i = threadIdx.x; i < n; i += 1024) leaves[i] = per_clamp_leaf(leaves[i], n_items);
     __syncthreads();
     for (int i = threadIdx.x; i < n; i += 1024) {
         const double p = nodes[first_leaf + (unsigned int)leaves[i]];
-        const double w = (p > 0.0 && root > 0.0) ? pow(n_items * p / root, -beta) : 0.0;
-        wmax = fmax(wmax, w);
+        wmax = fmax(wmax, per_raw_weight(p, root, n_items, beta));
     }
     red[threadIdx.x] = wmax;
     __syncthreads();
@@ -346,8 +166,7 @@ __global__ __launch_bounds__(1024) void k_per_weights(const double* __restrict__
     wmax = red[0];
     for (int i = threadIdx.x; i < n; i += 1024) {
         const double p = nodes[first_leaf + (unsigned int)leaves[i]];
-        const double w = (p > 0.0 && root > 0.0) ? pow(n_items * p / root, -beta) : 0.0;
-        out[i] = wmax > 0.0 ? (float)(w / wmax) : 1.0f;
+        out[i] = per_norm_weight(per_raw_weight(p, root, n_items, beta), wmax);
     }
 }
 
@@ -361,13 +180,7 @@ __global__ void k_per_priorities(const float* __restrict__ td_abs, int K, int n,
     if (i >= n) return;
     const int r = i / b, j = i - r * b;
     const float* td = td_abs + (long)r * K * b + j;
-    double acc = 0.0;
-    for (int k = 0; k < K; ++k) {
-        const double v = (double)td[(long)k * b];
-        acc = reduce_max ? fmax(acc, v) : acc + v;
-    }
-    if (!reduce_max) acc /= (double)K;
-    const double pr = pow(acc + eps, alpha);
+    const double pr = per_priority(td, K, b, reduce_max, eps, alpha);
     out[i] = pr;
     if (max_dev) atomicMax(reinterpret_cast<unsigned long long*>(max_dev), (unsigned long long)__double_as_longlong(pr));
 }
@@ -642,6 +455,57 @@ extern "C" int per_priorities_from_td_gathered(const float* td_all_dev, int32_t 
     const int n = world * shard;
     hipLaunchKernelGGL(k_per_priorities, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, td_all_dev, n_heads, n, shard,
                        reduce_max, eps, alpha, priorities_out_dev, max_priority_dev);
+    IDQN_HIP_CHECK(hipGetLastError());
+    return IDQN_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The two ends of a prioritized learner step as one launch each (per_step_kernels.h; include/idqn_hip.h).
+// ---------------------------------------------------------------------------------------------------
+// k_per_draw's arrival counter: one per stream (launches on a stream run one after the other and each leaves its counter at
+// zero), made on the stream's first call and kept for the life of the process.
+static int per_draw_counter(hipStream_t q, unsigned** out) {
+    static std::mutex mu;
+    static std::map<hipStream_t, unsigned*> counters;
+    std::lock_guard<std::mutex> lock(mu);
+    unsigned*& c = counters[q];
+    if (!c) {
+        unsigned* p = nullptr;
+        hipError_t e = hipMalloc((void**)&p, 64);
+        if (e == hipSuccess) e = hipMemset(p, 0, 64);
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);  // (the zero-fill runs on the null stream)
+        if (e != hipSuccess) {
+            if (p) (void)hipFree(p);
+            counters.erase(q);
+            IDQN_HIP_CHECK(e);
+        }
+        c = p;
+    }
+    *out = c;
+    return IDQN_OK;
+}
+
+extern "C" int per_draw(const double* nodes_dev, int32_t depth, const double* uniforms_dev, int32_t n, int32_t stratified,
+                        int64_t n_items, double beta, int32_t* leaves_out_dev, float* weights_out_dev, void* stream) {
+    const char* bad = per_draw_args_error(nodes_dev, depth, uniforms_dev, n, n_items, leaves_out_dev, weights_out_dev);
+    IDQN_REQUIRE(!bad, "per_draw: %s (depth %d, n %d, n_items %ld)", bad, depth, n, (long)n_items);
+    unsigned* arrivals = nullptr;
+    if (const int rc = per_draw_counter((hipStream_t)stream, &arrivals)) return rc;
+    hipLaunchKernelGGL(k_per_draw, dim3(cdiv(n, 4)), dim3(256), 0, (hipStream_t)stream, nodes_dev, depth, uniforms_dev, n, stratified,
+                       (double)n_items, beta, leaves_out_dev, weights_out_dev, arrivals);
+    IDQN_HIP_CHECK(hipGetLastError());
+    return IDQN_OK;
+}
+
+extern "C" int per_write_back(double* nodes_dev, int32_t depth, const int32_t* leaves_dev, const float* td_abs_dev, int32_t n_heads,
+                              int32_t n, int32_t reduce_max, double eps, double alpha, double* priorities_out_dev,
+                              double* max_priority_dev, void* scratch_dev, void* stream) {
+    const char* bad = per_write_back_args_error(nodes_dev, depth, leaves_dev, td_abs_dev, n_heads, n, scratch_dev);
+    IDQN_REQUIRE(!bad, "per_write_back: %s (depth %d, n %d, n_heads %d)", bad, depth, n, n_heads);
+    int m = 1;
+    while (m < n) m <<= 1;
+    hipLaunchKernelGGL(k_per_write_back, dim3(1), dim3(ST_THREADS), 0, (hipStream_t)stream, nodes_dev, depth, leaves_dev, td_abs_dev,
+                       n_heads, n, m, reduce_max, eps, alpha, priorities_out_dev, max_priority_dev, (double*)scratch_dev);
     IDQN_HIP_CHECK(hipGetLastError());
     return IDQN_OK;
 }

@@ -43,6 +43,20 @@ class Leaf(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("offset", C.c_int64), ("ndim", C.c_int32), ("shape", C.c_int64 * 4)]
 
 
+class PerStep(C.Structure):
+    """idqn_per_step_t: the prioritized-replay side of ``idqn_per_learn_on_replay``."""
+    _fields_ = [
+        ("nodes_dev", C.c_void_p), ("depth", C.c_int32), ("n_items", C.c_int64),
+        ("uniforms_host", C.c_void_p),
+        ("stratified", C.c_int32), ("reduce_max", C.c_int32), ("beta", C.c_double), ("eps", C.c_double), ("alpha", C.c_double),
+        ("max_priority_dev", C.c_void_p),
+        ("leaves_dev", C.c_void_p), ("weights_dev", C.c_void_p), ("td_abs_dev", C.c_void_p),
+        ("priorities_dev", C.c_void_p),
+        ("tree_scratch_dev", C.c_void_p),
+        ("tau_dev", C.c_void_p),
+    ]
+
+
 # every exported symbol of include/idqn_hip.h: (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -91,6 +105,10 @@ SYMBOLS = {
     "per_priorities_from_td": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P, _P, _P]),
     "per_priorities_from_td_gathered": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P,
                                                   _P, _P]),
+    "per_draw": (C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int64, C.c_double, _P, _P, _P]),
+    "per_write_back": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P, _P, _P, _P]),
+    "idqn_per_learn_on_replay": (C.c_int, [_P, C.POINTER(PerStep), _P, C.c_int64, C.c_int64, _P, C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_uint32, _P]),
     "idqn_target_update": (C.c_int, [_P, _P]),
     "idqn_target_sync": (C.c_int, [_P, _P]),
     "idqn_q_values": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P]),

@@ -19,7 +19,12 @@ Design (Schaul et al. 2016, proportional variant), all on the GPU, no host synch
   error per head and sample as its |TD| (``iIQN._learn``).  On a buffer with Atari-shaped uint8 frames the gather is
   skipped: the leaves go straight to ``idqn_iqn_learn_on_replay_dev``, bit-identical to the gathered step.  MLP agents (and
   general-shape cnn agents) skip it the same way through ``idqn_learn_on_replay_fc_dev``.
+* Where the agent's replay-sourced conditions hold, the whole chain is ONE C call, ``idqn_per_learn_on_replay`` (two fused
+  kernels around the replay-sourced step), byte-identical to the chain; ``fuse_per_step`` / ``fuse_per_family`` below.
 """
+import ctypes as C
+import os
+
 import numpy as np
 
 from slimdqn import _hip
@@ -108,17 +113,114 @@ class PrioritizedLearner:
         view = rb.ring_view()
         return view if agent._ring_fusable(view) else None
 
+    # The whole step as ONE C call (``idqn_per_learn_on_replay``: uniforms -> k_per_draw -> the agent's replay-sourced step ->
+    # k_per_write_back), byte-identical to the chain below.  Taken when the agent's own replay-sourced conditions hold (its
+    # switches included) and its ``_learn`` is the stock one; a plain plane-path ``iDQN`` / ``DQN`` agent, which the chain
+    # gathers for, qualifies too.  ``IDQN_PER_FUSED=0`` and the attribute switch it off; ``fuse_per_family`` holds the default
+    # per agent family, set from the measurements in profiles/per_step_fused.json.  ``_fused_ok`` (unset: not tried; False: the
+    # entry refused this handle the first time, the chain from then on; True: it served).
+    # Defaults by the rule "the one call stays the default where its median lies below the parent chain's minimum": MLP (47.8
+    # against 50.4 us on the LunarLander net, 341.7 against 342.1 on [520]) and plane-path cnn (292.0 against 297.8 us at B = 32,
+    # 1140.8 against 1144.4 at B = 256) on; general-shape cnn (5386 against 5365 us) and i-IQN (1553.4 against 1551.2 us) off.
+    fuse_per_step = True
+    fuse_per_family = {"plane": True, "fc": True, "gcnn": False, "iqn": False}
+
+    @staticmethod
+    def _general_shape(agent):
+        """Whether a cnn agent's handle runs the general-shape conv path: the plane entry said so, or the library's shape rule
+        restated (``cnn_fast_shape``, csrc/qnet.hip).  Only the default depends on it: both routes leave the same bytes."""
+        if agent.__dict__.get("_replay_fused_ok") is False or os.environ.get("IDQN_CNN_GENERAL", "0") not in ("", "0"):
+            return True
+        net = getattr(agent, "network", None)
+        if net is None:
+            return False
+        f = list(net.features)
+        return not (len(f) == 4 and agent._obs[2] == 4 and min(agent._obs[:2]) >= 8 and net.n_actions <= 32
+                    and all(x in (32, 64) for x in f[:3]) and f[3] % 128 == 0 and 128 <= f[3] <= 512)
+
+    def _fused_route(self):
+        """``(ring view, family)`` when this step goes through ``idqn_per_learn_on_replay``, else None; read on every call."""
+        from slimdqn.networks.iiqn import iIQN
+
+        agent, rb = self.agent, self.rb
+        if not self.fuse_per_step or os.environ.get("IDQN_PER_FUSED", "1") == "0" or self.__dict__.get("_fused_ok") is False:
+            return None
+        if rb._batch_size > 256:
+            return None
+        if isinstance(agent, iIQN):
+            view = self._replay_sourced() if type(agent)._learn is iIQN._learn else None
+            return (view, "iqn") if view is not None and self.fuse_per_family["iqn"] else None
+        if type(agent)._learn is not DeviceAgent._learn:
+            return None
+        family = "fc" if agent._arch == "fc" else ("gcnn" if self._general_shape(agent) else "plane")
+        if not self.fuse_per_family[family]:
+            return None
+        if agent._replay_fusable(rb):
+            view = rb.ring_view()
+            if agent._ring_fusable(view):
+                return view, family
+        if agent._replay_fc_route(rb):
+            view = rb.ring_view()
+            if agent._ring_fc_fusable(view):
+                return view, family
+        return None
+
+    def _step_fused(self, view, u, taus):
+        """The library's code for the one-call step on ring ``view`` with uniforms ``u`` (float64 [B], host)."""
+        rb, tree, agent = self.rb, self.sampler._sum_tree, self.agent
+        B = rb._batch_size
+        frames, n_frames, frame_bytes, rows, stack = view[:5]
+        if taus is not None:
+            agent._upload_fractions(B, taus)
+        agent._ensure_handle(B)
+        p = self.__dict__.get("_per_args")
+        if p is None:
+            p = self._per_args = _hip.PerStep()
+        vp = lambda t: None if t is None else int(t.data_ptr())  # noqa: E731
+        p.nodes_dev, p.depth, p.n_items = vp(tree._nodes_dev), tree._depth, len(self.sampler)
+        p.uniforms_host = u.ctypes.data
+        p.stratified, p.reduce_max, p.beta, p.eps, p.alpha = self.stratified, self.reduce_max, self.beta, self.eps, self.sampler._alpha
+        p.max_priority_dev = vp(self.sampler._max_priority_dev)
+        p.leaves_dev, p.weights_dev, p.td_abs_dev = vp(self._leaves), vp(self._weights), vp(self._td_abs)
+        p.priorities_dev, p.tree_scratch_dev = vp(self._priorities), vp(tree._scratch)
+        p.tau_dev = vp(agent._tau_dev) if taus is not None else None
+        return _hip.lib().idqn_per_learn_on_replay(agent._handle, C.byref(p), _hip.ptr(frames), int(n_frames), int(frame_bytes),
+                                                   _hip.ptr(rows), B, int(stack), B, 0, _hip.current_stream())
+
     def step(self):
         """One prioritized gradient step; returns the per-head losses (device tensor, not synchronised)."""
+        rb, agent = self.rb, self.agent
+        B = rb._batch_size
+        assert rb.add_count, "No samples in replay buffer!"
+        u = self.sampler._rng_key.random(B)  # the one draw from the sampler's generator, whichever route runs
+        route, taus = self._fused_route(), None
+        if route is not None:
+            view, family = route
+            taus = agent.sample_fractions(B) if family == "iqn" else None
+            rc = self._step_fused(view, u, taus)
+            if rc == _hip.E_INVALID and self.__dict__.get("_fused_ok") is None:
+                self._fused_ok = False  # not this handle: the chain from now on -- same uniforms (and fractions) for this step
+                self.fused_refusal = _hip.lib().idqn_last_error().decode(errors="replace")
+            else:
+                _hip.check(rc, "idqn_per_learn_on_replay")
+                self._fused_ok = True
+                if family == "iqn":  # the agent's replay-sourced entry served (the flags its own routes keep)
+                    agent._replay_fused_ok = True
+                elif family == "fc":
+                    agent._replay_fc_ok = True
+                return agent._losses
+        return self._step_chain(u, taus)
+
+    def _step_chain(self, u, taus=None):
+        """The step as a chain of calls on uniforms ``u`` (and, for an i-IQN agent, fractions ``taus`` already drawn)."""
         import torch
 
         lib, q = _hip.lib(), _hip.current_stream()
         rb, tree, agent = self.rb, self.sampler._sum_tree, self.agent
         B = rb._batch_size
-        assert rb.add_count, "No samples in replay buffer!"
         if self._u_ev is not None:
             self._u_ev.synchronize()  # the previous step's upload has left the pinned staging buffer
-        self._u_pin.copy_(torch.from_numpy(self.sampler._rng_key.random(B)))
+        self._u_pin.copy_(torch.from_numpy(u))
         self._u_dev.copy_(self._u_pin, non_blocking=True)
         self._u_ev = torch.cuda.Event()
         self._u_ev.record()
@@ -142,7 +244,7 @@ class PrioritizedLearner:
             elif view is None:
                 losses = agent._learn(batch)
             else:
-                taus = agent.sample_fractions(B)
+                taus = agent.sample_fractions(B) if taus is None else taus
                 rc = agent._learn_on_replay(view, slots_dev=self._leaves, taus=taus)
                 if rc == _hip.E_INVALID and agent.__dict__.get("_replay_fused_ok") is None:
                     agent._replay_fused_ok = False  # another conv path: gathered steps from now on, same leaves and fractions

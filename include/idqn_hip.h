@@ -453,6 +453,46 @@ int per_priorities_from_td(const float* td_abs_dev, int32_t n_heads, int32_t n, 
  * leaves.  Same mean / max, eps, alpha and running maximum; world == 1 is bit-identical to per_priorities_from_td.           */
 int per_priorities_from_td_gathered(const float* td_all_dev, int32_t world, int32_t n_heads, int32_t shard, int32_t reduce_max,
                                     double eps, double alpha, double* priorities_out_dev, double* max_priority_dev, void* stream);
+/* per_sample_leaves + per_importance_weights as ONE launch, n in [1, 256]: leaves_out_dev (int32 [n], already clamped to
+ * [0, n_items - 1]) and weights_out_dev (float [n]) equal, byte for byte, what the two calls leave there for the same tree and
+ * uniforms.  The descents run one wave each over cdiv(n, 4) workgroups; the last workgroup to arrive computes the weights (an
+ * arrival counter per stream, owned by the library, made on the stream's first call).                                        */
+int per_draw(const double* nodes_dev, int32_t depth, const double* uniforms_dev, int32_t n, int32_t stratified, int64_t n_items,
+             double beta, int32_t* leaves_out_dev, float* weights_out_dev, void* stream);
+/* per_priorities_from_td + sumtree_set on the same leaves as ONE launch of one workgroup, n in [1, 256]: the node array,
+ * max_priority_dev[0] (may be NULL) and priorities_out_dev (float64 [n], may be NULL: the values never leave the chip) equal,
+ * byte for byte, the two calls' results -- same sort keys, first occurrence of a duplicate leaf wins, sequential adds per node
+ * in ascending-leaf order.  td_abs_dev float [n_heads][n]; scratch_dev as sumtree_set.                                      */
+int per_write_back(double* nodes_dev, int32_t depth, const int32_t* leaves_dev, const float* td_abs_dev, int32_t n_heads,
+                   int32_t n, int32_t reduce_max, double eps, double alpha, double* priorities_out_dev,
+                   double* max_priority_dev, void* scratch_dev, void* stream);
+/* One prioritized learner step on the HBM frame ring as ONE call: uniforms -> per_draw -> the replay-sourced step of the
+ * handle's family with slots_dev = leaves_dev, the weights and |TD| output in force for this step only -> per_write_back.
+ * Handle state (online parameters, moments, count, losses, cum_losses), tree nodes, max_priority_dev, leaves, weights, |TD| and
+ * priorities afterwards equal, byte for byte, the chain per_sample_leaves, per_importance_weights, idqn_set_per_buffers, the
+ * step, idqn_set_per_buffers(NULL, NULL), per_priorities_from_td, sumtree_set for the same uniforms on the same stream.
+ *   uniforms_host: float64 [batch] in [0, 1), ordinary HOST memory, read before the call returns (staged through the pinned
+ *     blocks of idqn_learn_steps_on_replay_fc, so calls may follow each other with no synchronisation between them).
+ *   The step: idqn_learn_on_replay_dev for plane-path cnn handles, idqn_learn_on_replay_fc_dev for MLP and general-shape cnn
+ *     handles (the one-launch MLP step stays one launch), idqn_iqn_learn_on_replay_dev for handles with quantile heads, which
+ *     take tau_dev (and batch as their mean divisor).
+ * Restrictions (IDQN_E_INVALID otherwise, nothing enqueued, allocated or staged): everything the step's entry refuses; a NULL
+ * pointer other than the three marked; batch in [1, min(256, max_batch)]; depth in [1, 31]; n_items >= 1; tau_dev given exactly
+ * when the handle has quantile heads; no prioritized-replay buffers set on the handle (idqn_set_per_buffers: the call owns them
+ * for its duration and leaves none set); flags IDQN_F_PROFILE / IDQN_F_PROFILE_ALL only.                                     */
+typedef struct idqn_per_step {
+    double* nodes_dev; int32_t depth; int64_t n_items;
+    const double* uniforms_host;   /* [batch] in [0, 1), ordinary HOST memory, read before the call returns */
+    int32_t stratified, reduce_max; double beta, eps, alpha;
+    double* max_priority_dev;      /* may be NULL */
+    int32_t* leaves_dev; float* weights_dev; float* td_abs_dev /* [K][batch] */;
+    double* priorities_dev;        /* may be NULL */
+    void* tree_scratch_dev;        /* as sumtree_set */
+    const float* tau_dev;          /* i-IQN handles: [K][3][N][batch]; NULL otherwise */
+} idqn_per_step_t;
+int idqn_per_learn_on_replay(idqn_handle_t h, const idqn_per_step_t* per, const uint8_t* frame_ring_dev, int64_t n_frames,
+                             int64_t frame_bytes, const int32_t* rows_dev, int32_t batch, int32_t stack,
+                             int32_t batch_mean_divisor, uint32_t flags, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Replay store in HBM (slimdqn/sample_collection/replay_buffer.py:202-230).  The store the product uses is the
