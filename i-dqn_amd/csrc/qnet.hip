@@ -31,6 +31,7 @@
 #include "iqn_kernels.h"
 #include "gcnn_kernels.h"
 #include "fc_act_many_kernels.h"
+#include "fc_group_kernels.h"
 #include "dp_internal.h"
 #include "per_step_args.h"
 
@@ -3246,7 +3247,7 @@ static int act_many_conv_plans(idqn_handle_t h) {  // the entries' check, before
 // states, ONE float workspace of floats[0 .. n_floats) carved in that order into a[0], a[1], a[2], (n_floats == 6: cos, x,)
 // part, action[32] plus the two counters, and the mapped mailbox.  Everything goes into locals first: a failure part-way
 // frees what it got and leaves every field of the slot null.
-static int act_many_alloc(idqn_handle_t h, size_t head_bytes, size_t state_bytes, const long* floats, int n_floats) {
+static int act_many_alloc(ActManySlot& s, std::vector<void*>& owned, size_t head_bytes, size_t state_bytes, const long* floats, int n_floats) {
     const size_t block = head_bytes + ACT_MANY_MAX * state_bytes + 64;
     long total = 0;
     for (int i = 0; i < n_floats; ++i) total += floats[i];
@@ -3273,10 +3274,9 @@ static int act_many_alloc(idqn_handle_t h, size_t head_bytes, size_t state_bytes
         if (dev) (void)hipFree(dev);
         return rc;
     }
-    h->owned.push_back((void*)f);
-    h->owned.push_back((void*)act);
-    h->owned.push_back((void*)dev);
-    ActManySlot& s = h->many;
+    owned.push_back((void*)f);
+    owned.push_back((void*)act);
+    owned.push_back((void*)dev);
     s.pin = pin; s.head_bytes = head_bytes; s.mail = mail; s.mail_dev = mail_dev; s.ws = f;
     float* sub[6];
     for (int i = 0; i < n_floats; ++i) { sub[i] = f; f += floats[i]; }
@@ -3285,6 +3285,9 @@ static int act_many_alloc(idqn_handle_t h, size_t head_bytes, size_t state_bytes
     s.action = act; s.ctr = (unsigned*)(act + ACT_MANY_MAX);
     s.block = dev;
     return IDQN_OK;
+}
+static int act_many_alloc(idqn_handle_t h, size_t head_bytes, size_t state_bytes, const long* floats, int n_floats) {
+    return act_many_alloc(h->many, h->owned, head_bytes, state_bytes, floats, n_floats);
 }
 
 // grouped: the states sorted into groups by head, in state order within a group (the Dense_0 kernels of the cnn and i-IQN
@@ -3334,11 +3337,11 @@ static int act_many_convs(idqn_handle_t h, const ActManyNets& nets, const uint8_
 // What the three entries do once the block is filled: the copy node that uploads head and n states, chain(stream, mail) --
 // the entry's launches, whose last kernel delivers to `mail` unless it is null -- as a replayed graph per (n, buffers) or
 // eagerly (IDQN_ACT_GRAPH=0), then the wait on the slot's mailbox (IDQN_ACT_POLL=0: a device-to-host copy of the actions and a
-// stream synchronisation instead) and the n actions into the caller's buffer.
+// stream synchronisation instead) and the n actions into the caller's buffer.  `s` is the handle's slot, or a group's own
+// (idqn_group_act_host_fc), which captures on the stream of the handle it passes.
 template <class Chain>
-static int act_many_run(idqn_handle_t h, const char* fn_name, int n, size_t state_bytes, float* q_out_dev, int32_t* actions_host_pinned,
-                        hipStream_t q, Chain&& chain) {
-    ActManySlot& s = h->many;
+static int act_many_run(idqn_handle_t h, ActManySlot& s, const char* fn_name, int n, size_t state_bytes, float* q_out_dev,
+                        int32_t* actions_host_pinned, hipStream_t q, Chain&& chain) {
     const bool poll = !act_no_poll();
     auto issue = [&](hipStream_t qs) -> int {
         IDQN_HIP_CHECK(hipMemcpyAsync(s.block, s.pin, s.head_bytes + (size_t)n * state_bytes, hipMemcpyHostToDevice, qs));
@@ -3374,6 +3377,11 @@ static int act_many_run(idqn_handle_t h, const char* fn_name, int n, size_t stat
     }
     for (int e = 0; e < n; ++e) actions_host_pinned[e] = mail[e];
     return IDQN_OK;
+}
+template <class Chain>
+static int act_many_run(idqn_handle_t h, const char* fn_name, int n, size_t state_bytes, float* q_out_dev, int32_t* actions_host_pinned,
+                        hipStream_t q, Chain&& chain) {
+    return act_many_run(h, h->many, fn_name, n, state_bytes, q_out_dev, actions_host_pinned, q, chain);
 }
 
 // select_action's greedy branch on the MFMA cnn path (act_many_kernels.h): five launches behind the copy node -- three conv
@@ -3597,4 +3605,196 @@ extern "C" int idqn_profile_read(idqn_handle_t h, double* mean_ms, int32_t* n_la
     if (kernel_name) snprintf(kernel_name, 64, "%s", h->dominant);
     h->ev_used = 0;
     return IDQN_OK;
+}
+
+// ---- seed groups: S independent fc handles learn and act in one launch (fc_group_kernels.h; include/idqn_hip.h) ---------
+// A group owns no parameters: the members keep their arenas, and every member may still be driven alone between two group
+// calls.  What the group owns: a ring of per-call blocks {FcGroupMember[S], slots} (pinned block -> asynchronous copy ->
+// device block, each guarded by an event that is waited on before the block is rewritten, as idqn_learn_steps_on_replay_fc
+// stages its slots) and ONE acting slot of its own.
+struct idqn_group_s {
+    std::vector<idqn_handle_t> m;
+    size_t block_bytes = 0, slots_off = 0;
+    uint8_t* pin[IDQN_STEPS_STAGING_DEPTH] = {};
+    uint8_t* dev[IDQN_STEPS_STAGING_DEPTH] = {};
+    hipEvent_t ev[IDQN_STEPS_STAGING_DEPTH] = {};
+    bool busy[IDQN_STEPS_STAGING_DEPTH] = {};
+    int next = 0;
+    ActManySlot many;
+    std::vector<void*> owned;
+};
+
+extern "C" int idqn_group_create(const idqn_handle_t* members, int32_t n_members, idqn_group_t* out) {
+    IDQN_REQUIRE(members && out, "idqn_group_create: null pointer");
+    IDQN_REQUIRE(n_members >= 1 && n_members <= ACT_MANY_MAX, "idqn_group_create: %d members, must be in [1, %d]", n_members, ACT_MANY_MAX);
+    for (int g = 0; g < n_members; ++g) {
+        const idqn_handle_t h = members[g];
+        IDQN_REQUIRE(h, "idqn_group_create: member %d is null", g);
+        IDQN_REQUIRE(h->cfg.arch == IDQN_ARCH_FC && h->cfg.n_quantiles == 0 && h->iqn.N == 0,
+                     "idqn_group_create: member %d is not an MLP (fc) handle: groups serve fc handles only", g);
+        IDQN_REQUIRE(h->fcp_plan_.floats != 0,
+                     "idqn_group_create: member %d is outside the one-launch step (layer widths <= 128, heads of <= %d parameters)", g, 512 * FCP_NPT);
+        const idqn_config_t &c = h->cfg, &c0 = members[0]->cfg;
+        bool same = c.obs_h == c0.obs_h && c.obs_w == c0.obs_w && c.obs_c == c0.obs_c && c.n_features == c0.n_features &&
+                    c.n_actions == c0.n_actions && c.n_heads == c0.n_heads && c.max_batch == c0.max_batch;
+        for (int i = 0; same && i < c.n_features; ++i) same = c.features[i] == c0.features[i];
+        IDQN_REQUIRE(same, "idqn_group_create: member %d differs from member 0 in shape (obs, features, n_actions, n_heads, max_batch)", g);
+        for (int j = 0; j < g; ++j)
+            IDQN_REQUIRE(members[j] != h && members[j]->online != h->online,
+                         "idqn_group_create: members %d and %d are the same handle or share an arena: one arena would have two writers", j, g);
+    }
+    const idqn_handle_t h0 = members[0];
+    IDQN_HIP_CHECK(hipFuncSetAttribute((const void*)k_fc_group_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(h0->fcp_plan_.floats * 4)));
+    if (h0->fcs_plan_.floats)
+        IDQN_HIP_CHECK(hipFuncSetAttribute((const void*)k_fc_group_steps, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(h0->fcs_plan_.floats * 4)));
+    idqn_group_s* G = new idqn_group_s();
+    G->m.assign(members, members + n_members);
+    G->slots_off = ((size_t)n_members * sizeof(FcGroupMember) + 15) & ~(size_t)15;
+    G->block_bytes = G->slots_off + (size_t)n_members * STEPS_BLOCK_BYTES;
+    *out = G;
+    return IDQN_OK;
+}
+
+extern "C" int idqn_group_destroy(idqn_group_t G) {
+    if (!G) return IDQN_OK;
+    (void)hipDeviceSynchronize();
+    for (void* p : G->owned) (void)hipFree(p);
+    for (auto& g : G->many.graphs) (void)hipGraphExecDestroy(g.second);
+    if (G->many.mail) (void)hipHostFree(G->many.mail);
+    if (G->many.pin) (void)hipHostFree(G->many.pin);
+    for (int i = 0; i < IDQN_STEPS_STAGING_DEPTH; ++i) {
+        if (G->pin[i]) (void)hipHostFree(G->pin[i]);
+        if (G->dev[i]) (void)hipFree(G->dev[i]);
+        if (G->ev[i]) (void)hipEventDestroy(G->ev[i]);
+    }
+    delete G;
+    return IDQN_OK;
+}
+
+// Everything a group learner call refuses, before anything is enqueued, allocated or staged
+static int group_learn_check(idqn_group_t G, const char* fn, const idqn_group_ring_t* rings, const int32_t* slots_host, int32_t n_steps, int32_t batch,
+                             int32_t mean_divisor, uint32_t flags) {
+    IDQN_REQUIRE(G && rings && slots_host, "%s: null pointer", fn);
+    IDQN_REQUIRE(n_steps >= 1 && n_steps <= IDQN_MAX_STEPS_PER_CALL, "%s: n_steps %d not in [1, %d]", fn, n_steps, IDQN_MAX_STEPS_PER_CALL);
+    IDQN_REQUIRE(batch <= RPS_PAR_SLOTS, "%s: batch %d: a group runs the one-launch step, batches of <= %d samples", fn, batch, RPS_PAR_SLOTS);
+    IDQN_REQUIRE((flags & ~(uint32_t)IDQN_F_GRADS_ONLY) == 0, "%s: flags 0x%x: a group call takes IDQN_F_GRADS_ONLY only (profile a member alone)", fn, flags);
+    for (size_t g = 0; g < G->m.size(); ++g) {
+        const idqn_handle_t h = G->m[g];
+        const idqn_group_ring_t& r = rings[g];
+        IDQN_REQUIRE(!h->is_weight && !h->td_abs,
+                     "%s: member %d has prioritized-replay buffers set (idqn_set_per_buffers): prioritized groups are not served", fn, (int)g);
+        long obs_elems;
+        if (const int rc = replay_fc_check(h, fn, (const uint8_t*)r.frames_dev, r.n_frames, r.frame_bytes, r.rows_dev, slots_host, nullptr, batch, r.stack,
+                                           mean_divisor, flags, &obs_elems))
+            return rc;
+    }
+    return IDQN_OK;
+}
+
+// One launch of grid (K, S): block = {FcGroupMember[S], slots [S][n_steps][batch]}, n_steps == 0: the single step k_fc_group_step
+static int group_launch(idqn_group_t G, const idqn_group_ring_t* rings, const int32_t* slots_host, long member_stride, int n_steps, int32_t batch,
+                        int32_t mean_divisor, bool grads_only, hipStream_t q) {
+    const int S = (int)G->m.size(), ns = std::max(n_steps, 1), blk = G->next;
+    if (!G->pin[blk]) {
+        IDQN_HIP_CHECK(hipHostMalloc((void**)&G->pin[blk], G->block_bytes, hipHostMallocDefault));
+        IDQN_HIP_CHECK(hipMalloc((void**)&G->dev[blk], G->block_bytes));
+        IDQN_HIP_CHECK(hipEventCreateWithFlags(&G->ev[blk], hipEventDisableTiming));
+    }
+    if (G->busy[blk]) IDQN_HIP_CHECK(hipEventSynchronize(G->ev[blk]));  // the launch that read this block is done
+    G->busy[blk] = false;
+    FcGroupMember* tab = (FcGroupMember*)G->pin[blk];
+    int32_t* slots_pin = (int32_t*)(G->pin[blk] + G->slots_off);
+    const int32_t* slots_dev = (const int32_t*)(G->dev[blk] + G->slots_off);
+    const long per = (long)ns * batch;
+    for (int g = 0; g < S; ++g) {
+        const idqn_handle_t h = G->m[g];
+        const idqn_group_ring_t& r = rings[g];
+        memcpy(slots_pin + g * per, slots_host + g * member_stride, (size_t)per * 4);
+        h->pend_B = 0; h->pend_stage = 0;
+        h->tl_on = false;
+        FcGroupMember& m = tab[g];
+        memset(&m, 0, sizeof(m));
+        FcArgs& a = m.a;
+        a.net = h->fc; a.online = h->online; a.target = h->target; a.grad = h->grad; a.P = h->L.head_stride;
+        a.gamma_n = h->gamma_n; a.B = batch; a.Bdiv = mean_divisor; a.K = h->cfg.n_heads;  // (the ring is the minibatch source)
+        a.ws = h->fc_ws; a.losses = h->losses; a.q_dbg = h->qdbg;
+        a.count = h->count; a.bcinv = h->bcinv; a.adam_b1 = h->ad.b1; a.adam_b2 = h->ad.b2;
+        a.cum = h->cum; a.finish_step = grads_only ? 0 : 1;
+        a.gm = GradMap{h->gP, h->g_w0_begin, h->g_w0_end, h->g_w0_base};
+        m.plan = n_steps ? h->fcs_plan_ : h->fcp_plan_;
+        m.ad = h->ad;
+        m.theta = h->online; m.mu = h->mu; m.nu = h->nu;
+        m.src = FcRingSrc<RpsSlotsDev>{(const float*)r.frames_dev, r.rows_dev, r.n_frames, r.frame_bytes / 4, r.stack, RpsSlotsDev{slots_dev + g * per}};
+    }
+    const size_t bytes = G->slots_off + (size_t)S * per * 4;
+    IDQN_HIP_CHECK(hipMemcpyAsync(G->dev[blk], G->pin[blk], bytes, hipMemcpyHostToDevice, q));
+    G->next = (blk + 1) % IDQN_STEPS_STAGING_DEPTH;
+    const idqn_handle_t h0 = G->m[0];
+    const dim3 grid((unsigned)h0->cfg.n_heads, (unsigned)S);
+    if (n_steps) hipLaunchKernelGGL(k_fc_group_steps, grid, dim3(FCM_T), (size_t)h0->fcs_plan_.floats * 4, q, (const FcGroupMember*)G->dev[blk], n_steps);
+    else hipLaunchKernelGGL(k_fc_group_step, grid, dim3(FCM_T), (size_t)h0->fcp_plan_.floats * 4, q, (const FcGroupMember*)G->dev[blk], grads_only ? 0 : 1);
+    IDQN_HIP_CHECK(hipGetLastError());
+    IDQN_HIP_CHECK(hipEventRecord(G->ev[blk], q));
+    G->busy[blk] = true;
+    return IDQN_OK;
+}
+
+extern "C" int idqn_group_learn_on_replay_fc(idqn_group_t G, const idqn_group_ring_t* rings, const int32_t* slots_host, int32_t batch,
+                                             int32_t mean_divisor, uint32_t flags, void* stream) {
+    if (const int rc = group_learn_check(G, "idqn_group_learn_on_replay_fc", rings, slots_host, 1, batch, mean_divisor, flags)) return rc;
+    return group_launch(G, rings, slots_host, batch, 0, batch, mean_divisor, (flags & IDQN_F_GRADS_ONLY) != 0, (hipStream_t)stream);
+}
+
+// n_steps steps of every member: ONE launch of k_fc_group_steps (what the members' own idqn_learn_steps_on_replay_fc would run
+// persistently), or -- IDQN_FC_LEARN_STEPS_LOOP=1 -- n_steps launches of k_fc_group_step enqueued here, one after the other
+extern "C" int idqn_group_learn_steps_on_replay_fc(idqn_group_t G, const idqn_group_ring_t* rings, const int32_t* slots_host, int32_t n_steps,
+                                                   int32_t batch, int32_t mean_divisor, uint32_t flags, void* stream) {
+    const char* fn = "idqn_group_learn_steps_on_replay_fc";
+    IDQN_REQUIRE(flags == 0, "%s: takes no flags (got 0x%x): split a single step through idqn_group_learn_on_replay_fc", fn, flags);
+    if (const int rc = group_learn_check(G, fn, rings, slots_host, n_steps, batch, mean_divisor, flags)) return rc;
+    const char* force_loop = getenv("IDQN_FC_LEARN_STEPS_LOOP");  // (read per call, as the single-handle entry does)
+    if (G->m[0]->fcs_plan_.floats && !(force_loop && atoi(force_loop) != 0))
+        return group_launch(G, rings, slots_host, (long)n_steps * batch, n_steps, batch, mean_divisor, false, (hipStream_t)stream);
+    for (int i = 0; i < n_steps; ++i)
+        if (const int rc = group_launch(G, rings, slots_host + (long)i * batch, (long)n_steps * batch, 0, batch, mean_divisor, false, (hipStream_t)stream))
+            return rc;
+    return IDQN_OK;
+}
+
+// idqn_act_host_many_fc over the members of a group: state e on head heads[e] of member member[e]; the fc chain is ONE launch
+// (every member fits k_fc_act_many1: widths <= 128) behind the copy node, on the group's own slot
+extern "C" int idqn_group_act_host_fc(idqn_group_t G, int32_t which, const int32_t* member_host, const int32_t* heads_host,
+                                      const void* states_host_pinned, int32_t n, float* q_out_dev, int32_t* actions_host_pinned, void* stream) {
+    const char* fn = "idqn_group_act_host_fc";
+    IDQN_REQUIRE(G && member_host && heads_host && states_host_pinned && q_out_dev && actions_host_pinned, "%s: null pointer", fn);
+    IDQN_REQUIRE(n >= 1 && n <= ACT_MANY_MAX, "%s: n = %d, must be in [1, %d]", fn, n, ACT_MANY_MAX);
+    IDQN_REQUIRE(which == 0 || which == 1, "%s: which = %d", fn, which);
+    const idqn_handle_t h0 = G->m[0];
+    const int K = h0->cfg.n_heads, S = (int)G->m.size();
+    for (int e = 0; e < n; ++e) {
+        IDQN_REQUIRE(member_host[e] >= 0 && member_host[e] < S, "%s: member %d of state %d", fn, member_host[e], e);
+        IDQN_REQUIRE(heads_host[e] >= 0 && heads_host[e] < K, "%s: head %d of state %d", fn, heads_host[e], e);
+    }
+    const size_t sb = (size_t)h0->fc.d[0] * 4;
+    ActManySlot& s = G->many;
+    if (!s.block) {
+        long fl[4] = {0, 0, 0, (long)ACT_MANY_MAX * 2 * h0->fc.dmax};
+        if (const int rc = act_many_alloc(s, G->owned, sizeof(FcGroupActTable), sb, fl, 4)) return rc;
+    }
+    FcGroupActTable* gt = (FcGroupActTable*)s.pin;
+    act_many_fill_table(&gt->tab, which, heads_host, n, K, false);
+    for (int e = 0; e < ACT_MANY_MAX; ++e) {  // (entries past n: state 0's, never read)
+        const idqn_handle_t h = G->m[member_host[e < n ? e : 0]];
+        gt->params[e] = (which ? h->target : h->online) + (long)heads_host[e < n ? e : 0] * h->L.head_stride;
+    }
+    memcpy(s.pin + sizeof(FcGroupActTable), states_host_pinned, (size_t)n * sb);
+    return act_many_run(h0, s, fn, n, sb, q_out_dev, actions_host_pinned, (hipStream_t)stream, [&](hipStream_t qs, int32_t* mail_dev) {
+        FcActManyArgs a;
+        a.net = h0->fc;
+        a.nets.tab = (const ActManyTable*)s.block; a.nets.online = nullptr; a.nets.target = nullptr; a.nets.pstride = 0;  // (the bases are in the table)
+        a.s = (const float*)(s.block + s.head_bytes); a.s_ld = h0->fc.d[0]; a.ws = s.part; a.q_out = q_out_dev;
+        a.action = s.action; a.mail = mail_dev; a.ctr = s.ctr; a.n = n;
+        hipLaunchKernelGGL(k_fc_group_act_many1, dim3(n), dim3(512), 0, qs, a, (const FcGroupActTable*)s.block);
+        return IDQN_OK;
+    });
 }

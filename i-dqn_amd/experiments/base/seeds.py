@@ -1,0 +1,132 @@
+"""Trainer loop for S seeds at once: the reference starts one process per seed on one device (``launch_job/*/train.sh``); here S
+(agent, environment, replay buffer) triples advance in lock step inside one process, with ONE acting call and ONE learner
+call per step for all of them (``slimdqn.networks.group.AgentGroup``).
+
+Every triple runs the loop of ``experiments.base.dqn.Trainer`` -- its own key stream, epsilon schedule, epochs that end on its
+own episode boundaries, log records and saved model -- so a seed sees what it would see trained alone.  All unfinished seeds
+share the step counter (each advances one environment step per iteration); a seed whose last epoch has ended stops stepping,
+and from then on the remaining ones are driven through their own agents' calls.
+"""
+import numpy as np
+
+from experiments.base.dqn import EpochStats
+from slimdqn import prng
+from slimdqn.networks.group import AgentGroup
+from slimdqn.sample_collection.replay_buffer import TransitionElement
+from slimdqn.sample_collection.utils import linear_schedule
+
+
+class _Seed:
+    """The loop state ``Trainer`` keeps, for one triple."""
+
+    def __init__(self, key, p, agent, env, rb):
+        self.key, self.p, self.agent, self.env, self.rb = key, p, agent, env, rb
+        self.epsilon = linear_schedule(1.0, p["epsilon_end"], p["epsilon_duration"])
+        self.history, self.epoch, self.done, self.finished = [], 0, 0, p["n_epochs"] <= 0
+        if not self.finished:
+            self.history.append(EpochStats())
+
+
+class SeedTrainer:
+    def __init__(self, keys, p, agents, envs, replay_buffers, save_fn=None, group=None):
+        ps = list(p) if isinstance(p, (list, tuple)) else [p] * len(agents)
+        assert len(keys) == len(ps) == len(agents) == len(envs) == len(replay_buffers)
+        self.seeds = [_Seed(*t) for t in zip(keys, ps, agents, envs, replay_buffers)]
+        self.group = group if group is not None else AgentGroup(agents)
+        self.save_fn, self.total_steps = save_fn, 0
+
+    def _select_actions(self, live):
+        """``select_action`` of every live seed on its own key; the greedy ones share one acting call."""
+        actions, greedy, greedy_keys = {}, [], []
+        for i in live:
+            s = self.seeds[i]
+            s.key, key = prng.split(s.key)
+            explore_key, random_action_key, greedy_key = prng.split(key, 3)
+            if prng.uniform(explore_key) <= s.epsilon(self.total_steps):
+                actions[i] = prng.randint(random_action_key, 0, s.env.n_actions)
+            else:
+                greedy.append(i)
+                greedy_keys.append(greedy_key)
+        if greedy:  # (any subset of the members: the acting call names the member of every state)
+            heads = self.group.select_heads(greedy_keys, greedy)
+            best = self.group.best_actions(0, heads, [self.seeds[i].env.state for i in greedy], greedy)
+            for i, a in zip(greedy, best):
+                actions[i] = int(a)
+        return actions
+
+    def _environment_steps(self, live):
+        observations = {i: self.seeds[i].env.observation for i in live}  # the frame BEFORE the action goes with it
+        actions = self._select_actions(live)
+        out = {}
+        for i in live:
+            s = self.seeds[i]
+            reward, absorbing = s.env.step(actions[i])
+            ended = bool(absorbing) or s.env.n_steps >= s.p["horizon"]
+            stored = s.rb._clipping(reward) if s.rb._clipping is not None else reward
+            s.rb.add(TransitionElement(observations[i], actions[i], stored, absorbing, ended))
+            if ended:
+                s.env.reset()
+            out[i] = (reward, ended)
+        return out
+
+    def _gradient_steps(self, live):
+        learners = [i for i in live if self.total_steps > self.seeds[i].p["n_initial_samples"]]
+        if not learners:
+            return
+        if len(learners) == len(self.seeds):
+            self.group.update_online_params(self.total_steps, [s.rb for s in self.seeds])
+            results = self.group.update_target_params(self.total_steps)
+        else:
+            results = []
+            for i in learners:
+                s = self.seeds[i]
+                s.agent.update_online_params(self.total_steps, s.rb)
+                results.append(s.agent.update_target_params(self.total_steps))
+        for i, (updated, logs) in zip(learners, results):
+            if updated:
+                self.seeds[i].p["wandb"].log({"n_training_steps": self.total_steps, **logs})
+
+    def _end_epoch(self, s):
+        if hasattr(s.rb, "flush_deferred"):
+            s.rb.flush_deferred()
+        avg_return, avg_length, n_episodes = s.history[-1].summary()
+        print(f"\nSeed {s.p.get('seed')} epoch {s.epoch}: Return {avg_return} averaged on {n_episodes} episodes.\n", flush=True)
+        s.p["wandb"].log({"epoch": s.epoch, "n_training_steps": self.total_steps, "avg_return": avg_return,
+                          "avg_length_episode": avg_length})
+        if self.save_fn is not None:
+            self.save_fn(s.p, [e.returns for e in s.history], [e.lengths for e in s.history], s.agent.get_model())
+        s.epoch, s.done = s.epoch + 1, 0
+        if s.epoch >= s.p["n_epochs"]:
+            s.finished = True
+        else:
+            s.history.append(EpochStats())
+
+    def run(self):
+        for s in self.seeds:
+            s.env.reset()
+        while True:
+            live = [i for i, s in enumerate(self.seeds) if not s.finished]
+            if not live:
+                break
+            stepped = self._environment_steps(live)
+            self.total_steps += 1
+            closing = []
+            for i in live:
+                s, (reward, ended) = self.seeds[i], stepped[i]
+                s.done += 1
+                s.history[-1].record(reward)
+                budget = s.p["n_training_steps_per_epoch"]
+                if ended and s.done < budget:
+                    s.history[-1].open_episode()
+                if ended and s.done >= budget:  # an epoch always ends on an episode boundary
+                    closing.append(s)
+            self._gradient_steps(live)
+            for s in closing:
+                self._end_epoch(s)
+        self.group.close()
+        return [([e.returns for e in s.history], [e.lengths for e in s.history]) for s in self.seeds]
+
+
+def train_seeds(keys, p, agents, envs, replay_buffers, save_fn=None):
+    """``experiments.base.dqn.train`` for S seeds in one process; returns ``(returns, lengths)`` per epoch, per seed."""
+    return SeedTrainer(keys, p, agents, envs, replay_buffers, save_fn).run()

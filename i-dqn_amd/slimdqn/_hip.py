@@ -57,6 +57,12 @@ class PerStep(C.Structure):
     ]
 
 
+class GroupRing(C.Structure):
+    """idqn_group_ring_t: one member's replay frame ring, as ``idqn_learn_on_replay_fc`` takes it."""
+    _fields_ = [("frames_dev", C.c_void_p), ("n_frames", C.c_int64), ("frame_bytes", C.c_int64), ("rows_dev", C.c_void_p),
+                ("stack", C.c_int32), ("reserved", C.c_int32)]
+
+
 # every exported symbol of include/idqn_hip.h: (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -121,6 +127,11 @@ SYMBOLS = {
     "idqn_iqn_act_host": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     "idqn_iqn_act_host_begin": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     "idqn_iqn_act_host_many": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P]),
+    "idqn_group_create": (C.c_int, [C.POINTER(_P), C.c_int32, C.POINTER(_P)]),
+    "idqn_group_destroy": (C.c_int, [_P]),
+    "idqn_group_learn_on_replay_fc": (C.c_int, [_P, C.POINTER(GroupRing), _P, C.c_int32, C.c_int32, C.c_uint32, _P]),
+    "idqn_group_learn_steps_on_replay_fc": (C.c_int, [_P, C.POINTER(GroupRing), _P, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, _P]),
+    "idqn_group_act_host_fc": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P]),
     "idqn_debug_buffer": (C.c_int, [_P, C.c_char_p, C.POINTER(_P), C.POINTER(C.c_int64)]),
     "idqn_profile_read": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_char_p]),
     "idqn_profile_table": (C.c_int, [_P, C.c_char_p, C.c_int32]),

@@ -363,6 +363,46 @@ int idqn_iqn_act_host_many(idqn_handle_t h, int32_t which, const int32_t* heads_
                            const float* taus_host_pinned /* [n][N] */, int32_t n,
                            float* q_out_dev /* [n][A] */, int32_t* actions_host_pinned /* [n] */, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Seed groups: S independent MLP ("fc") handles learn and act in ONE launch.  No reference counterpart in code: the
+ * reference runs its seeds as N processes on one device (launch_job/.../train.sh).  The one-launch MLP step uses one
+ * workgroup per head; the heads of a step never talk to each other, so S agents are a grid of (K, S) such workgroups
+ * (csrc/fc_group_kernels.h) and every member's bytes after a group call are the bytes of the same call on that member alone.
+ * A group is an opaque object over S existing handles.  It owns no parameters: the members keep their arenas, their learning
+ * rate, Adam epsilon and gamma^n (a set of seeds or a hyper-parameter sweep), and may be driven alone between group calls
+ * on the same stream.  Destroy the group before its members.
+ * idqn_group_create refuses (IDQN_E_INVALID, nothing changed): n_members outside [1, 32]; a member that is not an fc handle or
+ * whose batches of <= 32 samples do not run the one-launch step; a member whose shape (obs, features, n_actions, n_heads,
+ * max_batch) differs from member 0's; a handle (or an online arena) named twice -- one arena would have two writers.  */
+typedef struct idqn_group_s* idqn_group_t;
+typedef struct idqn_group_ring {   /* a member's replay frame ring, as idqn_learn_on_replay_fc takes it */
+    const void* frames_dev; int64_t n_frames, frame_bytes;
+    const int32_t* rows_dev; int32_t stack, reserved;
+} idqn_group_ring_t;
+int idqn_group_create(const idqn_handle_t* members, int32_t n_members, idqn_group_t* out);
+int idqn_group_destroy(idqn_group_t group);
+/* idqn_learn_on_replay_fc for every member at once: rings [S], slots_host [S][batch] (ordinary host memory, read before the
+ * call returns; they and the S member records travel in ONE pinned block with one upload, staged as
+ * idqn_learn_steps_on_replay_fc stages its slots), one batch, mean divisor and flags for all members.  ONE launch of grid (K, S).
+ * Refuses (IDQN_E_INVALID, nothing enqueued, allocated or staged): batch > 32; flags other than IDQN_F_GRADS_ONLY; a member with
+ * prioritized-replay buffers set (idqn_set_per_buffers); everything idqn_learn_on_replay_fc refuses for a member and its ring. */
+int idqn_group_learn_on_replay_fc(idqn_group_t group, const idqn_group_ring_t* rings, const int32_t* slots_host, int32_t batch,
+                                  int32_t mean_divisor, uint32_t flags, void* stream);
+/* idqn_learn_steps_on_replay_fc for every member at once: slots_host [S][n_steps][batch]; ONE persistent launch of grid (K, S)
+ * (IDQN_FC_LEARN_STEPS_LOOP=1: n_steps single group launches enqueued inside the call).  Refuses what the single group step
+ * refuses, n_steps outside [1, IDQN_MAX_STEPS_PER_CALL] and any flag.                                                          */
+int idqn_group_learn_steps_on_replay_fc(idqn_group_t group, const idqn_group_ring_t* rings, const int32_t* slots_host,
+                                        int32_t n_steps, int32_t batch, int32_t mean_divisor, uint32_t flags, void* stream);
+/* idqn_act_host_many_fc over the members: state e (float32 rows [n][obs] in PINNED host memory) is evaluated on head
+ * heads_host[e] of member member_host[e] (both ordinary host memory, read before the call returns).  Row e of q_out_dev [n][A]
+ * and actions_host_pinned[e] are, byte for byte, what idqn_act_host gives on that member for (which, heads_host[e], state e).
+ * One launch behind the copy node, one workgroup per state; the per-state parameter base travels in the uploaded block, so one
+ * hipGraph per (n, buffers) serves every assignment.  The group has an acting slot (block, mailbox, counters) of its own; the
+ * members' slots are untouched.  IDQN_E_INVALID before anything is enqueued: a null pointer, n outside [1, 32], which not
+ * 0 / 1, a member outside [0, S), a head outside [0, K).                                                                  */
+int idqn_group_act_host_fc(idqn_group_t group, int32_t which, const int32_t* member_host, const int32_t* heads_host,
+                           const void* states_host_pinned, int32_t n, float* q_out_dev, int32_t* actions_host_pinned, void* stream);
+
 /* Test / debug access to internal activation buffers by name (device pointer + byte size).        */
 int idqn_debug_buffer(idqn_handle_t h, const char* name, void** ptr_dev, int64_t* nbytes);
 /* Mean duration (ms) and launch count of the dominant kernel over the IDQN_F_PROFILE calls since
