@@ -12,7 +12,9 @@ What is restated, and what pins it
   PINNED: checked against the reference's own known-answer tests
   (``tests/test_sum_tree.py``, ``tests/test_samplers.py``,
   ``tests/test_replay_buffer.py``) and against traces captured by importing the
-  reference's ``sum_tree.py`` / ``samplers.py`` in the build container
+  reference's ``sum_tree.py`` / ``samplers.py`` / ``replay_buffer.py`` (the last with
+  ``compress=False`` and dataclass-plumbing stand-ins for its jax / flax / snappy
+  imports) in the build container
   (``oracle/make_golden.py`` -> ``tests/golden/int_path_*.npz``).
 * fp32 path (``qnet_ref``, ``torch_ref``): restatement of
   ``slimdqn/networks/idqn.py:13-24,96-131``, ``slimdqn/networks/dqn.py:60-92`` and

@@ -13,6 +13,9 @@ jax / flax / snappy dependencies (compression is a host-RAM trick with no observ
 * ``add`` (``:202-213``): keys are the running ``add_count``; FIFO eviction once
   ``add_count > max_capacity``;
 * ``sample`` (``:215-230``): keys from the sampler, elements stacked along a new leading axis.
+
+Pinned by ``tests/golden/int_path_replay.npz`` (traces of the reference's own class, ``oracle/make_golden.py --replay``):
+tests/test_replay_pinned_host.py replays them through ``ReplayRef`` -- keys, ``add_count``, elements, draws and batches, exactly.
 """
 import collections
 
