@@ -1,0 +1,44 @@
+// Argument and aliasing checks of idqn_group_per_learn_on_replay_fc (qnet.hip) on the S prioritized-replay records of a call.
+// Plain host C++ without a HIP dependency, as per_step_args.h: NULL when the records are fine, else the refusal text with
+// the member(s) it is about in *g_out (and *j_out: the earlier member that names the same buffer, else -1), so that the
+// entry can refuse before it enqueues, allocates or stages anything.
+#pragma once
+#include "../../include/idqn_hip.h"
+#include "per_step_args.h"
+
+#define PER_GROUP_MAX_N 32  // samples per member: the one-launch step's batch limit (RPS_PAR_SLOTS)
+
+static inline const char* per_group_args_error(const idqn_per_step_t* per, int32_t n_members, int32_t batch, int32_t n_heads, int* g_out,
+                                               int* j_out) {
+    *g_out = -1;
+    *j_out = -1;
+    if (!per) return "null pointer";
+    if (batch < 1 || batch > PER_GROUP_MAX_N) return "batch not in [1, 32]";
+    for (int g = 0; g < n_members; ++g) {
+        const idqn_per_step_t& p = per[g];
+        *g_out = g;
+        if (p.tau_dev) return "tau_dev is set: a group serves MLP members, which take no fractions";
+        const char* bad = per_draw_args_error(p.nodes_dev, p.depth, p.uniforms_host, batch, p.n_items, p.leaves_dev, p.weights_dev);
+        if (!bad) bad = per_write_back_args_error(p.nodes_dev, p.depth, p.leaves_dev, p.td_abs_dev, n_heads, batch, p.tree_scratch_dev);
+        if (bad) return bad;
+    }
+    for (int g = 1; g < n_members; ++g)
+        for (int j = 0; j < g; ++j) {
+            const idqn_per_step_t &a = per[g], &b = per[j];
+            const char* bad = nullptr;
+            if (a.nodes_dev == b.nodes_dev) bad = "two members name the same nodes_dev: one buffer would have two writers";
+            else if (a.leaves_dev == b.leaves_dev) bad = "two members name the same leaves_dev: one buffer would have two writers";
+            else if (a.weights_dev == b.weights_dev) bad = "two members name the same weights_dev: one buffer would have two writers";
+            else if (a.td_abs_dev == b.td_abs_dev) bad = "two members name the same td_abs_dev: one buffer would have two writers";
+            else if (a.tree_scratch_dev == b.tree_scratch_dev) bad = "two members name the same tree_scratch_dev: one buffer would have two writers";
+            else if (a.priorities_dev && a.priorities_dev == b.priorities_dev) bad = "two members name the same priorities_dev: one buffer would have two writers";
+            else if (a.max_priority_dev && a.max_priority_dev == b.max_priority_dev) bad = "two members name the same max_priority_dev: one buffer would have two writers";
+            if (bad) {
+                *g_out = g;
+                *j_out = j;
+                return bad;
+            }
+        }
+    *g_out = -1;
+    return nullptr;
+}

@@ -44,34 +44,14 @@ __global__ __launch_bounds__(256) void k_per_draw(const double* __restrict__ nod
     if (t < n) out[t] = per_norm_weight(w, red[0]);
 }
 
-// val(i) of the write-back's set: the priorities the same workgroup has just left in LDS
-struct StValuesLds {
-    const double* v;
-    __device__ __forceinline__ double operator()(int i) const { return v[i]; }
-};
-
 // One workgroup.  Thread i < n computes priority i (k_per_priorities' arithmetic) into LDS -- and into priorities_out when the
 // caller wants them; the running maximum is the workgroup's maximum (an LDS integer maximum of the bit patterns) followed by ONE
 // atomicMax on max_dev: the maximum of a set of bit patterns does not depend on how it is grouped, so it is the result of
 // k_per_priorities' n atomics.  The body of k_sumtree_set follows with the values read from LDS; m: n rounded up to a power of two.
+// The text is per_write_back_body.h, shared with k_per_group_write_back (per_group_kernels.h: the same body on record g of a table).
 __global__ __launch_bounds__(ST_THREADS) void k_per_write_back(double* __restrict__ nodes, int depth, const int32_t* __restrict__ leaves,
                                                                const float* __restrict__ td_abs, int K, int n, int m, int reduce_max,
                                                                double eps, double alpha, double* __restrict__ priorities_out,
                                                                double* __restrict__ max_dev, double* __restrict__ delta_scratch) {
-    __shared__ unsigned long long key[PER_STEP_MAX_N];
-    __shared__ unsigned int cur[PER_STEP_MAX_N];
-    __shared__ double pri[PER_STEP_MAX_N];
-    __shared__ unsigned long long pmax;
-    const int tid = threadIdx.x;
-    if (tid == 0) pmax = 0ull;
-    __syncthreads();
-    if (tid < n) {
-        const double pr = per_priority(td_abs + tid, K, n, reduce_max, eps, alpha);
-        pri[tid] = pr;
-        if (priorities_out) priorities_out[tid] = pr;
-        atomicMax(&pmax, (unsigned long long)__double_as_longlong(pr));
-    }
-    __syncthreads();
-    if (tid == 0 && max_dev) atomicMax(reinterpret_cast<unsigned long long*>(max_dev), pmax);
-    sumtree_set_body(nodes, depth, leaves, StValuesLds{pri}, n, m, delta_scratch, key, cur);
+#include "per_write_back_body.h"
 }

@@ -34,6 +34,7 @@
 #include "fc_group_kernels.h"
 #include "dp_internal.h"
 #include "per_step_args.h"
+#include "per_group_kernels.h"
 
 namespace {
 
@@ -3614,7 +3615,7 @@ extern "C" int idqn_profile_read(idqn_handle_t h, double* mean_ms, int32_t* n_la
 // stages its slots) and ONE acting slot of its own.
 struct idqn_group_s {
     std::vector<idqn_handle_t> m;
-    size_t block_bytes = 0, slots_off = 0;
+    size_t block_bytes = 0, slots_off = 0, uni_off = 0;
     uint8_t* pin[IDQN_STEPS_STAGING_DEPTH] = {};
     uint8_t* dev[IDQN_STEPS_STAGING_DEPTH] = {};
     hipEvent_t ev[IDQN_STEPS_STAGING_DEPTH] = {};
@@ -3650,7 +3651,9 @@ extern "C" int idqn_group_create(const idqn_handle_t* members, int32_t n_members
     idqn_group_s* G = new idqn_group_s();
     G->m.assign(members, members + n_members);
     G->slots_off = ((size_t)n_members * sizeof(FcGroupMember) + 15) & ~(size_t)15;
-    G->block_bytes = G->slots_off + (size_t)n_members * STEPS_BLOCK_BYTES;
+    // the prioritized call (idqn_group_per_learn_on_replay_fc) puts its tree records and uniforms where the slots go
+    G->uni_off = G->slots_off + (((size_t)n_members * sizeof(PerGroupMember) + 15) & ~(size_t)15);
+    G->block_bytes = std::max(G->slots_off + (size_t)n_members * STEPS_BLOCK_BYTES, G->uni_off + (size_t)n_members * PER_GROUP_MAX_N * 8);
     *out = G;
     return IDQN_OK;
 }
@@ -3691,6 +3694,26 @@ static int group_learn_check(idqn_group_t G, const char* fn, const idqn_group_ri
     return IDQN_OK;
 }
 
+// Record g of the table: what a solo launch on member h and ring r receives as kernel arguments (the ring is the minibatch
+// source, so the batch pointers stay NULL; weights and |TD| too, unless the prioritized call sets them afterwards)
+static void group_fill_member(FcGroupMember& m, idqn_handle_t h, const idqn_group_ring_t& r, bool steps_plan, int32_t batch, int32_t mean_divisor,
+                              bool grads_only, const int32_t* slots_dev) {
+    h->pend_B = 0; h->pend_stage = 0;
+    h->tl_on = false;
+    memset(&m, 0, sizeof(m));
+    FcArgs& a = m.a;
+    a.net = h->fc; a.online = h->online; a.target = h->target; a.grad = h->grad; a.P = h->L.head_stride;
+    a.gamma_n = h->gamma_n; a.B = batch; a.Bdiv = mean_divisor; a.K = h->cfg.n_heads;
+    a.ws = h->fc_ws; a.losses = h->losses; a.q_dbg = h->qdbg;
+    a.count = h->count; a.bcinv = h->bcinv; a.adam_b1 = h->ad.b1; a.adam_b2 = h->ad.b2;
+    a.cum = h->cum; a.finish_step = grads_only ? 0 : 1;
+    a.gm = GradMap{h->gP, h->g_w0_begin, h->g_w0_end, h->g_w0_base};
+    m.plan = steps_plan ? h->fcs_plan_ : h->fcp_plan_;
+    m.ad = h->ad;
+    m.theta = h->online; m.mu = h->mu; m.nu = h->nu;
+    m.src = FcRingSrc<RpsSlotsDev>{(const float*)r.frames_dev, r.rows_dev, r.n_frames, r.frame_bytes / 4, r.stack, RpsSlotsDev{slots_dev}};
+}
+
 // One launch of grid (K, S): block = {FcGroupMember[S], slots [S][n_steps][batch]}, n_steps == 0: the single step k_fc_group_step
 static int group_launch(idqn_group_t G, const idqn_group_ring_t* rings, const int32_t* slots_host, long member_stride, int n_steps, int32_t batch,
                         int32_t mean_divisor, bool grads_only, hipStream_t q) {
@@ -3707,24 +3730,9 @@ static int group_launch(idqn_group_t G, const idqn_group_ring_t* rings, const in
     const int32_t* slots_dev = (const int32_t*)(G->dev[blk] + G->slots_off);
     const long per = (long)ns * batch;
     for (int g = 0; g < S; ++g) {
-        const idqn_handle_t h = G->m[g];
         const idqn_group_ring_t& r = rings[g];
         memcpy(slots_pin + g * per, slots_host + g * member_stride, (size_t)per * 4);
-        h->pend_B = 0; h->pend_stage = 0;
-        h->tl_on = false;
-        FcGroupMember& m = tab[g];
-        memset(&m, 0, sizeof(m));
-        FcArgs& a = m.a;
-        a.net = h->fc; a.online = h->online; a.target = h->target; a.grad = h->grad; a.P = h->L.head_stride;
-        a.gamma_n = h->gamma_n; a.B = batch; a.Bdiv = mean_divisor; a.K = h->cfg.n_heads;  // (the ring is the minibatch source)
-        a.ws = h->fc_ws; a.losses = h->losses; a.q_dbg = h->qdbg;
-        a.count = h->count; a.bcinv = h->bcinv; a.adam_b1 = h->ad.b1; a.adam_b2 = h->ad.b2;
-        a.cum = h->cum; a.finish_step = grads_only ? 0 : 1;
-        a.gm = GradMap{h->gP, h->g_w0_begin, h->g_w0_end, h->g_w0_base};
-        m.plan = n_steps ? h->fcs_plan_ : h->fcp_plan_;
-        m.ad = h->ad;
-        m.theta = h->online; m.mu = h->mu; m.nu = h->nu;
-        m.src = FcRingSrc<RpsSlotsDev>{(const float*)r.frames_dev, r.rows_dev, r.n_frames, r.frame_bytes / 4, r.stack, RpsSlotsDev{slots_dev + g * per}};
+        group_fill_member(tab[g], G->m[g], r, n_steps != 0, batch, mean_divisor, grads_only, slots_dev + g * per);
     }
     const size_t bytes = G->slots_off + (size_t)S * per * 4;
     IDQN_HIP_CHECK(hipMemcpyAsync(G->dev[blk], G->pin[blk], bytes, hipMemcpyHostToDevice, q));
@@ -3743,6 +3751,75 @@ extern "C" int idqn_group_learn_on_replay_fc(idqn_group_t G, const idqn_group_ri
                                              int32_t mean_divisor, uint32_t flags, void* stream) {
     if (const int rc = group_learn_check(G, "idqn_group_learn_on_replay_fc", rings, slots_host, 1, batch, mean_divisor, flags)) return rc;
     return group_launch(G, rings, slots_host, batch, 0, batch, mean_divisor, (flags & IDQN_F_GRADS_ONLY) != 0, (hipStream_t)stream);
+}
+
+// The prioritized step of every member as ONE call (include/idqn_hip.h): block = {FcGroupMember[S], PerGroupMember[S], uniforms
+// [S][batch]} in the group's staging ring -> one copy -> k_per_group_draw (S) -> k_fc_group_step (K, S) on the members' leaves,
+// weights and |TD| (they travel in the table: the members' own h->is_weight / h->td_abs stay unset) -> k_per_group_write_back (S).
+// Every refusal comes before anything is enqueued, allocated or staged.
+static_assert(PER_GROUP_MAX_N == RPS_PAR_SLOTS, "a prioritized group batch is a batch of the one-launch step");
+extern "C" int idqn_group_per_learn_on_replay_fc(idqn_group_t G, const idqn_group_ring_t* rings, const idqn_per_step_t* per, int32_t batch,
+                                                 int32_t mean_divisor, uint32_t flags, void* stream) {
+    const char* fn = "idqn_group_per_learn_on_replay_fc";
+    IDQN_REQUIRE(G && rings && per, "%s: null pointer", fn);
+    IDQN_REQUIRE(batch >= 1 && batch <= PER_GROUP_MAX_N, "%s: batch %d not in [1, %d]: a group runs the one-launch step", fn, batch, PER_GROUP_MAX_N);
+    IDQN_REQUIRE(flags == 0, "%s: takes no flags (got 0x%x): profile or split a member's step alone", fn, flags);
+    const int S = (int)G->m.size(), K = G->m[0]->cfg.n_heads;
+    for (int g = 0; g < S; ++g)
+        IDQN_REQUIRE(!G->m[g]->is_weight && !G->m[g]->td_abs,
+                     "%s: member %d has prioritized-replay buffers set (idqn_set_per_buffers): the call carries the members' weights and |TD| itself", fn, g);
+    int bad_g = -1, bad_j = -1;
+    const char* bad = per_group_args_error(per, S, batch, K, &bad_g, &bad_j);
+    IDQN_REQUIRE(!bad || bad_j < 0, "%s: members %d and %d: %s", fn, bad_j, bad_g, bad ? bad : "");
+    IDQN_REQUIRE(!bad, "%s: member %d: %s (depth %d, batch %d, n_items %ld)", fn, bad_g, bad, bad_g >= 0 ? per[bad_g].depth : 0, batch,
+                 bad_g >= 0 ? (long)per[bad_g].n_items : 0L);
+    for (int g = 0; g < S; ++g) {
+        const idqn_group_ring_t& r = rings[g];
+        long obs_elems;
+        if (const int rc = replay_fc_check(G->m[g], fn, (const uint8_t*)r.frames_dev, r.n_frames, r.frame_bytes, r.rows_dev, nullptr, per[g].leaves_dev, batch,
+                                           r.stack, mean_divisor, flags, &obs_elems))
+            return rc;
+    }
+    hipStream_t q = (hipStream_t)stream;
+    const int blk = G->next;
+    if (!G->pin[blk]) {
+        IDQN_HIP_CHECK(hipHostMalloc((void**)&G->pin[blk], G->block_bytes, hipHostMallocDefault));
+        IDQN_HIP_CHECK(hipMalloc((void**)&G->dev[blk], G->block_bytes));
+        IDQN_HIP_CHECK(hipEventCreateWithFlags(&G->ev[blk], hipEventDisableTiming));
+    }
+    if (G->busy[blk]) IDQN_HIP_CHECK(hipEventSynchronize(G->ev[blk]));  // the launches that read this block are done
+    G->busy[blk] = false;
+    FcGroupMember* tab = (FcGroupMember*)G->pin[blk];
+    PerGroupMember* ptab = (PerGroupMember*)(G->pin[blk] + G->slots_off);
+    double* uni_pin = (double*)(G->pin[blk] + G->uni_off);
+    const double* uni_dev = (const double*)(G->dev[blk] + G->uni_off);
+    for (int g = 0; g < S; ++g) {
+        const idqn_per_step_t& p = per[g];
+        memcpy(uni_pin + (size_t)g * batch, p.uniforms_host, (size_t)batch * 8);
+        group_fill_member(tab[g], G->m[g], rings[g], false, batch, mean_divisor, false, p.leaves_dev);
+        tab[g].a.is_weight = p.weights_dev;
+        tab[g].a.td_abs = p.td_abs_dev;
+        PerGroupMember& m = ptab[g];
+        memset(&m, 0, sizeof(m));
+        m.nodes = p.nodes_dev; m.uniforms = uni_dev + (size_t)g * batch; m.leaves = p.leaves_dev; m.weights = p.weights_dev;
+        m.td_abs = p.td_abs_dev; m.priorities = p.priorities_dev; m.max_dev = p.max_priority_dev; m.scratch = (double*)p.tree_scratch_dev;
+        m.n_items = (double)p.n_items; m.beta = p.beta; m.eps = p.eps; m.alpha = p.alpha;
+        m.depth = p.depth; m.stratified = p.stratified; m.reduce_max = p.reduce_max; m.K = K;
+    }
+    IDQN_HIP_CHECK(hipMemcpyAsync(G->dev[blk], G->pin[blk], G->uni_off + (size_t)S * batch * 8, hipMemcpyHostToDevice, q));
+    G->next = (blk + 1) % IDQN_STEPS_STAGING_DEPTH;
+    const idqn_handle_t h0 = G->m[0];
+    const PerGroupMember* ptab_dev = (const PerGroupMember*)(G->dev[blk] + G->slots_off);
+    int m2 = 1;
+    while (m2 < batch) m2 <<= 1;
+    hipLaunchKernelGGL(k_per_group_draw, dim3((unsigned)S), dim3(PER_GROUP_DRAW_T), 0, q, ptab_dev, (int)batch);
+    hipLaunchKernelGGL(k_fc_group_step, dim3((unsigned)K, (unsigned)S), dim3(FCM_T), (size_t)h0->fcp_plan_.floats * 4, q,
+                       (const FcGroupMember*)G->dev[blk], 1);
+    hipLaunchKernelGGL(k_per_group_write_back, dim3((unsigned)S), dim3(ST_THREADS), 0, q, ptab_dev, (int)batch, m2);
+    IDQN_HIP_CHECK(hipGetLastError());
+    IDQN_HIP_CHECK(hipEventRecord(G->ev[blk], q));
+    G->busy[blk] = true;
+    return IDQN_OK;
 }
 
 // n_steps steps of every member: ONE launch of k_fc_group_steps (what the members' own idqn_learn_steps_on_replay_fc would run

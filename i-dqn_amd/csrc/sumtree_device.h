@@ -231,3 +231,9 @@ struct StValuesGlobal {
     const double* __restrict__ v;
     __device__ __forceinline__ double operator()(int i) const { return v[i]; }
 };
+
+// val(i) of the write-back's set (per_write_back_body.h): the priorities the same workgroup has just left in LDS
+struct StValuesLds {
+    const double* v;
+    __device__ __forceinline__ double operator()(int i) const { return v[i]; }
+};

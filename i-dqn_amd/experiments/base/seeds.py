@@ -28,12 +28,16 @@ class _Seed:
 
 
 class SeedTrainer:
-    def __init__(self, keys, p, agents, envs, replay_buffers, save_fn=None, group=None):
+    def __init__(self, keys, p, agents, envs, replay_buffers, save_fn=None, group=None, learner=None):
+        """``learner``: a ``slimdqn.sample_collection.per.PrioritizedGroupLearner`` over the same agents and buffers -- the
+        gradient step of a step at which every seed learns is then ``learner.step()`` (one prioritized group call) in place
+        of ``group.update_online_params``; where only some seeds learn, their own ``learner.learners[i].step()``.  None: every
+        line behaves as without the argument."""
         ps = list(p) if isinstance(p, (list, tuple)) else [p] * len(agents)
         assert len(keys) == len(ps) == len(agents) == len(envs) == len(replay_buffers)
         self.seeds = [_Seed(*t) for t in zip(keys, ps, agents, envs, replay_buffers)]
         self.group = group if group is not None else AgentGroup(agents)
-        self.save_fn, self.total_steps = save_fn, 0
+        self.learner, self.save_fn, self.total_steps = learner, save_fn, 0
 
     def _select_actions(self, live):
         """``select_action`` of every live seed on its own key; the greedy ones share one acting call."""
@@ -74,17 +78,33 @@ class SeedTrainer:
         if not learners:
             return
         if len(learners) == len(self.seeds):
-            self.group.update_online_params(self.total_steps, [s.rb for s in self.seeds])
+            if self.learner is not None:
+                self._prioritized_steps(learners)
+            else:
+                self.group.update_online_params(self.total_steps, [s.rb for s in self.seeds])
             results = self.group.update_target_params(self.total_steps)
         else:
             results = []
             for i in learners:
                 s = self.seeds[i]
-                s.agent.update_online_params(self.total_steps, s.rb)
+                if self.learner is not None:
+                    self._prioritized_steps([i])
+                else:
+                    s.agent.update_online_params(self.total_steps, s.rb)
                 results.append(s.agent.update_target_params(self.total_steps))
         for i, (updated, logs) in zip(learners, results):
             if updated:
                 self.seeds[i].p["wandb"].log({"n_training_steps": self.total_steps, **logs})
+
+    def _prioritized_steps(self, learners):
+        """``update_online_params`` of seeds ``learners`` through the prioritized learner: a gradient step where
+        ``total_steps % update_to_data == 0`` (``idqn.py:65-66``) -- one group call when that holds for every seed."""
+        due = [i for i in learners if self.total_steps % getattr(self.seeds[i].agent, "update_to_data", 1) == 0]
+        if len(due) == len(self.seeds):
+            self.learner.step()
+        else:
+            for i in due:
+                self.learner.learners[i].step()
 
     def _end_epoch(self, s):
         if hasattr(s.rb, "flush_deferred"):
@@ -127,6 +147,6 @@ class SeedTrainer:
         return [([e.returns for e in s.history], [e.lengths for e in s.history]) for s in self.seeds]
 
 
-def train_seeds(keys, p, agents, envs, replay_buffers, save_fn=None):
+def train_seeds(keys, p, agents, envs, replay_buffers, save_fn=None, learner=None):
     """``experiments.base.dqn.train`` for S seeds in one process; returns ``(returns, lengths)`` per epoch, per seed."""
-    return SeedTrainer(keys, p, agents, envs, replay_buffers, save_fn).run()
+    return SeedTrainer(keys, p, agents, envs, replay_buffers, save_fn, learner=learner).run()

@@ -5,6 +5,10 @@ workgroup per head, so S agents are a grid of (K, S) workgroups (``csrc/fc_group
 moments, counters and losses after a group call are, byte for byte, what the member's own call leaves.  The members keep
 their arenas, handles and hyper-parameters; a member may be driven alone between two group calls.
 
+Prioritized samplers: ``AgentGroup`` itself steps such members through their own calls; their one-call group step is
+``slimdqn.sample_collection.per.PrioritizedGroupLearner`` (``idqn_group_per_learn_on_replay_fc``), which takes this group's
+C object (``_ensure_group``), its ring records (``_rings``) and its ``_stock`` rule.
+
 Every member's buffer draws its own keys with the host protocol of ``DeviceAgent._sample_and_learn`` -- the sampler stream
 of a member is what it would be alone -- and the drawn slots travel in one block.  Where the group entry refuses (agents
 that are not MLPs, batches of more than 32 samples, prioritized samplers, ...) the members' own methods run on the slots

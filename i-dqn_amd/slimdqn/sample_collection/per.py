@@ -21,6 +21,8 @@ Design (Schaul et al. 2016, proportional variant), all on the GPU, no host synch
   general-shape cnn agents) skip it the same way through ``idqn_learn_on_replay_fc_dev``.
 * Where the agent's replay-sourced conditions hold, the whole chain is ONE C call, ``idqn_per_learn_on_replay`` (two fused
   kernels around the replay-sourced step), byte-identical to the chain; ``fuse_per_step`` / ``fuse_per_family`` below.
+* ``PrioritizedGroupLearner``: the prioritized step of the S MLP agents of an ``AgentGroup`` as ONE C call,
+  ``idqn_group_per_learn_on_replay_fc`` (three launches for all members), byte-identical per member to the member's own step.
 """
 import ctypes as C
 import os
@@ -189,10 +191,16 @@ class PrioritizedLearner:
 
     def step(self):
         """One prioritized gradient step; returns the per-head losses (device tensor, not synchronised)."""
-        rb, agent = self.rb, self.agent
+        rb = self.rb
         B = rb._batch_size
         assert rb.add_count, "No samples in replay buffer!"
-        u = self.sampler._rng_key.random(B)  # the one draw from the sampler's generator, whichever route runs
+        return self.step_with_uniforms(self.sampler._rng_key.random(B))  # the one draw from the sampler's generator, whichever route runs
+
+    def step_with_uniforms(self, u):
+        """``step()`` on uniforms ``u`` (float64 [B] in [0, 1)) that the caller has drawn from the sampler's generator already --
+        what ``PrioritizedGroupLearner`` runs per member where the group call does not serve."""
+        rb, agent = self.rb, self.agent
+        B = rb._batch_size
         route, taus = self._fused_route(), None
         if route is not None:
             view, family = route
@@ -261,3 +269,87 @@ class PrioritizedLearner:
         _hip.check(lib.sumtree_set(_hip.ptr(tree._nodes_dev), tree._depth, _hip.ptr(self._leaves),
                                    _hip.ptr(self._priorities), B, _hip.ptr(tree._scratch), q), "sumtree_set")
         return losses
+
+
+class PrioritizedGroupLearner:
+    """``PrioritizedLearner.step`` for every member of an ``AgentGroup`` at once: one ``idqn_group_per_learn_on_replay_fc`` call
+    (S draws and weights, the group step on the leaves, S write-backs: three launches) leaves on every member, its tree and
+    its learner's buffers the bytes the member's own ``PrioritizedLearner.step`` leaves.
+
+    It owns one ``PrioritizedLearner`` per member: they supply the buffers and the fallback.  ``step()`` draws every member's
+    uniforms from the member's own sampler generator, once per member, in member order, whichever route runs -- a member's
+    sampler stream is what it would be alone.  The group call is taken when the group is stock (``AgentGroup._stock``), every
+    member's ring serves the replay-sourced MLP step, B <= 32, the group's size is in ``group_per_sizes`` and
+    ``IDQN_PER_FUSED`` is not 0; otherwise every member's own learner steps on the uniforms already drawn.
+    ``_group_per_ok`` (unset: not tried; False: the entry refused these members the first time -- text in
+    ``group_per_refusal`` -- the members' own steps from then on; True: it served)."""
+
+    # The sizes S at which the group call is taken by default: those where its median lay below the minimum of the S solo
+    # steps (tools/bench_group_per.py -> profiles/group_per.json), the rule of ``AgentGroup.group_sizes``.  LunarLander net,
+    # B = 32, us per step of all members: S = 1 50.7 against 48.1 (SLOWER: a group of one runs its member's own step),
+    # S = 2 52.7 against 95.6, 4 52.5 against 191.5, 8 67.2 against 384.7, 16 115.0 against 779.1, 32 207.2 against 1562.1.
+    group_per_sizes = frozenset(range(2, 33))
+
+    def __init__(self, group, replay_buffers, beta: float = 0.4, eps: float = 1e-6, reduce: str = "mean", stratified: bool = True):
+        rbs = list(replay_buffers)
+        assert len(rbs) == len(group.agents)
+        per_member = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * len(rbs)  # noqa: E731
+        self.group, self.rbs = group, rbs
+        self.learners = [PrioritizedLearner(a, rb, beta=b, eps=e, reduce=r, stratified=s) for a, rb, b, e, r, s in
+                         zip(group.agents, rbs, per_member(beta), per_member(eps), per_member(reduce), per_member(stratified))]
+
+    def _group_route(self):
+        """The members' ring views when this step goes through the group call, else None; read on every call."""
+        group = self.group
+        if os.environ.get("IDQN_PER_FUSED", "1") == "0" or self.__dict__.get("_group_per_ok") is False:
+            return None
+        if len(group.agents) not in self.group_per_sizes or not group._stock():
+            return None
+        if len({rb._batch_size for rb in self.rbs}) != 1 or self.rbs[0]._batch_size > 32:
+            return None
+        if not all(a._replay_fc_route(rb) for a, rb in zip(group.agents, self.rbs)):
+            return None
+        views = [rb.ring_view() for rb in self.rbs]
+        return views if all(a._ring_fc_fusable(v) for a, v in zip(group.agents, views)) else None
+
+    def _step_group(self, views, us):
+        """The library's code for the group call on ring ``views`` with uniforms ``us`` ([S] float64 arrays of [B], host), or
+        None when ``idqn_group_create`` refused the members."""
+        B = self.rbs[0]._batch_size
+        g = self.group._ensure_group(B)
+        if g is None:
+            return None
+        per = self.__dict__.get("_per_args")
+        if per is None:
+            per = self._per_args = (_hip.PerStep * len(self.learners))()
+        vp = lambda t: None if t is None else int(t.data_ptr())  # noqa: E731
+        for p, lr, u in zip(per, self.learners, us):
+            tree = lr.sampler._sum_tree
+            p.nodes_dev, p.depth, p.n_items = vp(tree._nodes_dev), tree._depth, len(lr.sampler)
+            p.uniforms_host = u.ctypes.data
+            p.stratified, p.reduce_max, p.beta, p.eps, p.alpha = lr.stratified, lr.reduce_max, lr.beta, lr.eps, lr.sampler._alpha
+            p.max_priority_dev = vp(lr.sampler._max_priority_dev)
+            p.leaves_dev, p.weights_dev, p.td_abs_dev = vp(lr._leaves), vp(lr._weights), vp(lr._td_abs)
+            p.priorities_dev, p.tree_scratch_dev, p.tau_dev = vp(lr._priorities), vp(tree._scratch), None
+        return _hip.lib().idqn_group_per_learn_on_replay_fc(g, self.group._rings(views), per, B, B, 0, _hip.current_stream())
+
+    def step(self):
+        """One prioritized gradient step of every member; returns the members' per-head losses (device tensors, not
+        synchronised)."""
+        for rb in self.rbs:
+            assert rb.add_count, "No samples in replay buffer!"
+        us = [np.ascontiguousarray(lr.sampler._rng_key.random(lr.rb._batch_size)) for lr in self.learners]  # member order
+        views = self._group_route()
+        if views is not None:
+            rc = self._step_group(views, us)
+            if rc is None or (rc == _hip.E_INVALID and self.__dict__.get("_group_per_ok") is None):
+                self._group_per_ok = False  # not these members: their own steps from now on -- same uniforms for this step
+                self.group_per_refusal = "idqn_group_create refused the members" if rc is None else \
+                    _hip.lib().idqn_last_error().decode(errors="replace")
+            else:
+                _hip.check(rc, "idqn_group_per_learn_on_replay_fc")
+                self._group_per_ok = True
+                for a in self.group.agents:
+                    a._replay_fc_ok = True
+                return [a._losses for a in self.group.agents]
+        return [lr.step_with_uniforms(u) for lr, u in zip(self.learners, us)]

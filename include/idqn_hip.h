@@ -393,6 +393,27 @@ int idqn_group_learn_on_replay_fc(idqn_group_t group, const idqn_group_ring_t* r
  * refuses, n_steps outside [1, IDQN_MAX_STEPS_PER_CALL] and any flag.                                                          */
 int idqn_group_learn_steps_on_replay_fc(idqn_group_t group, const idqn_group_ring_t* rings, const int32_t* slots_host,
                                         int32_t n_steps, int32_t batch, int32_t mean_divisor, uint32_t flags, void* stream);
+/* idqn_per_learn_on_replay for every member at once: the prioritized step of S MLP agents.  per[g] is member g's
+ * idqn_per_step_t (declared with idqn_per_learn_on_replay below): its own tree (depth, n_items -- members with different
+ * replay capacities are served), beta, eps, alpha, reduce_max, stratified and buffers; uniforms_host float64 [batch] in
+ * ordinary host memory, read before the call returns; tau_dev NULL.  The S member records with the members' weights / |TD|
+ * pointers, the S tree records and the S x batch uniforms travel in ONE pinned block of the group's staging ring (the event
+ * guard of the other learner entries): one asynchronous copy, then THREE launches -- k_per_group_draw (grid S: the draws and
+ * weights of every member), k_fc_group_step (grid (K, S), slots = member g's leaves_dev) and k_per_group_write_back (grid S)
+ * (csrc/per_group_kernels.h).  No host synchronisation, no allocation after the first call, no per-member launch; the
+ * members' own prioritized-replay pointers (idqn_set_per_buffers) stay unset throughout.
+ * CONTRACT: for every member, online parameters, moments, count, losses, cum_losses, tree nodes, max_priority_dev, leaves,
+ * weights, |TD| and priorities after the call equal, byte for byte, what idqn_per_learn_on_replay leaves on that member
+ * alone for the same uniforms on the same stream.
+ * Refuses (IDQN_E_INVALID with idqn_last_error, nothing enqueued, allocated or staged, nothing changed): a NULL pointer other
+ * than max_priority_dev / priorities_dev; batch outside [1, 32]; any flag; a non-NULL tau_dev; depth outside [1, 31];
+ * n_items < 1; a member with idqn_set_per_buffers set; everything per_draw, per_write_back and idqn_learn_on_replay_fc_dev
+ * refuse for a member; two members naming the same nodes_dev, leaves_dev, weights_dev, td_abs_dev, tree_scratch_dev or non-NULL
+ * priorities_dev / max_priority_dev (one buffer would have two writers).                                                      */
+struct idqn_per_step;
+int idqn_group_per_learn_on_replay_fc(idqn_group_t group, const idqn_group_ring_t* rings /*[S]*/,
+                                      const struct idqn_per_step* per /*[S]*/, int32_t batch, int32_t mean_divisor,
+                                      uint32_t flags, void* stream);
 /* idqn_act_host_many_fc over the members: state e (float32 rows [n][obs] in PINNED host memory) is evaluated on head
  * heads_host[e] of member member_host[e] (both ordinary host memory, read before the call returns).  Row e of q_out_dev [n][A]
  * and actions_host_pinned[e] are, byte for byte, what idqn_act_host gives on that member for (which, heads_host[e], state e).
