@@ -221,6 +221,8 @@ extern "C" int replay_ring_regrow(const void* old_ring_dev, int64_t old_n, void*
 #define REPLAY_STEP_MAX_IN 32
 #define REPLAY_STEP_MAX_WRITES 64
 #define REPLAY_STEP_MAX_ROWS 128
+#define REPLAY_GROUP_MAX_ROWS 32  // replay_group_add_step (replay_group_kernels.h): rows per MEMBER and call -- a lock-step add makes
+                                  // one row, an episode end update_horizon of them; a member with more sends them itself first
 #define REPLAY_STEP_HEADER_BYTES ((2 * REPLAY_STEP_MAX_WRITES + REPLAY_STEP_MAX_ROWS + 8 * REPLAY_STEP_MAX_ROWS) * 4)
 
 __global__ __launch_bounds__(256) void k_replay_add_step(const uint8_t* __restrict__ block, uint8_t* __restrict__ ring,
@@ -290,6 +292,61 @@ extern "C" int replay_add_step(void* frame_ring_dev, int64_t n_frames, int64_t f
     hipLaunchKernelGGL(k_replay_add_step, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)block_staging_dev,
                        (uint8_t*)frame_ring_dev, (long)n_frames, (long)frame_bytes, rows_dev, (long)capacity, n_in, n_writes, n_rows,
                        chunks);
+    IDQN_HIP_CHECK(hipGetLastError());
+    return IDQN_OK;
+}
+
+// The S replay adds of a lock-step iteration of a seed group as one call (include/idqn_hip.h, replay_group_add_step).
+#include "replay_group_kernels.h"
+
+extern "C" int replay_group_add_step(int32_t n_members, const replay_group_member_t* members, void* block_host_pinned,
+                                     void* block_staging_dev, int64_t block_bytes, void* stream) {
+    IDQN_REQUIRE(members && block_host_pinned && block_staging_dev, "replay_group_add_step: null pointer");
+    IDQN_REQUIRE(n_members >= 1 && n_members <= REPLAY_GROUP_MAX_MEMBERS, "replay_group_add_step: %d members outside [1, %d]", n_members,
+                 REPLAY_GROUP_MAX_MEMBERS);
+    IDQN_REQUIRE(((uintptr_t)block_host_pinned & 15) == 0 && ((uintptr_t)block_staging_dev & 15) == 0,
+                 "replay_group_add_step: the blocks must be 16-byte aligned");
+    const int64_t head = (int64_t)n_members * (int64_t)sizeof(replay_group_member_t);
+    IDQN_REQUIRE(block_bytes >= head && block_bytes <= ((int64_t)1 << 31), "replay_group_add_step: block_bytes = %ld below the %ld bytes of the records",
+                 (long)block_bytes, (long)head);
+    const uint8_t* block = (const uint8_t*)block_host_pinned;
+    int width = 0;
+    for (int g = 0; g < n_members; ++g) {
+        const replay_group_member_t& m = members[g];
+        IDQN_REQUIRE(m.ring_dev && m.rows_dev && ((uintptr_t)m.rows_dev & 3) == 0, "replay_group_add_step: member %d: null ring or rows, or rows not 4-byte aligned", g);
+        IDQN_REQUIRE(m.n_frames >= 1 && m.frame_bytes >= 1 && m.capacity >= 1 && m.n_rows >= 0 && m.n_rows <= REPLAY_GROUP_MAX_ROWS,
+                     "replay_group_add_step: member %d: n_frames = %ld, frame_bytes = %ld, capacity = %ld, n_rows = %d (<= %d)", g,
+                     (long)m.n_frames, (long)m.frame_bytes, (long)m.capacity, m.n_rows, REPLAY_GROUP_MAX_ROWS);
+        IDQN_REQUIRE(m.frame_slot == -1 || (m.frame_slot >= 0 && m.frame_slot < m.n_frames),
+                     "replay_group_add_step: member %d: frame slot %d outside [0, %ld) (-1: no frame)", g, m.frame_slot, (long)m.n_frames);
+        if (m.frame_slot >= 0)
+            IDQN_REQUIRE((m.frame_offset & 15) == 0 && m.frame_offset >= head && m.frame_bytes <= block_bytes &&
+                             m.frame_offset <= block_bytes - m.frame_bytes,
+                         "replay_group_add_step: member %d: frame at byte %ld (16-byte aligned, behind the records) leaves the block of %ld", g,
+                         (long)m.frame_offset, (long)block_bytes);
+        if (m.n_rows) {
+            IDQN_REQUIRE((m.rows_offset & 3) == 0 && m.rows_offset >= head && m.rows_offset <= block_bytes - (int64_t)m.n_rows * 36,
+                         "replay_group_add_step: member %d: row table at byte %ld (4-byte aligned, behind the records) leaves the block of %ld", g,
+                         (long)m.rows_offset, (long)block_bytes);
+            const int32_t* slots = (const int32_t*)(block + m.rows_offset);
+            for (int r = 0; r < m.n_rows; ++r) {
+                IDQN_REQUIRE(slots[r] >= 0 && slots[r] < m.capacity, "replay_group_add_step: member %d: row %d goes to slot %d outside capacity = %ld",
+                             g, r, slots[r], (long)m.capacity);
+                for (int v = 0; v < r; ++v)
+                    IDQN_REQUIRE(slots[v] != slots[r], "replay_group_add_step: member %d: element slot %d is written twice", g, slots[r]);
+            }
+        }
+        for (int v = 0; v < g; ++v)
+            IDQN_REQUIRE(members[v].ring_dev != m.ring_dev && (void*)members[v].rows_dev != (void*)m.rows_dev &&
+                             members[v].ring_dev != (void*)m.rows_dev && (void*)members[v].rows_dev != m.ring_dev,
+                         "replay_group_add_step: members %d and %d name the same ring or the same rows", v, g);
+        width = std::max(width, (m.frame_slot >= 0 ? replay_group_chunks((long)m.frame_bytes) : 0) + (int)cdiv((long)m.n_rows * 8, 256));
+    }
+    memmove(block_host_pinned, members, (size_t)head);  // the records travel at the head of the block
+    IDQN_HIP_CHECK(hipMemcpyAsync(block_staging_dev, block_host_pinned, (size_t)block_bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
+    if (width == 0) return IDQN_OK;  // (no member had a frame or a row)
+    hipLaunchKernelGGL(k_replay_group_add_step, dim3(width, n_members), dim3(256), 0, (hipStream_t)stream,
+                       (const uint8_t*)block_staging_dev, (long)block_bytes);
     IDQN_HIP_CHECK(hipGetLastError());
     return IDQN_OK;
 }

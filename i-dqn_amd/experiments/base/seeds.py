@@ -12,6 +12,7 @@ import numpy as np
 from experiments.base.dqn import EpochStats
 from slimdqn import prng
 from slimdqn.networks.group import AgentGroup
+from slimdqn.sample_collection.group_replay import GroupCollector
 from slimdqn.sample_collection.replay_buffer import TransitionElement
 from slimdqn.sample_collection.utils import linear_schedule
 
@@ -28,16 +29,18 @@ class _Seed:
 
 
 class SeedTrainer:
-    def __init__(self, keys, p, agents, envs, replay_buffers, save_fn=None, group=None, learner=None):
+    def __init__(self, keys, p, agents, envs, replay_buffers, save_fn=None, group=None, learner=None, collector=None):
         """``learner``: a ``slimdqn.sample_collection.per.PrioritizedGroupLearner`` over the same agents and buffers -- the
         gradient step of a step at which every seed learns is then ``learner.step()`` (one prioritized group call) in place
         of ``group.update_online_params``; where only some seeds learn, their own ``learner.learners[i].step()``.  None: every
-        line behaves as without the argument."""
+        line behaves as without the argument.  ``collector``: a ``slimdqn.sample_collection.group_replay.GroupCollector`` over the
+        same buffers (default: one with the measured default sizes) -- the replay adds of an iteration are its ``add_many``."""
         ps = list(p) if isinstance(p, (list, tuple)) else [p] * len(agents)
         assert len(keys) == len(ps) == len(agents) == len(envs) == len(replay_buffers)
         self.seeds = [_Seed(*t) for t in zip(keys, ps, agents, envs, replay_buffers)]
         self.group = group if group is not None else AgentGroup(agents)
         self.learner, self.save_fn, self.total_steps = learner, save_fn, 0
+        self.collector = collector if collector is not None else GroupCollector(replay_buffers)
 
     def _select_actions(self, live):
         """``select_action`` of every live seed on its own key; the greedy ones share one acting call."""
@@ -61,16 +64,19 @@ class SeedTrainer:
     def _environment_steps(self, live):
         observations = {i: self.seeds[i].env.observation for i in live}  # the frame BEFORE the action goes with it
         actions = self._select_actions(live)
-        out = {}
+        out, transitions = {}, []
         for i in live:
             s = self.seeds[i]
             reward, absorbing = s.env.step(actions[i])
             ended = bool(absorbing) or s.env.n_steps >= s.p["horizon"]
             stored = s.rb._clipping(reward) if s.rb._clipping is not None else reward
-            s.rb.add(TransitionElement(observations[i], actions[i], stored, absorbing, ended))
+            transitions.append(TransitionElement(observations[i], actions[i], stored, absorbing, ended))
             if ended:
                 s.env.reset()
             out[i] = (reward, ended)
+        # the adds of all live seeds in one go (one call where the collector takes that route, else every buffer's own add);
+        # `observations` are the environments' own copies of the frames before the step, which a reset does not touch
+        self.collector.add_many(transitions, live)
         return out
 
     def _gradient_steps(self, live):

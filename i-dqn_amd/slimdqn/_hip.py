@@ -21,6 +21,8 @@ MAX_STEPS_PER_CALL, STEPS_STAGING_DEPTH = 32, 4  # include/idqn_hip.h: idqn_lear
 # csrc/replay.hip, replay_add_step: frames in / ring writes / rows per call, and the byte offset of the frames in its block
 REPLAY_STEP_MAX_IN, REPLAY_STEP_MAX_WRITES, REPLAY_STEP_MAX_ROWS = 32, 64, 128
 REPLAY_STEP_HEADER_BYTES = 4 * (2 * REPLAY_STEP_MAX_WRITES + REPLAY_STEP_MAX_ROWS + 8 * REPLAY_STEP_MAX_ROWS)
+# csrc/replay_group_kernels.h, replay_group_add_step: members per call, rows per member and call
+REPLAY_GROUP_MAX_MEMBERS, REPLAY_GROUP_MAX_ROWS = 32, 32
 
 
 class HipExtensionError(RuntimeError):
@@ -61,6 +63,13 @@ class GroupRing(C.Structure):
     """idqn_group_ring_t: one member's replay frame ring, as ``idqn_learn_on_replay_fc`` takes it."""
     _fields_ = [("frames_dev", C.c_void_p), ("n_frames", C.c_int64), ("frame_bytes", C.c_int64), ("rows_dev", C.c_void_p),
                 ("stack", C.c_int32), ("reserved", C.c_int32)]
+
+
+class GroupAddMember(C.Structure):
+    """replay_group_member_t: one member's record of ``replay_group_add_step`` (64 bytes)."""
+    _fields_ = [("ring_dev", C.c_void_p), ("rows_dev", C.c_void_p), ("n_frames", C.c_int64), ("frame_bytes", C.c_int64),
+                ("capacity", C.c_int64), ("frame_offset", C.c_int64), ("frame_slot", C.c_int32), ("n_rows", C.c_int32),
+                ("rows_offset", C.c_int64)]
 
 
 # every exported symbol of include/idqn_hip.h: (restype, argtypes)
@@ -144,6 +153,7 @@ SYMBOLS = {
     "replay_gather": (C.c_int, [_P, C.c_int64, _P, C.c_int32, _P, _P, _P]),
     "replay_add_frame": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P]),
     "replay_add_step": (C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "replay_group_add_step": (C.c_int, [C.c_int32, _P, _P, _P, C.c_int64, _P]),
     "replay_ring_regrow": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P]),
     "replay_gather_scalars": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, _P, _P, _P]),
 }

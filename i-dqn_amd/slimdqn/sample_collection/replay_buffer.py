@@ -262,10 +262,8 @@ class ReplayBuffer:
         self._frames, self._n_frames = new, new_n
         self._flushed = max(0, self.add_count - self._max_capacity)  # every alive row goes to the device again
 
-    def _upload_frame(self, observation) -> int:
-        """The newest frame goes to ring slot ``t % n_frames`` (async copy from a pinned staging slot); returns t."""
-        import torch
-
+    def _prepare_frame(self, observation):
+        """The host half of ``_upload_frame``: allocation at the first frame, the ring-growth check; returns (frame, t)."""
         frame = np.ascontiguousarray(observation)
         if self._frames is None:
             self._allocate(frame)
@@ -276,6 +274,13 @@ class ReplayBuffer:
             oldest_needed = int(self._first_frame[oldest_key % self._max_capacity])
             if t - oldest_needed >= self._n_frames:  # the slot still holds a frame an alive element needs
                 self._grow_ring(oldest_needed)
+        return frame, t
+
+    def _upload_frame(self, observation) -> int:
+        """The newest frame goes to ring slot ``t % n_frames`` (async copy from a pinned staging slot); returns t."""
+        import torch
+
+        frame, t = self._prepare_frame(observation)
         # one C call (hipMemcpyAsync) per frame; the staging ring is guarded by ONE event per half: before the first slot
         # of a half is rewritten, the copies of that half's previous round (issued >= STAGING / 2 frames ago) have passed
         from slimdqn import _hip
@@ -360,7 +365,28 @@ class ReplayBuffer:
     def add(self, transition: TransitionElement, **kwargs: Any) -> None:
         if getattr(self, "_deferred", None) is not None:
             self.flush_deferred()
-        t_now = self._upload_frame(transition.observation)
+        self._add_elements(transition, self._upload_frame(transition.observation), **kwargs)
+
+    def _add_host(self, transition: TransitionElement, **kwargs: Any):
+        """``add`` without its device copy (``slimdqn.sample_collection.group_replay.GroupCollector`` sends the frames of S
+        buffers in one call): every host effect of ``add``, in ``add``'s order; returns ``(frame bytes, ring slot)`` -- the
+        frame is the caller's to put into slot ``ring slot`` of ``_frames`` before anything reads the ring."""
+        if getattr(self, "_deferred", None) is not None:
+            self.flush_deferred()
+        frame, t = self._prepare_frame(transition.observation)
+        i, half = t % self.STAGING, self.STAGING // 2
+        if i % half == half - 1:  # slot i of the staging ring stays unused; the half's guard still has to stand behind the
+            import torch          # copies that solo adds issued from its other slots
+
+            ev = torch.cuda.Event()
+            ev.record()
+            self._pin_events[i // half] = ev
+        self._t = t + 1
+        self._add_elements(transition, t, **kwargs)
+        return frame.view(np.uint8).reshape(-1), t % self._n_frames
+
+    def _add_elements(self, transition: TransitionElement, t_now: int, **kwargs: Any) -> None:
+        """The elements that the transition at index ``t_now`` completes: rows, sampler keys, FIFO eviction (``:202-213``)."""
         light = transition._replace(observation=None)  # the window decides positions; pixels stay on the device
         for plan, window_size in self._accumulator.plan(light):
             key = ReplayItemID(self.add_count)

@@ -607,6 +607,34 @@ int replay_add_frame(void* frame_ring_dev, int64_t slot, int64_t frame_bytes, co
 int replay_add_step(void* frame_ring_dev, int64_t n_frames, int64_t frame_bytes, int32_t* rows_dev, int64_t capacity,
                     const void* block_host_pinned, void* block_staging_dev, int32_t n_in, int32_t n_writes, int32_t n_rows,
                     void* stream);
+/* One lock-step collection of a SEED GROUP (no reference counterpart: the reference starts one process per seed): S SEPARATE
+ * ReplayBuffers -- own rings, capacities and row tables, which may differ in frame_bytes, n_frames and capacity -- each take at
+ * most one new frame and their pending element rows.  This call replaces the S replay_add_frame calls of the frames and the S to
+ * 2 S of the row uploads: the caller fills ONE PINNED block, the call copies `members` to its head, copies block_bytes of it
+ * asynchronously into block_staging_dev (caller-owned, at least as large) and ONE launch, grid (work items, S), writes every
+ * frame to its ring slot and every row to its table.  Block layout, both sides:
+ *   replay_group_member_t [n_members]  from byte 0 (written by the call)
+ *   per member, behind the records:    int32 [n_rows] destination element slots + int32 [n_rows][8] the rows, at rows_offset
+ *                                      (a multiple of 4; replay_gather_stacked documents the row), n_rows <= 32 (the row cap: a
+ *                                      member with more sends them itself first);
+ *                                      uint8 [frame_bytes] its new frame at frame_offset (a multiple of 16), if frame_slot >= 0
+ * Frames move 16 B per lane when the member's frame_bytes % 16 == 0 and its source and destination are 16-byte aligned, else 4 B,
+ * else bytes.  It needs no agent handle and no idqn_group_* object.  IDQN_E_INVALID before anything is enqueued (and before the
+ * block is written): a null pointer, n_members outside [1, 32], a block that is not 16-byte aligned, a frame or a row table that
+ * is misaligned or leaves [64 * n_members, block_bytes), a frame slot outside [0, n_frames) other than -1, more than 32 rows, an
+ * element slot outside [0, capacity) or named twice within a member, two members naming the same ring or the same row table.
+ * The pinned block and the staging block may be refilled once the stream has passed this call.                                */
+typedef struct replay_group_member_t {
+    void* ring_dev;       /* [n_frames][frame_bytes] */
+    int32_t* rows_dev;    /* [capacity][8] */
+    int64_t n_frames, frame_bytes, capacity;
+    int64_t frame_offset; /* byte offset of the new frame in the block */
+    int32_t frame_slot;   /* destination ring slot; -1: this member writes no frame */
+    int32_t n_rows;
+    int64_t rows_offset;  /* byte offset of the row table in the block */
+} replay_group_member_t;
+int replay_group_add_step(int32_t n_members, const replay_group_member_t* members, void* block_host_pinned,
+                          void* block_staging_dev, int64_t block_bytes, void* stream);
 /* Growth of the frame ring (no reference counterpart: the reference's host dict grows by itself,
  * replay_buffer.py:206-213): the live frames, transition indices [first_t, first_t + count), are copied from slot
  * t % old_n of the old ring to slot t % new_n of the new one (count <= old_n <= new_n, distinct buffers).             */
