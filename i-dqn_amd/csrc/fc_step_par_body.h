@@ -176,10 +176,10 @@
         }
     }
     // delta = dL/dq, transposed [A rows][32 samples], in the buffer that does NOT hold the target's Q (still being read): its rows
-    // up to the next multiple of 32 zero (activations were there); the target net's LDS copy, dead now, becomes the gradient arena
+    // up to the next multiple of 32 past A zero (activations were there; every one of them, not the first 32: A may be 128); the target net's LDS copy, dead now, becomes the gradient arena
     float* delta = tq == dA ? dB : dA;
     float* dprev = tq == dA ? dA : dB;
-    for (int e = t; e < 32 * 32; e += FCM_T) delta[(e >> 5) * FCM_BSP + (e & 31)] = 0.f;
+    for (int e = t; e < 32 * ((A + 31) & ~31); e += FCM_T) delta[(e >> 5) * FCM_BSP + (e & 31)] = 0.f;  // (A <= 128 rows <= drows)
     __syncthreads();  // (every wave is done with the target net's matrices and with delta's old contents)
     for (long e = t; e < P / 4; e += FCM_T) reinterpret_cast<float4*>(Gs)[e] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (t < 32 && t < B) delta[a_b * FCM_BSP + t] = g_b;

@@ -170,7 +170,7 @@
         }
         float* delta = tq == dA ? dB : dA;
         float* dprev = tq == dA ? dA : dB;
-        for (int e = t; e < 32 * 32; e += FCM_T) delta[(e >> 5) * FCM_BSP + (e & 31)] = 0.f;
+        for (int e = t; e < 32 * ((A + 31) & ~31); e += FCM_T) delta[(e >> 5) * FCM_BSP + (e & 31)] = 0.f;  // (A <= 128 rows <= drows)
         if (!last && t < 32 && t < B) {  // the next step's rows to LDS: every thread needs the rows of its elements' samples
             reinterpret_cast<int4*>(rowsL)[2 * t] = rw0;
             reinterpret_cast<int4*>(rowsL)[2 * t + 1] = rw1;

@@ -2183,7 +2183,9 @@ extern "C" int idqn_learn_on_batch(idqn_handle_t h, const void* state_dev, const
         const size_t lds = (size_t)fp.floats * 4;
         const FcMfmaPlan& fm = h->fcm_plan_;
         const bool par = h->fcp_plan_.floats && batch <= 32;  // one launch: forwards side by side, Adam in the gradient epilogues
+        // h->dominant names the kernel this call launches, template variant included (idqn_profile_read reports it)
         if (par && h->rpf) {  // the minibatch comes from the replay frame ring (idqn_learn_on_replay_fc): the same single launch
+            h->dominant = "k_fc_step_par<ring>";
             const idqn_handle_s::FcReplaySrc& r = *h->rpf;
             const size_t lds_par = (size_t)h->fcp_plan_.floats * 4;
             const int adam = grads_only ? 0 : 1, prof = debug_on("IDQN_FC_PROF") ? 1 : 0;
@@ -2193,14 +2195,29 @@ extern "C" int idqn_learn_on_batch(idqn_handle_t h, const void* state_dev, const
             else
                 hipLaunchKernelGGL(k_fc_step_par<FcRingSrc<RpsSlotsPar>>, dim3(h->cfg.n_heads), dim3(FCM_T), lds_par, q, a, h->fcp_plan_, h->ad, h->online, h->mu,
                                    h->nu, adam, prof, FcRingSrc<RpsSlotsPar>{r.frames, r.rows, r.n_frames, r.frame_elems, r.stack, r.slots});
-        } else if (par) hipLaunchKernelGGL(k_fc_step_par<FcBatchSrc>, dim3(h->cfg.n_heads), dim3(FCM_T), (size_t)h->fcp_plan_.floats * 4, q, a, h->fcp_plan_, h->ad,
-                                    h->online, h->mu, h->nu, grads_only ? 0 : 1, debug_on("IDQN_FC_PROF") ? 1 : 0, FcBatchSrc{});
-        else if (fm.floats && h->fcm_global_) hipLaunchKernelGGL(k_fc_step_mfma<true>, dim3(h->cfg.n_heads), dim3(FCM_T), (size_t)fm.floats * 4, q, a, fm.ldw, fm.drows, fm.w_floats);
-        else if (fm.floats) hipLaunchKernelGGL(k_fc_step_mfma<false>, dim3(h->cfg.n_heads), dim3(FCM_T), (size_t)fm.floats * 4, q, a, fm.ldw, fm.drows, fm.w_floats);
-        else if (fp.BS == 32) hipLaunchKernelGGL(k_fc_step_lds<32>, dim3(h->cfg.n_heads), dim3(FC_T), lds, q, a, fp.tw, fp.wfl);
-        else if (fp.BS == 16) hipLaunchKernelGGL(k_fc_step_lds<16>, dim3(h->cfg.n_heads), dim3(FC_T), lds, q, a, fp.tw, fp.wfl);
-        else if (fp.BS == 8) hipLaunchKernelGGL(k_fc_step_lds<8>, dim3(h->cfg.n_heads), dim3(FC_T), lds, q, a, fp.tw, fp.wfl);
-        else hipLaunchKernelGGL(k_fc_step, dim3(h->cfg.n_heads), dim3(256), 0, q, a);
+        } else if (par) {
+            h->dominant = "k_fc_step_par";
+            hipLaunchKernelGGL(k_fc_step_par<FcBatchSrc>, dim3(h->cfg.n_heads), dim3(FCM_T), (size_t)h->fcp_plan_.floats * 4, q, a, h->fcp_plan_, h->ad,
+                               h->online, h->mu, h->nu, grads_only ? 0 : 1, debug_on("IDQN_FC_PROF") ? 1 : 0, FcBatchSrc{});
+        } else if (fm.floats && h->fcm_global_) {
+            h->dominant = "k_fc_step_mfma<global>";
+            hipLaunchKernelGGL(k_fc_step_mfma<true>, dim3(h->cfg.n_heads), dim3(FCM_T), (size_t)fm.floats * 4, q, a, fm.ldw, fm.drows, fm.w_floats);
+        } else if (fm.floats) {
+            h->dominant = "k_fc_step_mfma<lds>";
+            hipLaunchKernelGGL(k_fc_step_mfma<false>, dim3(h->cfg.n_heads), dim3(FCM_T), (size_t)fm.floats * 4, q, a, fm.ldw, fm.drows, fm.w_floats);
+        } else if (fp.BS == 32) {
+            h->dominant = "k_fc_step_lds<32>";
+            hipLaunchKernelGGL(k_fc_step_lds<32>, dim3(h->cfg.n_heads), dim3(FC_T), lds, q, a, fp.tw, fp.wfl);
+        } else if (fp.BS == 16) {
+            h->dominant = "k_fc_step_lds<16>";
+            hipLaunchKernelGGL(k_fc_step_lds<16>, dim3(h->cfg.n_heads), dim3(FC_T), lds, q, a, fp.tw, fp.wfl);
+        } else if (fp.BS == 8) {
+            h->dominant = "k_fc_step_lds<8>";
+            hipLaunchKernelGGL(k_fc_step_lds<8>, dim3(h->cfg.n_heads), dim3(FC_T), lds, q, a, fp.tw, fp.wfl);
+        } else {
+            h->dominant = "k_fc_step";
+            hipLaunchKernelGGL(k_fc_step, dim3(h->cfg.n_heads), dim3(256), 0, q, a);
+        }
         if (profile && h->ev_used + 2 <= (int)h->ev.size()) {
             IDQN_HIP_CHECK(hipEventRecord(h->ev[h->ev_used + 1], q));
             h->ev_used += 2;
@@ -2535,6 +2552,7 @@ static int learn_steps_on_replay_fc(idqn_handle_t h, const char* fn, const uint8
     a.cum = h->cum; a.finish_step = 1;
     a.is_weight = nullptr; a.td_abs = nullptr;
     a.s_stride = 0; a.din = nullptr; a.gm = GradMap{h->gP, h->g_w0_begin, h->g_w0_end, h->g_w0_base};
+    h->dominant = "k_fc_steps_par";  // (the loop route above leaves the single step's name)
     hipLaunchKernelGGL(k_fc_steps_par<FcRingSrc<RpsSlotsDev>>, dim3(h->cfg.n_heads), dim3(FCM_T), (size_t)h->fcs_plan_.floats * 4, q, a, h->fcs_plan_, h->ad,
                        h->online, h->mu, h->nu, (int)n_steps,
                        FcRingSrc<RpsSlotsDev>{(const float*)frame_ring_dev, rows_dev, n_frames, frame_bytes / 4, stack, RpsSlotsDev{slots_dev}});

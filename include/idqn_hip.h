@@ -427,7 +427,12 @@ int idqn_group_act_host_fc(idqn_group_t group, int32_t which, const int32_t* mem
 /* Test / debug access to internal activation buffers by name (device pointer + byte size).        */
 int idqn_debug_buffer(idqn_handle_t h, const char* name, void** ptr_dev, int64_t* nbytes);
 /* Mean duration (ms) and launch count of the dominant kernel over the IDQN_F_PROFILE calls since
- * the last read; synchronises the events it reads.                                                 */
+ * the last read; synchronises the events it reads.  kernel_name: the dominant kernel.  For MLP
+ * handles it is the kernel the LAST step launched, chosen per call and not at idqn_create, with the
+ * template variant: k_fc_step_par, k_fc_step_par<ring>, k_fc_steps_par (the persistent launch of
+ * idqn_learn_steps_on_replay_fc; when that entry loops, the single step's name), k_fc_step_mfma<global>,
+ * k_fc_step_mfma<lds>, k_fc_step_lds<32>, k_fc_step_lds<16>, k_fc_step_lds<8>, k_fc_step.  It is
+ * returned whether or not a step carried IDQN_F_PROFILE.                                             */
 int idqn_profile_read(idqn_handle_t h, double* mean_ms, int32_t* n_launches, char* kernel_name /*[64]*/);
 /* Per-launch table of the IDQN_F_PROFILE_ALL steps since the last read (at most ~100 steps are kept): one line per
  * launch of a step, "name\tmean microseconds\tcount\n", in launch order.  A launch's time is the span between the

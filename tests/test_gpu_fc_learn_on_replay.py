@@ -15,6 +15,8 @@ slots the fused agent really drew.
 import numpy as np
 import pytest
 
+import fc_shapes as F
+
 pytestmark = pytest.mark.gpu
 
 #        kind   frame shape  dtype     stack  obs dim / shape  features          K  A  B   agent
@@ -26,6 +28,11 @@ CONFIGS = {
     "gcnn_12x10x2": ("cnn", (12, 10), np.uint8, 2, (12, 10, 2), [2, 3, 1, 15], 2, 3, 5, "iDQN"),
     "gcnn_20x20x4": ("cnn", (20, 20), np.uint8, 4, (20, 20, 4), [8, 8, 8, 30, 20], 2, 6, 8, "iDQN"),
 }
+# Rows of the one-launch step's shape table (tests/fc_shapes.py) as ring-sourced cases "shape_<row>": odd din, 33- and 128-wide
+# layers, A = 1, d0 = 128, B = 1, the net within 2 KB of the LDS budget and the one that fits fc_par_plan but not fc_steps_plan
+SHAPE_CASES = ["shape_" + rid for rid in F.DESCENDANT_ROWS + (F.DESCENDANT_LOOP_ROW,)]
+CONFIGS.update({"shape_" + rid: ("fc", (F.BY_ID[rid].d0,), np.float32, 1, F.BY_ID[rid].d0, list(F.BY_ID[rid].feats), F.BY_ID[rid].K,
+                                 F.BY_ID[rid].A, F.BY_ID[rid].B, "iDQN") for rid in F.DESCENDANT_ROWS + (F.DESCENDANT_LOOP_ROW,)})
 STATE = ("_online", "_mu", "_nu", "_losses", "_cum", "_count")
 STEPS, HORIZON, CAPACITY = 3, 2, 40
 
@@ -146,6 +153,14 @@ def test_update_online_params_is_sample_then_learn(name):
     fused = _identity(name, _buffer)
     if CONFIGS[name][0] == "cnn":  # the plane entry's own flag says what it said before: not its handle / not its ring
         assert fused.__dict__.get("_replay_fused_ok") is False
+    if name in SHAPE_CASES:  # inside fc_par_plan: the ring was the one-launch step's own minibatch source
+        import ctypes as C
+
+        from slimdqn import _hip
+
+        mean_ms, n_l, kernel = C.c_double(), C.c_int32(), C.create_string_buffer(64)
+        _hip.check(_hip.lib().idqn_profile_read(fused._handle, C.byref(mean_ms), C.byref(n_l), kernel), "idqn_profile_read")
+        assert kernel.value.decode() == "k_fc_step_par<ring>"
 
 
 @pytest.mark.parametrize("name", ["lunar_par", "gcnn_12x10x2"])

@@ -9,6 +9,8 @@ and, for a stack of two, a stack with zero frames in front of an episode start -
 import numpy as np
 import pytest
 
+import fc_shapes as F
+
 pytestmark = pytest.mark.gpu
 
 #        arch  frame shape  dtype     stack  obs         features      K  A  B   agent
@@ -21,6 +23,18 @@ CONFIGS = {
     "gcnn": ("cnn", (12, 10), np.uint8, 2, (12, 10, 2), [2, 3, 1, 15], 2, 3, 5, "iDQN"),
 }
 PERSISTENT = ("lunar", "dqn_ragged", "odd_tiles")
+# Rows of the one-launch step's shape table (tests/fc_shapes.py: odd din, 33- and 128-wide layers, A = 1, d0 = 128, B = 1, the net
+# within 2 KB of the LDS budget), as "shape_<row>"; the net that fits fc_par_plan but not fc_steps_plan goes to the loop route.
+
+
+def _shape_config(rid):
+    r = F.BY_ID[rid]
+    return ("fc", (r.d0,), np.float32, 1, r.d0, list(r.feats), r.K, r.A, r.B, "iDQN")
+
+
+CONFIGS.update({"shape_" + rid: _shape_config(rid) for rid in F.DESCENDANT_ROWS + (F.DESCENDANT_LOOP_ROW,)})
+PERSISTENT += tuple("shape_" + rid for rid in F.DESCENDANT_ROWS)
+SHAPE_LOOP = "shape_" + F.DESCENDANT_LOOP_ROW
 STATE = ("_online", "_mu", "_nu", "_losses", "_cum", "_count", "_grad", "_target")
 HORIZON, CAPACITY = 2, 40
 
@@ -85,12 +99,13 @@ def _covers(rb, slots, stack):
     return bool((rows[:, 6] == 1).any()) and (stack == 1 or bool((rows[:, 1] < stack).any() or (rows[:, 3] < stack).any()))
 
 
-def _draws(rb, n, stack):
-    """``n`` sampler draws [n][B] from the first generator seed whose draws hold the elements the cases are about."""
+def _draws(rb, n, stack, head=None):
+    """``n`` sampler draws [n][B] from the first generator seed whose draws hold the elements the cases are about (``head``: and
+    whose first ``head`` draws already do -- the small batches of the shape-table rows)."""
     for seed in range(400):
         rb._sampling_distribution._rng_key = np.random.default_rng(seed)
         slots = np.stack([np.ascontiguousarray(rb.sample_slots(), np.int32) for _ in range(n)])
-        if _covers(rb, slots, stack):
+        if _covers(rb, slots, stack) and (head is None or _covers(rb, slots[:head], stack)):
             return slots
     raise AssertionError("no sampler seed below 400 draws the elements this case is about")
 
@@ -166,7 +181,7 @@ def _case_draws(name, ring, n=32):
     key = (name, ring)
     if key not in _DRAWS:
         rb = (_buffer if ring == "ring" else _vector_buffer)(name)
-        _DRAWS[key] = _draws(rb, n, CONFIGS[name][3])
+        _DRAWS[key] = _draws(rb, n, CONFIGS[name][3], head=7 if name.startswith("shape_") else None)
     return _DRAWS[key]
 
 
@@ -195,9 +210,22 @@ def test_identity_persistent_route(name, ring, warm):
         assert _snapshot(many, ("_target",))["_target"] == before
         assert (many._count.cpu().numpy() == n + (5 if warm else 0)).all() and np.isfinite(many._losses.cpu().numpy()).all()
         assert many._handle.value and many.__dict__.get("_replay_fc_ok") is None
+        if name.startswith("shape_"):  # the launch is the persistent kernel, the twin's the ring-sourced single step
+            assert _route(many) == _route(many_dev) == "k_fc_steps_par" and _route(twin) == "k_fc_step_par<ring>"
 
 
-@pytest.mark.parametrize("name", ["lunar_b64", "fc_520", "gcnn"])
+def _route(agent):
+    """The kernel the handle's last MLP step launched (idqn_profile_read)."""
+    import ctypes as C
+
+    from slimdqn import _hip
+
+    mean_ms, n_l, kernel = C.c_double(), C.c_int32(), C.create_string_buffer(64)
+    _hip.check(_hip.lib().idqn_profile_read(agent._handle, C.byref(mean_ms), C.byref(n_l), kernel), "idqn_profile_read")
+    return kernel.value.decode()
+
+
+@pytest.mark.parametrize("name", ["lunar_b64", "fc_520", "gcnn", SHAPE_LOOP])
 def test_identity_loop_route(name):
     """Handles and batches outside the one-launch plan: the entry loops over the single step (case 2)."""
     rb = _buffer(name)
@@ -211,6 +239,8 @@ def test_identity_loop_route(name):
     _assert_same(many, twin)
     _assert_same(many_dev, twin, "device slots")
     assert (many._count.cpu().numpy() == 3).all()
+    if name == SHAPE_LOOP:  # inside fc_par_plan, 1 KB short for fc_steps_plan: every step of the loop is the one-launch step on the ring
+        assert _route(many) == _route(many_dev) == _route(twin) == "k_fc_step_par<ring>"
 
 
 def test_staging_blocks_are_reused_safely():

@@ -14,6 +14,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import fc_shapes as F
+
 pytestmark = pytest.mark.gpu
 
 #         frame  stack  obs  features    K  A  B
@@ -22,6 +24,11 @@ SHAPES = {
     "ragged": ((5,), 1, 5, [33, 70], 2, 3, 7),
     "ragged_stack2": ((3,), 2, 6, [33, 70], 2, 3, 7),
 }
+# Rows of the one-launch step's shape table (tests/fc_shapes.py) as member shapes "shape_<row>": odd din, 33- and 128-wide layers,
+# A = 1, d0 = 128, B = 1 and the net within 2 KB of the LDS budget, two members each
+SHAPES.update({"shape_" + rid: ((F.BY_ID[rid].d0,), 1, F.BY_ID[rid].d0, list(F.BY_ID[rid].feats), F.BY_ID[rid].K, F.BY_ID[rid].A, F.BY_ID[rid].B)
+               for rid in F.DESCENDANT_ROWS})
+TABLE_SHAPES = ["shape_" + rid for rid in F.DESCENDANT_ROWS]
 HYPER = [(1e-3, 1e-8, 0.99), (3e-4, 1.5e-4, 0.9), (2e-3, 1e-6, 0.95), (5e-4, 1e-7, 0.999)]  # lr, Adam eps, gamma per member
 ARENAS = ("_online", "_target", "_mu", "_nu", "_grad", "_count", "_cum")
 CAPACITY = 40
@@ -166,7 +173,8 @@ def _members(shape, S, vector_member=None):
     return agents, rbs
 
 
-@pytest.mark.parametrize("shape,S,vector_member", [("lunar", 3, None), ("ragged", 2, 1), ("ragged_stack2", 2, 1), ("lunar", 1, None)])
+@pytest.mark.parametrize("shape,S,vector_member", [("lunar", 3, None), ("ragged", 2, 1), ("ragged_stack2", 2, 1), ("lunar", 1, None)]
+                         + [(name, 2, None) for name in TABLE_SHAPES])
 @pytest.mark.parametrize("flags", [0, 1])  # 1: IDQN_F_GRADS_ONLY
 def test_group_step_equals_solo_steps(shape, S, vector_member, flags):
     """Two group calls (the second on warm moments); after each, every member equals its twin stepped alone."""
@@ -226,7 +234,7 @@ def test_history_of_group_and_solo_calls():
 
 
 @pytest.mark.parametrize("n", [1, 2, 5, 7])
-@pytest.mark.parametrize("shape,S,vector_member", [("lunar", 3, None), ("ragged_stack2", 2, 1)])
+@pytest.mark.parametrize("shape,S,vector_member", [("lunar", 3, None), ("ragged_stack2", 2, 1)] + [(name, 2, None) for name in TABLE_SHAPES])
 def test_group_n_steps_equal_n_group_steps_and_n_solo_steps(n, shape, S, vector_member):
     import torch
 
@@ -252,7 +260,7 @@ def test_group_n_steps_equal_n_group_steps_and_n_solo_steps(n, shape, S, vector_
 
 
 @pytest.mark.parametrize("n", [1, 3, 32])
-@pytest.mark.parametrize("shape,S", [("lunar", 3), ("ragged", 2)])
+@pytest.mark.parametrize("shape,S", [("lunar", 3), ("ragged", 2)] + [(name, 2) for name in TABLE_SHAPES])
 def test_group_acting_equals_act_host_on_the_member(n, shape, S):
     """Members in shuffled order, several states on one member with different heads, both parameter sets; the single-state
     reference runs blocking and as a begin / end pair (``lazy_host_actions``)."""
