@@ -3,8 +3,8 @@
 // The one-launch step k_fc_step_par (fc_par_kernels.h), its persistent sibling k_fc_steps_par (fc_steps_kernels.h) and the
 // acting kernel k_fc_act_many1 (fc_act_many_kernels.h) use one workgroup per head or state: K = 3 workgroups of a 256-CU chip
 // for the LunarLander net.  Within a step the K heads never talk to each other, so S agents are S * K such workgroups:
-//   * k_fc_group_step / k_fc_group_steps, grid (K, S): workgroup (k, g) runs the body of k_fc_step_par / k_fc_steps_par -- the
-//     SAME text (fc_step_par_body.h, fc_steps_par_body.h), statement for statement -- for head k of member g.  What a solo
+//   * k_fc_group_step / k_fc_group_steps, grid (K, S): workgroup (k, g) calls fc_step_par / fc_steps_par -- the
+//     functions k_fc_step_par / k_fc_steps_par call (phases: fc_par_phases.h) -- for head k of member g.  What a solo
 //     launch receives as kernel arguments (FcArgs, the LDS plan, AdamConsts, the arenas, the ring source) is record g of a
 //     device table FcGroupMember[S]: loads at uniform addresses from memory nothing writes during the launch.  Every
 //     member's bytes after the launch are therefore the bytes of a solo launch on that member.
@@ -24,27 +24,15 @@ struct FcGroupMember {  // what a solo launch of member g receives as kernel arg
     FcRingSrc<RpsSlotsDev> src;
 };
 
-// the names the bodies expect, as references into record blockIdx.y
-#define FC_GROUP_MEMBER_SCOPE                                    \
-    using Src = FcRingSrc<RpsSlotsDev>;                          \
-    const FcGroupMember& member = tab[blockIdx.y];               \
-    const FcArgs& a = member.a;                                  \
-    const FcParPlan& p = member.plan;                            \
-    const AdamConsts& ad = member.ad;                            \
-    float *const theta = member.theta, *const mu = member.mu, *const nu = member.nu; \
-    const Src& src = member.src;
-
 __global__ __launch_bounds__(FCM_T) void k_fc_group_step(const FcGroupMember* __restrict__ tab, int do_adam) {
-    FC_GROUP_MEMBER_SCOPE
-    const int prof = 0;
-#include "fc_step_par_body.h"
+    const FcGroupMember& m = tab[blockIdx.y];
+    fc_step_par<false>(m.a, m.plan, m.ad, m.theta, m.mu, m.nu, do_adam, m.src);
 }
 
 __global__ __launch_bounds__(FCM_T) void k_fc_group_steps(const FcGroupMember* __restrict__ tab, int n_steps) {
-    FC_GROUP_MEMBER_SCOPE
-#include "fc_steps_par_body.h"
+    const FcGroupMember& m = tab[blockIdx.y];
+    fc_steps_par(m.a, m.plan, m.ad, m.theta, m.mu, m.nu, n_steps, m.src);
 }
-#undef FC_GROUP_MEMBER_SCOPE
 
 // The head of the group's acting block: ActManyTable as in every many-state chain (n is used), then the parameter base of
 // each state's (member, parameter set, head); the n float32 states follow.

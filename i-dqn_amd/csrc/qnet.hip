@@ -393,7 +393,7 @@ struct idqn_handle_s {
     // launch's stacked minibatches [max_batch][obs], and -- set for the duration of a call whose batch runs k_fc_step_par --
     // the ring as that kernel's minibatch source (slots_dev != nullptr: read from that device array, `slots` unused)
     void *rp_state = nullptr, *rp_next = nullptr;
-    struct FcReplaySrc { const float* frames; const int32_t* rows; long n_frames, frame_elems; int stack; const int32_t* slots_dev; RpsSlotsPar slots; };
+    struct FcReplaySrc { const void* frames; const int32_t* rows; long n_frames, frame_bytes; int stack; const int32_t* slots_dev; RpsSlotsPar slots; };
     const FcReplaySrc* rpf = nullptr;
     const float* is_weight = nullptr;  // prioritized-replay extension (idqn_set_per_buffers)
     float* td_abs = nullptr;
@@ -885,6 +885,48 @@ int gcnn_trunk(idqn_handle_s* h, const float* const* wbase, int n_nets, int n_sp
     return IDQN_OK;
 }
 
+// What every MLP-step launch of handle h is told: the arenas, the counters and outputs, the constants.  The batch pointers,
+// s_stride / din and is_weight / td_abs stay NULL / 0 for the caller to set.
+static FcArgs fc_args(idqn_handle_s* h, int batch, int mean_divisor, bool grads_only) {
+    FcArgs a;
+    memset(&a, 0, sizeof(a));
+    a.net = h->fc; a.online = h->online; a.target = h->target; a.grad = h->grad; a.P = h->L.head_stride;
+    a.gamma_n = h->gamma_n; a.B = batch; a.Bdiv = mean_divisor; a.K = h->cfg.n_heads;
+    a.ws = h->fc_ws; a.losses = h->losses; a.q_dbg = h->qdbg;
+    a.count = h->count; a.bcinv = h->bcinv; a.adam_b1 = h->ad.b1; a.adam_b2 = h->ad.b2;
+    a.cum = h->cum; a.finish_step = grads_only ? 0 : 1;
+    a.gm = GradMap{h->gP, h->g_w0_begin, h->g_w0_end, h->g_w0_base};
+    return a;
+}
+
+// The replay frame ring as the one-launch step's minibatch source
+template <class Slots>
+static FcRingSrc<Slots> fc_ring_src(const void* ring, const int32_t* rows, long n_frames, long frame_bytes, int stack, const Slots& slots) {
+    return FcRingSrc<Slots>{(const float*)ring, rows, n_frames, frame_bytes / 4, stack, slots};
+}
+
+// k_fc_step_par<PROF, Src>: the stamped instantiation (IDQN_FC_PROF) exists in the debug build only
+template <class Src>
+static hipError_t fc_step_par_set_lds(int bytes) {
+#ifdef IDQN_DEBUG_KNOBS
+    if (const hipError_t e = hipFuncSetAttribute((const void*)k_fc_step_par<true, Src>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes)) return e;
+#endif
+    return hipFuncSetAttribute((const void*)k_fc_step_par<false, Src>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+}
+template <class Src>
+static void fc_step_par_launch(idqn_handle_s* h, hipStream_t q, const FcArgs& a, bool grads_only, const Src& src) {
+    const dim3 grid(h->cfg.n_heads);
+    const size_t lds = (size_t)h->fcp_plan_.floats * 4;
+    const int adam = grads_only ? 0 : 1;
+#ifdef IDQN_DEBUG_KNOBS
+    if (debug_on("IDQN_FC_PROF")) {
+        hipLaunchKernelGGL((k_fc_step_par<true, Src>), grid, dim3(FCM_T), lds, q, a, h->fcp_plan_, h->ad, h->online, h->mu, h->nu, adam, src);
+        return;
+    }
+#endif
+    hipLaunchKernelGGL((k_fc_step_par<false, Src>), grid, dim3(FCM_T), lds, q, a, h->fcp_plan_, h->ad, h->online, h->mu, h->nu, adam, src);
+}
+
 int gcnn_learn(idqn_handle_s* h, const uint8_t* st, const uint8_t* st2, const int32_t* action, const float* reward,
                const uint8_t* terminal, int B, int Bdiv, bool grads_only, bool profile, hipStream_t q) {
     GcnnWs& g = h->gc;
@@ -892,15 +934,10 @@ int gcnn_learn(idqn_handle_s* h, const uint8_t* st, const uint8_t* st2, const in
     IDQN_REQUIRE(B <= g.Bmax, "batch %d exceeds the workspace (%d)", B, g.Bmax);
     int rc = gcnn_trunk(h, h->train.wbase, 2 * K, K, B, st, st2, g.act, q);
     if (rc) return rc;
-    FcArgs a;
-    a.net = h->fc; a.online = h->online; a.target = h->target; a.grad = h->grad; a.P = h->L.head_stride;
+    FcArgs a = fc_args(h, B, Bdiv, grads_only);
     a.s = g.act[2]; a.s2 = g.act[2] + (long)K * B * h->F; a.s_stride = (long)B * h->F; a.din = g.dact[2];
-    a.action = action; a.reward = reward; a.terminal = terminal; a.gamma_n = h->gamma_n; a.B = B; a.Bdiv = Bdiv; a.K = K;
-    a.ws = h->fc_ws; a.losses = h->losses; a.q_dbg = h->qdbg;
-    a.count = h->count; a.bcinv = h->bcinv; a.adam_b1 = h->ad.b1; a.adam_b2 = h->ad.b2;
-    a.cum = h->cum; a.finish_step = grads_only ? 0 : 1;
+    a.action = action; a.reward = reward; a.terminal = terminal;
     a.is_weight = h->is_weight; a.td_abs = h->td_abs;
-    a.gm = GradMap{h->gP, h->g_w0_begin, h->g_w0_end, h->g_w0_base};
     if (profile && h->ev_used + 2 <= (int)h->ev.size()) IDQN_HIP_CHECK(hipEventRecord(h->ev[h->ev_used], q));
     hipLaunchKernelGGL(k_fc_step, dim3(K), dim3(256), 0, q, a);
     if (profile && h->ev_used + 2 <= (int)h->ev.size()) {
@@ -950,9 +987,9 @@ int fc_setup(idqn_handle_s* h) {
     if ((getenv("IDQN_FC_PAR") && atoi(getenv("IDQN_FC_PAR")) == 0) || n.dmax > FC_MAX_WIDTH) h->fcp_plan_.floats = 0;
     if (h->fcp_plan_.floats) {
         const int bytes = (int)(h->fcp_plan_.floats * 4);
-        IDQN_HIP_CHECK(hipFuncSetAttribute((const void*)k_fc_step_par<FcBatchSrc>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-        IDQN_HIP_CHECK(hipFuncSetAttribute((const void*)k_fc_step_par<FcRingSrc<RpsSlotsPar>>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-        IDQN_HIP_CHECK(hipFuncSetAttribute((const void*)k_fc_step_par<FcRingSrc<RpsSlotsDev>>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        IDQN_HIP_CHECK(fc_step_par_set_lds<FcBatchSrc>(bytes));
+        IDQN_HIP_CHECK(fc_step_par_set_lds<FcRingSrc<RpsSlotsPar>>(bytes));
+        IDQN_HIP_CHECK(fc_step_par_set_lds<FcRingSrc<RpsSlotsDev>>(bytes));
         h->fcs_plan_ = fc_steps_plan(n, h->L.head_stride);
         if (h->fcs_plan_.floats)
             IDQN_HIP_CHECK(hipFuncSetAttribute((const void*)k_fc_steps_par<FcRingSrc<RpsSlotsDev>>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -2169,15 +2206,10 @@ extern "C" int idqn_learn_on_batch(idqn_handle_t h, const void* state_dev, const
         }
         if ((rc = issue(q))) return rc;
     } else {
-        FcArgs a;
-        a.net = h->fc; a.online = h->online; a.target = h->target; a.grad = h->grad; a.P = h->L.head_stride;
+        FcArgs a = fc_args(h, batch, batch_mean_divisor, grads_only);
         a.s = (const float*)state_dev; a.s2 = (const float*)next_state_dev; a.action = action_dev; a.reward = reward_dev;
-        a.terminal = terminal_dev; a.gamma_n = h->gamma_n; a.B = batch; a.Bdiv = batch_mean_divisor; a.K = h->cfg.n_heads;
-        a.ws = h->fc_ws; a.losses = h->losses; a.q_dbg = h->qdbg;
-        a.count = h->count; a.bcinv = h->bcinv; a.adam_b1 = h->ad.b1; a.adam_b2 = h->ad.b2;
-        a.cum = h->cum; a.finish_step = grads_only ? 0 : 1;
+        a.terminal = terminal_dev;
         a.is_weight = h->is_weight; a.td_abs = h->td_abs;
-        a.s_stride = 0; a.din = nullptr; a.gm = GradMap{h->gP, h->g_w0_begin, h->g_w0_end, h->g_w0_base};
         if (profile && h->ev_used + 2 <= (int)h->ev.size()) IDQN_HIP_CHECK(hipEventRecord(h->ev[h->ev_used], q));
         const FcPlan& fp = h->fc_plan_;
         const size_t lds = (size_t)fp.floats * 4;
@@ -2187,18 +2219,11 @@ extern "C" int idqn_learn_on_batch(idqn_handle_t h, const void* state_dev, const
         if (par && h->rpf) {  // the minibatch comes from the replay frame ring (idqn_learn_on_replay_fc): the same single launch
             h->dominant = "k_fc_step_par<ring>";
             const idqn_handle_s::FcReplaySrc& r = *h->rpf;
-            const size_t lds_par = (size_t)h->fcp_plan_.floats * 4;
-            const int adam = grads_only ? 0 : 1, prof = debug_on("IDQN_FC_PROF") ? 1 : 0;
-            if (r.slots_dev)
-                hipLaunchKernelGGL(k_fc_step_par<FcRingSrc<RpsSlotsDev>>, dim3(h->cfg.n_heads), dim3(FCM_T), lds_par, q, a, h->fcp_plan_, h->ad, h->online, h->mu,
-                                   h->nu, adam, prof, FcRingSrc<RpsSlotsDev>{r.frames, r.rows, r.n_frames, r.frame_elems, r.stack, RpsSlotsDev{r.slots_dev}});
-            else
-                hipLaunchKernelGGL(k_fc_step_par<FcRingSrc<RpsSlotsPar>>, dim3(h->cfg.n_heads), dim3(FCM_T), lds_par, q, a, h->fcp_plan_, h->ad, h->online, h->mu,
-                                   h->nu, adam, prof, FcRingSrc<RpsSlotsPar>{r.frames, r.rows, r.n_frames, r.frame_elems, r.stack, r.slots});
+            if (r.slots_dev) fc_step_par_launch(h, q, a, grads_only, fc_ring_src(r.frames, r.rows, r.n_frames, r.frame_bytes, r.stack, RpsSlotsDev{r.slots_dev}));
+            else fc_step_par_launch(h, q, a, grads_only, fc_ring_src(r.frames, r.rows, r.n_frames, r.frame_bytes, r.stack, r.slots));
         } else if (par) {
             h->dominant = "k_fc_step_par";
-            hipLaunchKernelGGL(k_fc_step_par<FcBatchSrc>, dim3(h->cfg.n_heads), dim3(FCM_T), (size_t)h->fcp_plan_.floats * 4, q, a, h->fcp_plan_, h->ad,
-                               h->online, h->mu, h->nu, grads_only ? 0 : 1, debug_on("IDQN_FC_PROF") ? 1 : 0, FcBatchSrc{});
+            fc_step_par_launch(h, q, a, grads_only, FcBatchSrc{});
         } else if (fm.floats && h->fcm_global_) {
             h->dominant = "k_fc_step_mfma<global>";
             hipLaunchKernelGGL(k_fc_step_mfma<true>, dim3(h->cfg.n_heads), dim3(FCM_T), (size_t)fm.floats * 4, q, a, fm.ldw, fm.drows, fm.w_floats);
@@ -2421,7 +2446,7 @@ static int learn_on_replay_fc(idqn_handle_t h, const char* fn, const uint8_t* fr
     static const bool always_stage = getenv("IDQN_FC_REPLAY_STAGE") && atoi(getenv("IDQN_FC_REPLAY_STAGE")) != 0;
     if (fc && h->fcp_plan_.floats && batch <= RPS_PAR_SLOTS && !always_stage) {
         idqn_handle_s::FcReplaySrc src;
-        src.frames = (const float*)frame_ring_dev; src.rows = rows_dev; src.n_frames = n_frames; src.frame_elems = frame_bytes / 4;
+        src.frames = frame_ring_dev; src.rows = rows_dev; src.n_frames = n_frames; src.frame_bytes = frame_bytes;
         src.stack = stack; src.slots_dev = slots_dev;
         memset(&src.slots, 0, sizeof(src.slots));
         if (!slots_dev) memcpy(src.slots.slot, slots_host, (size_t)batch * 4);
@@ -2543,19 +2568,11 @@ static int learn_steps_on_replay_fc(idqn_handle_t h, const char* fn, const uint8
     }
     h->pend_B = 0; h->pend_stage = 0;
     h->tl_on = false;
-    FcArgs a;
-    a.net = h->fc; a.online = h->online; a.target = h->target; a.grad = h->grad; a.P = h->L.head_stride;
-    a.s = nullptr; a.s2 = nullptr; a.action = nullptr; a.reward = nullptr; a.terminal = nullptr;  // (the ring is the minibatch source)
-    a.gamma_n = h->gamma_n; a.B = batch; a.Bdiv = batch_mean_divisor; a.K = h->cfg.n_heads;
-    a.ws = h->fc_ws; a.losses = h->losses; a.q_dbg = h->qdbg;
-    a.count = h->count; a.bcinv = h->bcinv; a.adam_b1 = h->ad.b1; a.adam_b2 = h->ad.b2;
-    a.cum = h->cum; a.finish_step = 1;
-    a.is_weight = nullptr; a.td_abs = nullptr;
-    a.s_stride = 0; a.din = nullptr; a.gm = GradMap{h->gP, h->g_w0_begin, h->g_w0_end, h->g_w0_base};
+    const FcArgs a = fc_args(h, batch, batch_mean_divisor, false);  // (the ring is the minibatch source: the batch pointers stay NULL)
     h->dominant = "k_fc_steps_par";  // (the loop route above leaves the single step's name)
     hipLaunchKernelGGL(k_fc_steps_par<FcRingSrc<RpsSlotsDev>>, dim3(h->cfg.n_heads), dim3(FCM_T), (size_t)h->fcs_plan_.floats * 4, q, a, h->fcs_plan_, h->ad,
                        h->online, h->mu, h->nu, (int)n_steps,
-                       FcRingSrc<RpsSlotsDev>{(const float*)frame_ring_dev, rows_dev, n_frames, frame_bytes / 4, stack, RpsSlotsDev{slots_dev}});
+                       fc_ring_src(frame_ring_dev, rows_dev, n_frames, frame_bytes, stack, RpsSlotsDev{slots_dev}));
     IDQN_HIP_CHECK(hipGetLastError());
     if (blk >= 0) return steps_stage_guard(h, blk, q);
     return IDQN_OK;
@@ -3719,17 +3736,11 @@ static void group_fill_member(FcGroupMember& m, idqn_handle_t h, const idqn_grou
     h->pend_B = 0; h->pend_stage = 0;
     h->tl_on = false;
     memset(&m, 0, sizeof(m));
-    FcArgs& a = m.a;
-    a.net = h->fc; a.online = h->online; a.target = h->target; a.grad = h->grad; a.P = h->L.head_stride;
-    a.gamma_n = h->gamma_n; a.B = batch; a.Bdiv = mean_divisor; a.K = h->cfg.n_heads;
-    a.ws = h->fc_ws; a.losses = h->losses; a.q_dbg = h->qdbg;
-    a.count = h->count; a.bcinv = h->bcinv; a.adam_b1 = h->ad.b1; a.adam_b2 = h->ad.b2;
-    a.cum = h->cum; a.finish_step = grads_only ? 0 : 1;
-    a.gm = GradMap{h->gP, h->g_w0_begin, h->g_w0_end, h->g_w0_base};
+    m.a = fc_args(h, batch, mean_divisor, grads_only);
     m.plan = steps_plan ? h->fcs_plan_ : h->fcp_plan_;
     m.ad = h->ad;
     m.theta = h->online; m.mu = h->mu; m.nu = h->nu;
-    m.src = FcRingSrc<RpsSlotsDev>{(const float*)r.frames_dev, r.rows_dev, r.n_frames, r.frame_bytes / 4, r.stack, RpsSlotsDev{slots_dev}};
+    m.src = fc_ring_src(r.frames_dev, r.rows_dev, r.n_frames, r.frame_bytes, r.stack, RpsSlotsDev{slots_dev});
 }
 
 // One launch of grid (K, S): block = {FcGroupMember[S], slots [S][n_steps][batch]}, n_steps == 0: the single step k_fc_group_step

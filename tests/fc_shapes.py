@@ -1,4 +1,4 @@
-"""The shape table of the one-launch MLP step (``k_fc_step_par``, csrc/fc_par_kernels.h + csrc/fc_step_par_body.h) and a
+"""The shape table of the one-launch MLP step (``k_fc_step_par``, csrc/fc_par_kernels.h + csrc/fc_par_phases.h) and a
 Python restatement of the two LDS plans that decide which nets run it.
 
 The restatement (``par_plan`` = ``fc_par_plan``, ``steps_plan`` = ``fc_steps_plan``, ``layout`` = the fc branch of

@@ -1,6 +1,6 @@
 """GPU: the one-launch MLP step ``k_fc_step_par`` against the fp64 oracle at every boundary of its LDS plan.
 
-Every descendant of csrc/fc_step_par_body.h (the ring-sourced step, the persistent n-step kernel, seed groups, prioritized seed
+Every descendant of fc_step_par, csrc/fc_par_kernels.h (the ring-sourced step, the persistent n-step kernel, seed groups, prioritized seed
 groups, grouped acting) is pinned to ``k_fc_step_par<FcBatchSrc>`` byte for byte, so the oracle reaches the family through
 this kernel only -- and which kernel a step ran was not observable.  Here every row of tests/fc_shapes.py
 
