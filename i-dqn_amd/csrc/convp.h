@@ -43,7 +43,22 @@ struct CVar {  // one sub-convolution of a launch (forward: one; data gradient o
     int out_mul, out_add_h, out_add_w;  // output position (oh, ow) -> (oh * out_mul + out_add_h, ...)
     int pad;
 };
+// What a one-item workgroup (k_cfwd, the data-gradient role of k_cpair) needs to know about its item, resolved on the
+// host where the launch plan is made (convp_items.h) and read with ONE 64-byte scalar load of table[workgroup]: byte
+// offsets, not pointers, so a plan's table serves every step.  SAME padding is materialised as zero borders of the
+// planes, so an item carries origins only, no edge masks.
+struct CFwdDesc {
+    long in_off;        // bytes from CFwdArgs::in: the item's input slot + the pixel chunk strip 0 starts at (kernel row 0, chunk 0)
+    long w_off;         // bytes from CFwdArgs::wq: the net's packed kernels + the variant's
+    int net, out_slot;  // out_slot = net * nb + batch block
+    int var, p0, np, oh0;  // positions [p0, p0 + np) of variant var; oh0 = output row of p0
+    unsigned short c0[CP_MAX_STRIPS], ncol[CP_MAX_STRIPS];  // strip r: output columns [c0, c0 + ncol) of output row oh0 + r (ncol 0: none)
+    int bb, pad;
+};
+static_assert(sizeof(CFwdDesc) == 64, "CFwdDesc is one 64-byte scalar load");
+
 struct CFwdArgs {
+    const CFwdDesc* items;      // one-item launches: the plan's item table, indexed by the (XCD-contiguous) workgroup index
     const unsigned short* in;   // input planes
     const unsigned short* wq;   // packed weights
     const float* pbase[2];      // f32 parameter arenas: net n < n_first reads pbase[0] + n * pstride, else pbase[1] + (n - n_first) * pstride
@@ -55,8 +70,8 @@ struct CFwdArgs {
     long in_slot, out_slot, mask_slot, f32_slot;  // bytes / bytes / bytes / floats per (net, batch block)
     long b_off, pstride;
     int n_first;
-    // work items (no table: a workgroup derives its item from its index): per (net, batch block) slot, variant v has
-    // r_cnt[v] balanced ranges of its OH * OW positions, the ranges of variant v start at r_begin[v]
+    // work items: per (net, batch block) slot, variant v has r_cnt[v] balanced ranges of its OH * OW positions, the ranges
+    // of variant v start at r_begin[v] (what convp_items.h makes the item table from; the kernels read the table)
     int items_per_slot, r_begin[4], r_cnt[4];
     int in_split;   // input slot of net n: (in_split > 0 ? n >= in_split : n) * nb + bb
     int range_major;  // 1: consecutive workgroups walk the nets of one position range (nets share the input: Conv_0)

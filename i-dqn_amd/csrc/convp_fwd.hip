@@ -9,7 +9,7 @@ namespace {
 template <int NPA, int CT, int NQ, int NT>
 __global__ __launch_bounds__(512) void k_cfwd(CFwdArgs a, unsigned stage_bytes, int ring, unsigned mask_off, long long* prof) {
     warm_kernargs<sizeof(CFwdArgs)>();
-    cfwd_body<NPA, CT, NQ, NT>(a, stage_bytes, ring, mask_off, prof, xcd_contiguous_id(), (int)gridDim.x);
+    cfwd_body<NPA, CT, NQ, NT>(a, stage_bytes, ring, mask_off, prof, xcd_contiguous_id());
 }
 
 template <int NPA, int CT, int NQ, int NT>

@@ -38,10 +38,10 @@ __device__ __forceinline__ bf16x8 frag_lin(const unsigned char* p) {
     return *(const __attribute__((address_space(3))) bf16x8*)p;
 }
 
-// b = this workgroup's item index (already remapped XCD-contiguously), nblk = items of the launch (or of this role).
+// b = this workgroup's item index (already remapped XCD-contiguously): its entry of the item table a.items.
 template <int NPA, int CT, int NQ, int NT>
-__device__ __forceinline__ void cfwd_body(const CFwdArgs& a, unsigned stage_bytes, int ring, unsigned mask_off, long long* prof,
-                                          const int b, const int nblk) {
+__device__ __forceinline__ void cfwd_body(const CFwdArgs& a, unsigned stage_bytes, int ring, unsigned mask_off, long long* prof_arg,
+                                          const int b) {
     extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];
     constexpr int WB = NQ * CT * 3 * 1024, BLKA = NPA * 1024, NWP = NQ * CT * 3;
     const int t = threadIdx.x, lane = t & 63, h = lane >> 5, cl = lane & 31;
@@ -50,71 +50,53 @@ __device__ __forceinline__ void cfwd_body(const CFwdArgs& a, unsigned stage_byte
     const int wave8 = __builtin_amdgcn_readfirstlane(t >> 6);
     const bool loader = wave8 >= 4;
     const int wave = wave8 & 3;
-    // (stamps are unconditional up to the loop: a branch here splits the block and the kernel-argument loads, which the
-    // scheduler otherwise batches at the top, become a chain of dependent round trips)
+    // The phase stamps exist in the debug build only: in the shipped one `prof` is a constant and the stamps, their counter
+    // reads in front of the first copy and the ten scalar registers they kept live across the superstep loop fold away.
+    // (In the debug build they are unconditional up to the loop: a branch here splits the block and the kernel-argument
+    // loads, which the scheduler otherwise batches at the top, become a chain of dependent round trips.)
+#ifdef IDQN_DEBUG_KNOBS
+    long long* const prof = prof_arg;
     const long long pt0 = clock64(), pw0 = wall_clock64();
-    CItem it;  // derived from the workgroup index (an XCD walks consecutive items of one net): no dependent load
-    int vi = 0, item_in_slot = 0;
-    {
-        // net-major by default: an XCD walks consecutive ranges of one net and shares its packed kernels through L2.
-        // Range-major where the nets read the SAME input (Conv_0: K nets per staged minibatch): an XCD then holds a few
-        // position ranges of every net, so a pixel strip crosses the fabric once per XCD instead of once per net.
-        int slot, rr;
-        if (a.range_major) {
-            const int n_slots = nblk / a.items_per_slot;
-            rr = b / n_slots;
-            slot = b - rr * n_slots;
-        } else {
-            slot = b / a.items_per_slot;
-            rr = b - slot * a.items_per_slot;
-        }
-#pragma unroll
-        for (int i = 1; i < 4; ++i)
-            if (i < a.n_var && rr >= a.r_begin[i]) vi = i;
-        it.net = slot / a.nb;
-        it.bb = slot - it.net * a.nb;
-        it.var = vi;
-        item_in_slot = rr;
-        const int r = rr - a.r_begin[vi], npos_v = a.var[vi].OH * a.var[vi].OW, R = a.r_cnt[vi];
-        const int base = npos_v / R, rem = npos_v - base * R;
-        it.p0 = r * base + min(r, rem);
-        it.np = base + (r < rem ? 1 : 0);
-    }
+#else
+    constexpr long long* prof = nullptr;
+    constexpr long long pt0 = 0, pw0 = 0;
+    (void)prof_arg;
+#endif
+    // the item: one 64-byte scalar load of the plan's table (convp_items.h), no division in front of the first copy
+    const auto dp = (const __attribute__((address_space(4))) u32x4*)(uintptr_t)(a.items + b);
+    const u32x4 d0 = dp[0], d1 = dp[1], d2 = dp[2], d3 = dp[3];
+    const int net = (int)d1.x, out_slot = (int)d1.y, vi = (int)d1.z, p0 = (int)d1.w, np = (int)d2.x, oh0 = (int)d2.y;
     const CVar& v = a.var[vi];
-    const int OW = v.OW, p0 = it.p0, np = it.np;
-    const int in_slot = (a.in_split > 0 ? (it.net >= a.in_split ? 1 : 0) : it.net) * a.nb + it.bb;
-    const int out_slot = it.net * a.nb + it.bb;
-    const unsigned long in_base = (unsigned long)a.in + (unsigned long)in_slot * a.in_slot;
-    const int oh0 = p0 / OW;
+    const unsigned long in_base = (unsigned long)a.in + ((unsigned long)d0.x | (unsigned long)d0.y << 32);
     // strips: input row r of this workgroup serves output columns [c0, c0 + ncol) of output row oh0 + r
-    int nx[CP_MAX_STRIPS], c0[CP_MAX_STRIPS];
+    int nx[CP_MAX_STRIPS], c0[CP_MAX_STRIPS], nc[CP_MAX_STRIPS];
     unsigned soff[CP_MAX_STRIPS];
     unsigned long sb[CP_MAX_STRIPS];
     {
+        const unsigned cw[2] = {d2.z, d2.w}, nw[2] = {d3.x, d3.y};
+        const long row_step = (long)a.S * a.row_bytes, col_step = (long)a.S * a.pix_bytes;
         unsigned accb = 0;
 #pragma unroll
         for (int r = 0; r < CP_MAX_STRIPS; ++r) {
-            const int row = oh0 + r;
-            const int lo = max(p0, row * OW), hi = min(p0 + np, (row + 1) * OW);
-            const int ncol = hi - lo;
-            c0[r] = lo - row * OW;
-            nx[r] = ncol > 0 ? (ncol - 1) * a.SX + NQ : 0;
+            c0[r] = (int)((r & 1) ? cw[r >> 1] >> 16 : cw[r >> 1] & 0xffffu);
+            nc[r] = (int)((r & 1) ? nw[r >> 1] >> 16 : nw[r >> 1] & 0xffffu);
+            nx[r] = nc[r] > 0 ? (nc[r] - 1) * a.SX + NQ : 0;
             soff[r] = accb;
             accb += (unsigned)nx[r] * BLKA;
-            sb[r] = in_base + (unsigned long)(row * a.S + v.in_off_h) * (unsigned long)a.row_bytes +
-                    (unsigned long)(c0[r] * a.S + v.in_off_w) * (unsigned long)a.pix_bytes;
+            sb[r] = in_base + (unsigned long)(r * row_step + (long)(c0[r] - c0[0]) * col_step);
         }
     }
-    // tiles of this wave: tile index wave + 4 i -> position j = idx / CT, channel tile ct = idx % CT (= wave % CT)
+    // tiles of this wave: tile index wave + 4 i -> position j = idx / CT, channel tile ct = idx % CT (= wave % CT);
+    // tpos = (output row << 16 | column) of the variant's grid, -1: no tile
     const int ct = wave % CT;
     unsigned abase[NT];
     int tpos[NT];
+    const int e0 = nc[0], e1 = e0 + nc[1], e2 = e1 + nc[2];  // positions of the item before strip 1, 2, 3
 #pragma unroll
     for (int i = 0; i < NT; ++i) {
-        const int j = (wave + 4 * i) / CT;
-        tpos[i] = j < np ? p0 + j : -1;
-        const int p = p0 + min(j, np - 1);
-        const int oh = p / OW, ow = p - oh * OW, r = oh - oh0;
+        const int j = (wave + 4 * i) / CT, jj = min(j, np - 1);
+        const int r = (jj >= e0 ? 1 : 0) + (jj >= e1 ? 1 : 0) + (jj >= e2 ? 1 : 0);
+        const int x = jj - (r == 0 ? 0 : r == 1 ? e0 : r == 2 ? e1 : e2);  // column inside strip r
         int c0r = c0[0];
         unsigned so = soff[0];
 #pragma unroll
@@ -122,12 +104,13 @@ __device__ __forceinline__ void cfwd_body(const CFwdArgs& a, unsigned stage_byte
             c0r = (r == s) ? c0[s] : c0r;
             so = (r == s) ? soff[s] : so;
         }
-        abase[i] = WB + so + (unsigned)((ow - c0r) * a.SX) * BLKA;
+        tpos[i] = j < np ? ((oh0 + r) << 16 | (c0r + x)) : -1;
+        abase[i] = WB + so + (unsigned)(x * a.SX) * BLKA;
     }
     const unsigned lo_tr = (8 * h + ((lane & 15) >> 2)) * 64 + (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2;
     const unsigned lane16 = lane * 16;
     const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)&lds[0];
-    const unsigned long wb0 = (unsigned long)a.wq + (unsigned long)it.net * a.wq_stride + (unsigned long)v.w_off;
+    const unsigned long wb0 = (unsigned long)a.wq + ((unsigned long)d0.z | (unsigned long)d0.w << 32);
     const int NSS = a.KH * a.NCC;
 
     auto stage_w = [&](int ss, unsigned buf, int first, int step) {  // the packed kernels of superstep ss
@@ -158,12 +141,12 @@ __device__ __forceinline__ void cfwd_body(const CFwdArgs& a, unsigned stage_byte
     const int co = ct * 32 + cl;
     float bias = 0.f;
     if (a.epilogue == 0)
-        bias = (it.net < a.n_first ? a.pbase[0] + (long)it.net * a.pstride : a.pbase[1] + (long)(it.net - a.n_first) * a.pstride)[a.b_off + co];
+        bias = (net < a.n_first ? a.pbase[0] + (long)net * a.pstride : a.pbase[1] + (long)(net - a.n_first) * a.pstride)[a.b_off + co];
     // data gradient: the ReLU mask = plane 0 of the forward activation at the output pixel, 2 KB per tile, copied into
     // LDS behind the stage buffers while the last superstep computes
     const unsigned mask_lds = mask_off + wave * (NT * 2048);
     auto tile_out = [&](int p, int& yh, int& yw) {
-        const int oh = p / OW, ow = p - oh * OW;
+        const int oh = p >> 16, ow = p & 0xffff;
         yh = oh * v.out_mul + v.out_add_h;
         yw = ow * v.out_mul + v.out_add_w;
     };
@@ -174,7 +157,11 @@ __device__ __forceinline__ void cfwd_body(const CFwdArgs& a, unsigned stage_byte
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
 
+#ifdef IDQN_DEBUG_KNOBS
     const long long pt1 = clock64();
+#else
+    constexpr long long pt1 = 0;
+#endif
     long long pwait = 0, pt2 = 0;
     if (loader) {
         // ---- loader waves: copy `ring - 1` supersteps ahead while the compute waves work ----------------------------
@@ -405,7 +392,7 @@ __device__ __forceinline__ void cfwd_body(const CFwdArgs& a, unsigned stage_byte
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         long long* pr = prof + (long)b * 8;
         pr[0] = pw0; pr[1] = pt1 - pt0; pr[2] = pt2 - pt1; pr[3] = pt3 - pt2; pr[4] = clock64() - pt3; pr[5] = pwait; pr[6] = wall_clock64();
-        pr[7] = it.np;
+        pr[7] = np;
     }
 }
 

@@ -26,10 +26,10 @@ __global__ __launch_bounds__(512) void k_cpair(CFwdArgs f, unsigned f_stage, int
     const int qf = n_f >> 3, rf = n_f & 7, fx = qf + (x < rf ? 1 : 0);
     if (!split_xcd) {
         const int v = xcd_contiguous_id();
-        if (v < n_f) cfwd_body<NPA, CT, NQ, NT>(f, f_stage, ring, mask_off, prof, v, n_f);
+        if (v < n_f) cfwd_body<NPA, CT, NQ, NT>(f, f_stage, ring, mask_off, prof, v);
         else cwgrad_body<WNPX, WCT, WNTW, WPG>(w, w_stage, MT, v - n_f);
     } else if (slot < fx) {
-        cfwd_body<NPA, CT, NQ, NT>(f, f_stage, ring, mask_off, prof, x * qf + min(x, rf) + slot, n_f);
+        cfwd_body<NPA, CT, NQ, NT>(f, f_stage, ring, mask_off, prof, x * qf + min(x, rf) + slot);
     } else {
         const int n_w = n - n_f, qn = n >> 3, rn = n & 7;
         // weight-gradient blocks of the XCDs before x: their block counts minus their data-gradient blocks

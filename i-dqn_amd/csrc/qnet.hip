@@ -35,6 +35,7 @@
 #include "dp_internal.h"
 #include "per_step_args.h"
 #include "per_group_kernels.h"
+#include "convp_items.h"
 
 namespace {
 
@@ -230,7 +231,8 @@ struct NetSet {
 // host-side plans of the plane conv launches: the work items of a launch depend only on geometry, net count and batch
 // blocks, so they are built once and kept on the device
 struct FwdPlan { int n_items = 0, NT = 0, ring = 2, items_per_slot = 0, r_begin[4] = {0, 0, 0, 0}, r_cnt[4] = {1, 1, 1, 1}; size_t stage = 0, lds = 0;
-                 int row_parts = 0, n_wg = 0; CItem* items_dev = nullptr; };  // row_parts > 0: a plan of the persistent kernel (convp_pp.hip), n_wg workgroups
+                 int row_parts = 0, n_wg = 0; CItem* items_dev = nullptr;  // row_parts > 0: a plan of the persistent kernel (convp_pp.hip), n_wg workgroups
+                 CFwdDesc* desc_dev = nullptr; };  // one-item plans: the item table (convp_items.h), made with the plan, handle-owned
 struct WgradPlan { int n_items = 0, n_chunks = 0, chunk_major = 0, MT = 0, PG = 0; size_t lds = 0; };
 
 // workspace of the i-IQN heads (iqn_kernels.h): V = 3K virtual nets x NB = N x nb blocks (fraction q of sample block s
@@ -1428,6 +1430,19 @@ int conv_args(idqn_handle_s* h, NetSet& s, int role, int nb, int target, CFwdArg
     a.row_bytes = gin->Wp * a.pix_bytes;
     a.out_slot = gout->block * 6; a.out_Wp = gout->Wp; a.out_lo_h = gout->lo_h; a.out_lo_w = gout->lo_w;
     a.out_W = gout->W; a.out_H = gout->H;
+    // The plan's item table: what it holds depends on the plan key (role and net set, nets, blocks, target) and the handle's
+    // geometry only -- offsets, no pointers -- so it is made once, with the plan (a debug-build plan override is another key:
+    // another plan, another table), and every later step only passes its address.
+    if (!pl->desc_dev) {
+        std::vector<CFwdDesc> tab((size_t)pl->n_items);
+        IDQN_REQUIRE(convp_fill_fwd_items(a, pl->n_items, tab.data()), "plane conv: role %d has an item its descriptor cannot hold", role);
+        CFwdDesc* dev = nullptr;
+        IDQN_HIP_CHECK(hipMalloc((void**)&dev, tab.size() * sizeof(CFwdDesc)));
+        h->owned.push_back((void*)dev);
+        IDQN_HIP_CHECK(hipMemcpy(dev, tab.data(), tab.size() * sizeof(CFwdDesc), hipMemcpyHostToDevice));
+        pl->desc_dev = dev;
+    }
+    a.items = pl->desc_dev;
     return IDQN_OK;
 }
 
@@ -3581,6 +3596,23 @@ extern "C" int idqn_iqn_act_host_many(idqn_handle_t h, int32_t which, const int3
     memcpy(h->many.pin + sizeof(IqnActManyBlock), states_host_pinned, (size_t)n * sb);
     return act_many_run(h, "idqn_iqn_act_host_many", n, sb, q_out_dev, actions_host_pinned, (hipStream_t)stream,
                         [&](hipStream_t qs, int32_t* mail_dev) { return iqn_act_many_chain(h, n, q_out_dev, mail_dev, qs); });
+}
+
+extern "C" int idqn_debug_conv_items(const int64_t* p, int32_t n_params, int32_t n_items, void* out_host) {
+    IDQN_REQUIRE(p && out_host && n_params == 38 && n_items >= 1, "idqn_debug_conv_items: 38 parameters, at least one item");
+    CFwdArgs a;
+    memset(&a, 0, sizeof(a));
+    a.items_per_slot = (int)p[0]; a.range_major = (int)p[1]; a.nb = (int)p[2]; a.n_var = (int)p[3]; a.in_split = (int)p[4];
+    a.S = (int)p[5]; a.row_bytes = (int)p[6]; a.pix_bytes = (int)p[7]; a.in_slot = p[8]; a.wq_stride = p[9];
+    IDQN_REQUIRE(a.nb >= 1 && a.n_var >= 1 && a.n_var <= 4, "idqn_debug_conv_items: %d blocks, %d variants", a.nb, a.n_var);
+    for (int v = 0; v < 4; ++v) {
+        const int64_t* q = p + 10 + 7 * v;
+        a.r_begin[v] = (int)q[0]; a.r_cnt[v] = (int)q[1]; a.var[v].OH = (int)q[2]; a.var[v].OW = (int)q[3];
+        a.var[v].in_off_h = (int)q[4]; a.var[v].in_off_w = (int)q[5]; a.var[v].w_off = q[6];
+        IDQN_REQUIRE(v >= a.n_var || (a.r_cnt[v] >= 1 && a.var[v].OH >= 1 && a.var[v].OW >= 1), "idqn_debug_conv_items: variant %d is empty", v);
+    }
+    IDQN_REQUIRE(convp_fill_fwd_items(a, n_items, (CFwdDesc*)out_host), "idqn_debug_conv_items: an item does not fit its descriptor");
+    return IDQN_OK;
 }
 
 extern "C" int idqn_debug_buffer(idqn_handle_t h, const char* name, void** ptr_dev, int64_t* nbytes) {

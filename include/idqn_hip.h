@@ -426,6 +426,13 @@ int idqn_group_act_host_fc(idqn_group_t group, int32_t which, const int32_t* mem
 
 /* Test / debug access to internal activation buffers by name (device pointer + byte size).        */
 int idqn_debug_buffer(idqn_handle_t h, const char* name, void** ptr_dev, int64_t* nbytes);
+
+/* Test access to the host code that builds the item table of a one-item plane conv launch (csrc/convp_items.h); no
+ * device call.  params = {items_per_slot, range_major, nb, n_var, in_split, S, row_bytes, pix_bytes, in_slot_bytes,
+ * wq_stride, then per variant (4 of them): r_begin, r_cnt, OH, OW, in_off_h, in_off_w, w_off} (38 values);
+ * out = n_items descriptors of 64 bytes: int64 in_off, int64 w_off, int32 net, out_slot, var, p0, np, oh0,
+ * uint16 c0[4], uint16 ncol[4], int32 batch block, int32 0.                                                        */
+int idqn_debug_conv_items(const int64_t* params, int32_t n_params, int32_t n_items, void* out_host);
 /* Mean duration (ms) and launch count of the dominant kernel over the IDQN_F_PROFILE calls since
  * the last read; synchronises the events it reads.  kernel_name: the dominant kernel.  For MLP
  * handles it is the kernel the LAST step launched, chosen per call and not at idqn_create, with the
