@@ -4,8 +4,8 @@ read once per process) and compared with the default.  Six switches, each a seco
   IDQN_STEP_GRAPH=1     the plain step replayed as a hipGraph                       -> bit-identical to the eager launches
   IDQN_ACT_POLL=0       acting result by copy + synchronisation                     -> the polled mailbox's greedy actions
   IDQN_CONV_PP=0        one work item per workgroup instead of the persistent conv kernel (csrc/convp_pp.hip) where a launch has
-                        several items per CU (B = 256)                              -> same losses / parameters within fp32 round-off
-                        (the items are cut differently, the sums inside a tile are the same)
+                        several items per CU (B = 256)                              -> bit-identical losses, parameters and actions
+                        (the items are cut differently; every 32 x 32 tile is summed in the same k order)
   IDQN_FC_PAR=0         the MLP step as k_fc_step_mfma + k_adam instead of the one-launch kernel (csrc/fc_par_kernels.h)
                                                                                     -> same within fp32 round-off
   IDQN_LOOP_OVERLAP=0   the trainer loop without the replay bookkeeping under the acting launch   -> bit-identical parameters
