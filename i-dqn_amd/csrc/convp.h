@@ -33,9 +33,12 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 #define CP_MAX_STRIPS 4  // input rows one workgroup's output positions may span
 
 // ---- forward / data-gradient launch ---------------------------------------------------------------------------
-struct CItem {  // one workgroup: np consecutive output positions (row-major over the variant's OH x OW) of one net
-    int net, bb, var, p0, np, pad0, pad1, pad2;
+struct CItem {  // one item of the persistent kernel: np consecutive output positions of ONE row of a variant of one net
+    int net, bb, var, p0, np;  // p0 = row * OW + col0 (row-major over the variant's OH x OW)
+    int row, col0;             // output row and first column
+    int pad2;
 };
+static_assert(sizeof(CItem) == 32, "CItem is read one item ahead with scalar loads: 32 bytes, this field order");
 struct CVar {  // one sub-convolution of a launch (forward: one; data gradient of a stride-S conv: S * S output parities)
     long w_off;              // bytes from the net's packed weights
     int in_off_h, in_off_w;  // padded input row / column read by output (0, 0), tap (0, 0)
@@ -235,7 +238,7 @@ int convp_fwd_max_nt(int CT);
 // persistent form for launches with several items per CU (convp_pp.hip): n_wg workgroups walk n_items items
 bool convp_pp_built(int NPA, int CT, int NQ, int NT);
 size_t convp_pp_epi_bytes(int NT, int epilogue, bool planes_out, bool f32_out);
-// items: device table of the n_items work items in launch order (row-aligned: pad0 = output row, pad1 = first column)
+// items: device table of the n_items work items in launch order (row-aligned: convp_items.h makes it)
 int convp_launch_fwd_pp(const CFwdArgs& a, int NPA, int CT, int NQ, int NT, int n_items, int n_wg, size_t stage_bytes, int ring,
                         size_t lds_bytes, hipStream_t q, const CItem* items, long long* prof = nullptr);
 

@@ -1,4 +1,5 @@
-// Plane-layout convolution, forward and data gradient: kernels and launcher (the workgroup body is convp_fwd_body.h).
+// Plane-layout convolution, forward and data gradient: kernels and launcher (the workgroup body is convp_fwd_body.h, a
+// schedule over the phases of convp_fwd_phases.h, which also has the LDS sizes used below).
 #include <algorithm>
 #include <cstdlib>
 
@@ -47,21 +48,22 @@ int launch_nt(const CFwdArgs& a, int NT, int n_items, size_t stage_bytes, int ri
 
 int convp_fwd_max_nt(int CT) { return CT == 1 ? 6 : 3; }
 
-// two stage buffers, behind them the data gradient's mask tiles (2 KB per tile and wave); the epilogue turns every tile
-// around in 10 KB per wave of the (then free) stage buffers
+// two stage buffers, behind them the data gradient's mask tiles (CF_MASK_TILE_BYTES per tile and wave); the epilogue turns
+// every tile around in cf_turn_bytes per wave of the (then free) stage buffers
+static size_t fwd_mask_bytes(int NT, int epilogue) { return epilogue == 1 ? (size_t)4 * NT * CF_MASK_TILE_BYTES : 0; }
 int convp_fwd_ring(size_t stage_bytes, int NT, int epilogue, size_t budget) {  // three stage buffers when they fit
     static const int forced = (0);
     if (forced == 2 || forced == 3) return forced;
-    return 3 * stage_bytes + (epilogue == 1 ? (size_t)4 * NT * 2048 : 0) <= budget ? 3 : 2;
+    return 3 * stage_bytes + fwd_mask_bytes(NT, epilogue) <= budget ? 3 : 2;
 }
 // LDS map: [ring stage buffers | ...] reused by the epilogue as [8 turn-around tiles | hand-off tiles]; the data gradient's
 // mask tiles sit behind whichever of the two is larger
 size_t convp_fwd_mask_off(size_t stage_bytes, int NT, int ring, bool planes_out, bool f32_out) {
-    const size_t rsz = (planes_out ? 6144 : 0) + (f32_out ? 4096 : 0), nh = NT - (NT + 1) / 2;
+    const size_t rsz = cf_turn_bytes(planes_out, f32_out), nh = NT - (NT + 1) / 2;
     return std::max(ring * stage_bytes, 8 * rsz + 4 * nh * 4096);
 }
 size_t convp_fwd_lds(size_t stage_bytes, int NT, int epilogue, int ring, bool planes_out, bool f32_out) {
-    return convp_fwd_mask_off(stage_bytes, NT, ring, planes_out, f32_out) + (epilogue == 1 ? (size_t)4 * NT * 2048 : 0);
+    return convp_fwd_mask_off(stage_bytes, NT, ring, planes_out, f32_out) + fwd_mask_bytes(NT, epilogue);
 }
 
 int convp_launch_fwd(const CFwdArgs& a, int NPA, int CT, int NQ, int NT, int n_items, size_t stage_bytes, int ring,

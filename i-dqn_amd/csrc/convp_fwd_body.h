@@ -1,4 +1,6 @@
-// Plane-layout convolution, forward and data gradient: the workgroup body (convp.h has the layouts and the arithmetic).
+// Plane-layout convolution, forward and data gradient: the one-item workgroup body (convp.h has the layouts and the
+// arithmetic; convp_fwd_phases.h the superstep's matrix work and the tile epilogue, which the persistent kernel of
+// convp_pp.hip restates -- this file is the one-item SCHEDULE over them: who loads, the ring hand-over, the epilogue's hand-off).
 // Kernels: convp_fwd.hip (one role per launch), convp_pair.hip (a data gradient beside a weight gradient).
 //   forward        architectures/dqn.py:42-52  flax nn.Conv (NHWC x HWIO, cross-correlation) + bias + ReLU
 //   data gradient  jax.value_and_grad, idqn.py:105: a stride-1 convolution over the zero-bordered dout planes with the
@@ -17,26 +19,9 @@
 // Orientation: A = activations (rows = samples), B = weights (columns = channels), so a lane ends up with 4 x 4
 // consecutive samples of ONE channel: plane rows are written as 8-byte pieces, the bias / mask is one value per lane.
 #pragma once
-#include "convp.h"
+#include "convp_fwd_phases.h"
 
 namespace {
-
-
-__device__ __forceinline__ bf16x8 frag_tr(const unsigned char* p) {
-    auto q = (__attribute__((address_space(3))) s16x4*)p;
-    s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(q);
-    s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(q + 32);  // 4 rows (256 B) on
-    return __builtin_shufflevector(__builtin_bit_cast(bf16x4, v0), __builtin_bit_cast(bf16x4, v1), 0, 1, 2, 3, 4, 5, 6, 7);
-}
-__device__ __forceinline__ s16x4 tr_half(const unsigned char* p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p);
-}
-__device__ __forceinline__ bf16x8 join8(s16x4 v0, s16x4 v1) {
-    return __builtin_shufflevector(__builtin_bit_cast(bf16x4, v0), __builtin_bit_cast(bf16x4, v1), 0, 1, 2, 3, 4, 5, 6, 7);
-}
-__device__ __forceinline__ bf16x8 frag_lin(const unsigned char* p) {
-    return *(const __attribute__((address_space(3))) bf16x8*)p;
-}
 
 // b = this workgroup's item index (already remapped XCD-contiguously): its entry of the item table a.items.
 template <int NPA, int CT, int NQ, int NT>
@@ -107,7 +92,7 @@ __device__ __forceinline__ void cfwd_body(const CFwdArgs& a, unsigned stage_byte
         tpos[i] = j < np ? ((oh0 + r) << 16 | (c0r + x)) : -1;
         abase[i] = WB + so + (unsigned)(x * a.SX) * BLKA;
     }
-    const unsigned lo_tr = (8 * h + ((lane & 15) >> 2)) * 64 + (16 * ((lane >> 4) & 1) + 4 * (lane & 3)) * 2;
+    const unsigned lo_tr = cf_lo_tr(lane);
     const unsigned lane16 = lane * 16;
     const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)&lds[0];
     const unsigned long wb0 = (unsigned long)a.wq + ((unsigned long)d0.z | (unsigned long)d0.w << 32);
@@ -140,16 +125,11 @@ __device__ __forceinline__ void cfwd_body(const CFwdArgs& a, unsigned stage_byte
     // epilogue operands that only depend on the item: requested now, used after the loop
     const int co = ct * 32 + cl;
     float bias = 0.f;
-    if (a.epilogue == 0)
-        bias = (net < a.n_first ? a.pbase[0] + (long)net * a.pstride : a.pbase[1] + (long)(net - a.n_first) * a.pstride)[a.b_off + co];
-    // data gradient: the ReLU mask = plane 0 of the forward activation at the output pixel, 2 KB per tile, copied into
-    // LDS behind the stage buffers while the last superstep computes
-    const unsigned mask_lds = mask_off + wave * (NT * 2048);
-    auto tile_out = [&](int p, int& yh, int& yw) {
-        const int oh = p >> 16, ow = p & 0xffff;
-        yh = oh * v.out_mul + v.out_add_h;
-        yw = ow * v.out_mul + v.out_add_w;
-    };
+    if (a.epilogue == 0) bias = cf_bias_row(a, net)[co];
+    // data gradient: the ReLU masks of this wave's tiles are copied into LDS behind the stage buffers while the last
+    // superstep computes
+    const unsigned mask_lds = mask_off + wave * (NT * CF_MASK_TILE_BYTES);
+    auto tile_out = [&](int p, int& yh, int& yw) { cf_out_pos(v, p >> 16, p & 0xffff, yh, yw); };
 
     f32x16 acc[NT];
 #pragma unroll
@@ -191,10 +171,7 @@ __device__ __forceinline__ void cfwd_body(const CFwdArgs& a, unsigned stage_byte
                     if (tpos[i] < 0) continue;
                     int yh, yw;
                     tile_out(tpos[i], yh, yw);
-                    const unsigned long msrc = (unsigned long)a.mask3 + (unsigned long)out_slot * a.mask_slot +
-                        ((unsigned long)((yh + a.mask_lo_h) * a.mask_Wp + (yw + a.mask_lo_w)) * (3UL * a.mask_C) + ct * 32) * 64;
-                    dma16(lane16, msrc, lds0 + mask_lds + i * 2048);
-                    dma16(lane16, msrc + 1024, lds0 + mask_lds + i * 2048 + 1024);
+                    cf_mask_copy(lane16, cf_mask_src(a, out_slot, yh, yw, ct), lds0 + mask_lds + i * CF_MASK_TILE_BYTES);
                 }
             }
         }
@@ -205,8 +182,6 @@ __device__ __forceinline__ void cfwd_body(const CFwdArgs& a, unsigned stage_byte
         }
     }
     // ---- compute waves -------------------------------------------------------------------------------------------
-    // Fragment reads of tile-step u + 1 are issued one per gap BETWEEN the MFMAs of tile-step u (the wave issues an MFMA,
-    // is free for the ~32 cycles it runs, and blocks at the next, dependent one): sched_barrier pins that order.
     int cbuf = 0;
     for (int ss = 0; ss < NSS && !loader; ++ss) {
         const unsigned cur_off = cbuf * stage_bytes;
@@ -215,81 +190,16 @@ __device__ __forceinline__ void cfwd_body(const CFwdArgs& a, unsigned stage_byte
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         if (prof) { const long long now = clock64(); pwait += now - pw; if (ss == 0) pt2 = now; }
-        const unsigned char* cur = lds + cur_off;
-        // Fragments: the activation halves of tile-step u + 2 are requested in the gaps between the MFMAs of tile-step u
-        // (a ring of three register sets), the weight planes of tap q + 1 during the last-but-one tile-step of tap q:
-        // every ds_read has at least one whole tile-step (~190 cycles) to return before an MFMA waits for it.
-        constexpr int U = NQ * NT, NM = NPA == 3 ? 6 : 3, WSTEP = NT >= 2 ? NT - 2 : 0;
-        bf16x8 wf[2][3];
-        s16x4 ah[3][NPA][2];
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl) wf[0][pl] = frag_lin(cur + (ct * 3 + pl) * 1024 + lane16);
-#pragma unroll
-        for (int u0 = 0; u0 < 2 && u0 < U; ++u0)
-#pragma unroll
-            for (int pl = 0; pl < NPA; ++pl) {
-                const unsigned char* ap = cur + abase[u0 % NT] + (u0 / NT) * BLKA + pl * 1024 + lo_tr;
-                ah[u0][pl][0] = tr_half(ap);
-                ah[u0][pl][1] = tr_half(ap + 256);
-            }
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-#pragma unroll
-            for (int i = 0; i < NT; ++i) {
-                const int u = q * NT + i;
-                const bool next_w = (i == WSTEP && q + 1 < NQ), next_a = (u + 2 < U);
-                const int qn = (u + 2) / NT, in_ = (u + 2) % NT;
-                const unsigned char* an = cur + abase[next_a ? in_ : 0] + qn * BLKA + lo_tr;
-                const unsigned char* wn = cur + (((q + 1) * CT + ct) * 3) * 1024 + lane16;
-                bf16x8 A[NPA];
-#pragma unroll
-                for (int pl = 0; pl < NPA; ++pl) A[pl] = join8(ah[u % 3][pl][0], ah[u % 3][pl][1]);
-                const bf16x8* W = wf[q & 1];
-                __builtin_amdgcn_sched_barrier(0);
-#define CF_GAP(m)                                                                                              \
-    {                                                                                                          \
-        __builtin_amdgcn_sched_barrier(0);                                                                     \
-        if (next_a && (m) < 2 * NPA) ah[(u + 2) % 3][((m) / 2) % NPA][(m) % 2] = tr_half(an + ((m) / 2) * 1024 + ((m) % 2) * 256); \
-        if (next_w && (m) < 3) wf[(q + 1) & 1][(m) < 3 ? (m) : 0] = frag_lin(wn + (m) * 1024);                 \
-        __builtin_amdgcn_sched_barrier(0);                                                                     \
-    }
-                if (NPA == 3) {  // smallest terms first
-                    acc[i] = mfma_bf16(A[2], W[0], acc[i]);
-                    CF_GAP(0)
-                    acc[i] = mfma_bf16(A[0], W[2], acc[i]);
-                    CF_GAP(1)
-                    acc[i] = mfma_bf16(A[1], W[1], acc[i]);
-                    CF_GAP(2)
-                    acc[i] = mfma_bf16(A[1], W[0], acc[i]);
-                    CF_GAP(3)
-                    acc[i] = mfma_bf16(A[0], W[1], acc[i]);
-                    CF_GAP(4)
-                    acc[i] = mfma_bf16(A[0], W[0], acc[i]);
-                    CF_GAP(5)
-                } else {
-                    acc[i] = mfma_bf16(A[0], W[2], acc[i]);
-                    CF_GAP(0)
-                    acc[i] = mfma_bf16(A[0], W[1], acc[i]);
-                    CF_GAP(1)
-                    acc[i] = mfma_bf16(A[0], W[0], acc[i]);
-                    CF_GAP(2)
-                }
-#undef CF_GAP
-                (void)NM;
-            }
-        }
+        cf_superstep<NPA, CT, NQ, NT>(lds + cur_off, abase, ct, lane16, lo_tr, acc);
     }
 
     const long long pt3 = prof ? clock64() : 0;
-    // ---- epilogue: lane = channel co, registers = samples (r & 3) + 8 (r >> 2) + 4 h -------------------------------
-    // A lane's values of a tile are 8-byte pieces of 64-byte rows; written straight to HBM every store instruction would
-    // touch 32 rows (measured: ~330 cycles each).  Each wave therefore turns a tile around in LDS (the stage buffers
-    // are free now) and stores whole 1 KiB runs: 16 rows of a plane, or 8 rows of the f32 copy, per instruction.
+    // ---- epilogue: every tile is turned around in LDS (the stage buffers are free now; convp_fwd_phases.h has the why) ----
     // The work (bias / mask, the 3-way bf16 split: ~120 VALU instructions per tile) is shared with the loader waves, idle
     // by now: compute wave w keeps its first KEEP tiles and hands the others, as raw accumulators through LDS, to loader
     // wave w + 4, which has the same tile table.
     constexpr int KEEP = (NT + 1) / 2, NH = NT - KEEP;
-    const unsigned r_f32 = a.out3 ? 6144 : 0, rsz = r_f32 + (a.out_f32 ? 4096 : 0);
+    const unsigned rsz = cf_turn_bytes(a.out3 != nullptr, a.out_f32 != nullptr);
     unsigned char* R = lds + wave8 * rsz;                       // this wave's turn-around tile: [3 planes x 2 KB][f32 4 KB]
     unsigned char* H = lds + 8 * rsz + wave * (NH * 4096);      // hand-off tiles of compute wave `wave`
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -306,9 +216,7 @@ __device__ __forceinline__ void cfwd_body(const CFwdArgs& a, unsigned stage_byte
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
     }
-    const unsigned wsw = (cl >> 1) & 3;                                      // plane rows: 16-byte slot ^ (row >> 1) & 3
-    const unsigned rsw = (lane * 16) ^ ((((unsigned)lane >> 3) & 3) << 4);   // = row (lane >> 2), slot (lane & 3) ^ swizzle
-    const unsigned fsw = (lane * 16) ^ ((((unsigned)lane >> 3) & 7) << 4);   // f32 rows: slot (lane & 7) ^ (row & 7)
+    const CfSwizzle sw = cf_swizzle(lane);
 #pragma unroll
     for (int i = 0; i < NT; ++i) {
         if (tpos[i] < 0 || loader != (i >= KEEP)) continue;  // wave-uniform
@@ -325,68 +233,10 @@ __device__ __forceinline__ void cfwd_body(const CFwdArgs& a, unsigned stage_byte
         int yh, yw;
         tile_out(tpos[i], yh, yw);
         float val[16];
-        if (a.epilogue == 0) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) val[r] = fmaxf(av[r] + bias, 0.f);
-        } else {
-            const unsigned char* M = lds + mask_lds + i * 2048 + cl * 64 + 8 * h;
-            float s = 0.f;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const u32x2 mk = *LDS_PTR(const u32x2, M + 16 * g);
-                const float m0 = __uint_as_float(mk.x << 16), m1 = __uint_as_float(mk.x & 0xffff0000u);
-                const float m2 = __uint_as_float(mk.y << 16), m3 = __uint_as_float(mk.y & 0xffff0000u);
-                val[4 * g + 0] = m0 > 0.f ? av[4 * g + 0] : 0.f;
-                val[4 * g + 1] = m1 > 0.f ? av[4 * g + 1] : 0.f;
-                val[4 * g + 2] = m2 > 0.f ? av[4 * g + 2] : 0.f;
-                val[4 * g + 3] = m3 > 0.f ? av[4 * g + 3] : 0.f;
-            }
-            if (a.pb) {  // sum over the 32 samples, fixed order: registers, then the two half-waves
-#pragma unroll
-                for (int r = 0; r < 16; ++r) s += val[r];
-                s += __shfl_xor(s, 32);
-                if (h == 0) a.pb[((long)out_slot * (a.out_H * a.out_W) + (long)yh * a.out_W + yw) * a.CO + co] = s;
-            }
-        }
-        if (a.out3) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                unsigned q0a, q1a, q2a, q0b, q1b, q2b;
-                split3_pk(val[4 * g + 0], val[4 * g + 1], q0a, q1a, q2a);
-                split3_pk(val[4 * g + 2], val[4 * g + 3], q0b, q1b, q2b);
-                unsigned char* wp = R + cl * 64 + ((g ^ wsw) * 16) + 8 * h;
-                *LDS_PTR(u32x2, wp) = (u32x2){q0a, q0b};
-                *LDS_PTR(u32x2, wp + 2048) = (u32x2){q1a, q1b};
-                *LDS_PTR(u32x2, wp + 4096) = (u32x2){q2a, q2b};
-            }
-        }
-        if (a.out_f32) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-                *LDS_PTR(f32x4, R + r_f32 + cl * 128 + (((2 * g + h) ^ (cl & 7)) * 16)) =
-                    (f32x4){val[4 * g], val[4 * g + 1], val[4 * g + 2], val[4 * g + 3]};
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // same wave, LDS is in order: its writes are visible to its reads
-        if (a.out3) {
-            unsigned char* O = (unsigned char*)a.out3 + (unsigned long)out_slot * a.out_slot +
-                               ((unsigned long)((yh + a.out_lo_h) * a.out_Wp + (yw + a.out_lo_w)) * (3UL * a.CO) + ct * 32) * 64 + lane16;
-#pragma unroll
-            for (int pl = 0; pl < 3; ++pl)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const u32x4 x = *LDS_PTR(const u32x4, R + pl * 2048 + j * 1024 + rsw);
-                    *reinterpret_cast<u32x4*>(O + (unsigned long)pl * a.CO * 64 + j * 1024) = x;
-                }
-        }
-        if (a.out_f32) {
-            float* F = a.out_f32 + (long)out_slot * a.f32_slot + (((long)yh * a.f32_W + yw) * a.CO + ct * 32) * 32 + lane * 4;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const f32x4 x = *LDS_PTR(const f32x4, R + r_f32 + j * 1024 + fsw);
-                *reinterpret_cast<f32x4*>(F + j * 256) = x;
-            }
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the tile has left LDS before the next one overwrites it
+        cf_tile_values(a, av, bias, lds + mask_lds + i * CF_MASK_TILE_BYTES, cl, h, val);
+        if (a.epilogue == 1 && a.pb) cf_bias_grad_sum(a, val, out_slot, yh, yw, co, h);
+        cf_tile_to_lds(a, val, R, sw, cl, h);
+        cf_tile_store(a, R, sw, out_slot, yh, yw, ct, lane);
     }
     if (prof && t == 0) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

@@ -1,6 +1,12 @@
 // Plane-layout convolution, forward and data gradient, PERSISTENT form for launches with several items per CU
 // (B >= 64 sample blocks or many heads: BASELINE configs 4 / 5).  Same arithmetic, operands, layouts and work items as
 // k_cfwd (convp_fwd_body.h; architectures/dqn.py:42-52, idqn.py:105) -- what changes is who does what, when.
+// Shared with k_cfwd through convp_fwd_phases.h: the fragment helpers, the LDS sizes, the per-tile store counts of the vmcnt
+// bookkeeping, and (convp_items.h) the launch order of the item table.  The superstep's matrix work, the tile epilogue and
+// the operand addresses are still TYPED HERE, equal to cf_superstep / cf_tile_* / cf_mask_src / cf_bias_row of that header
+// and to be kept so by hand: calling the shared functions gives the same bytes but cost +0.9 % per step at B = 256 and
+// +0.8 % at K = 64 (the superstep alone and the epilogue alone each did, profiles/conv_phases_refactor.json), so this
+// kernel keeps the text its timing was tuned on; its assembly is the one it had before the header existed.
 //
 // Why (profiles/r6_cprof_b256.txt, B = 256): a one-item workgroup spends 1.5 k cycles deriving its tables, 5.5-7.5 k waiting
 // for its first two stages (the latency of a cold fill, not its bytes), 14-28 k in the superstep loop and 3-8 k in the
@@ -25,7 +31,7 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "convp_fwd_body.h"
+#include "convp_fwd_phases.h"
 
 namespace {
 
@@ -68,8 +74,8 @@ __device__ __forceinline__ void cfwd_pp_body(const CFwdArgs& a, const unsigned s
     const int NSS = a.KH * a.NCC, ahead = ring - 1;
     // LDS behind the ring, one slot per wave TRIPLE (w, w + 4, w + 8): only the one in its epilogue role uses it
     //   4 x [turn-around tile rsz (the bias row lands in its first KB before the first tile)][ReLU masks NT x 2 KB (data gradient)]
-    const unsigned r_f32 = a.out3 ? 6144 : 0, rsz = r_f32 + (a.out_f32 ? 4096 : 0);
-    const unsigned slot_bytes = rsz + (a.epilogue == 1 ? NT * 2048 : 0);
+    const unsigned r_f32 = a.out3 ? CF_TURN_PLANES_BYTES : 0, rsz = r_f32 + (a.out_f32 ? CF_TURN_F32_BYTES : 0);
+    const unsigned slot_bytes = rsz + (a.epilogue == 1 ? NT * CF_MASK_TILE_BYTES : 0);
     const unsigned R_off = epi_off + wave * slot_bytes, mask_off = R_off + rsz;
 
     // ---- this workgroup's items: XCD x (= blockIdx % 8) walks a contiguous slice of the items, its workgroups take
@@ -89,7 +95,7 @@ __device__ __forceinline__ void cfwd_pp_body(const CFwdArgs& a, const unsigned s
         const CVar& v = a.var[it.var];
         const int in_slot = (a.in_split > 0 ? (it.net >= a.in_split ? 1 : 0) : it.net) * a.nb + it.bb;
         const unsigned long in_base = (unsigned long)a.in + (unsigned long)in_slot * a.in_slot;
-        const int row = it.pad0, c0 = it.pad1;  // output row and first column of the item
+        const int row = it.row, c0 = it.col0;  // output row and first column of the item
         S.nx = (it.np - 1) * a.SX + NQ;
         S.sb = in_base + (unsigned long)(row * a.S + v.in_off_h) * (unsigned long)a.row_bytes +
                (unsigned long)(c0 * a.S + v.in_off_w) * (unsigned long)a.pix_bytes;
@@ -129,7 +135,8 @@ __device__ __forceinline__ void cfwd_pp_body(const CFwdArgs& a, const unsigned s
     };
 
     // ---- the epilogue of one tile in two slices: A = bias / mask, 3-way split, into the wave's turn-around tile;
-    // B = whole 1 KiB runs out of it to HBM (convp_fwd_body.h has the why of the turn-around and its swizzles)
+    // B = whole 1 KiB runs out of it to HBM (convp_fwd_phases.h has the why of the turn-around and its swizzles; its
+    // cf_tile_values / cf_bias_grad_sum / cf_tile_to_lds / cf_tile_store are this text, their store counts what vm_seq adds)
     const unsigned wsw = (cl >> 1) & 3;
     const unsigned rsw = (lane * 16) ^ ((((unsigned)lane >> 3) & 3) << 4);
     const unsigned fsw = (lane * 16) ^ ((((unsigned)lane >> 3) & 7) << 4);
@@ -147,7 +154,7 @@ __device__ __forceinline__ void cfwd_pp_body(const CFwdArgs& a, const unsigned s
 #pragma unroll
             for (int r = 0; r < 16; ++r) val[r] = fmaxf(av[r] + bias, 0.f);
         } else {
-            const unsigned char* M = lds + mask_off + i * 2048 + cl * 64 + 8 * h;
+            const unsigned char* M = lds + mask_off + i * CF_MASK_TILE_BYTES + cl * 64 + 8 * h;
             float s = 0.f;
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
@@ -166,7 +173,7 @@ __device__ __forceinline__ void cfwd_pp_body(const CFwdArgs& a, const unsigned s
                 for (int r = 0; r < 16; ++r) s += val[r];
                 s += __shfl_xor(s, 32);
                 if (h == 0) a.pb[((long)out_slot * (a.out_H * a.out_W) + (long)yh * a.out_W + yw) * a.CO + co] = s;
-                ++vm_seq;
+                vm_seq += CF_PB_STORES;
             }
         }
         if (a.out3) {
@@ -202,7 +209,7 @@ __device__ __forceinline__ void cfwd_pp_body(const CFwdArgs& a, const unsigned s
                     const u32x4 x = *LDS_PTR(const u32x4, Rt + pl * 2048 + j * 1024 + rsw);
                     *reinterpret_cast<u32x4*>(O + (unsigned long)pl * a.CO * 64 + j * 1024) = x;
                 }
-            vm_seq += 6;
+            vm_seq += CF_PLANE_STORES;
         }
         if (a.out_f32) {
             float* F = a.out_f32 + (long)out_slot * a.f32_slot + (((long)yh * a.f32_W + yw) * a.CO + ct * 32) * 32 + lane * 4;
@@ -211,7 +218,7 @@ __device__ __forceinline__ void cfwd_pp_body(const CFwdArgs& a, const unsigned s
                 const f32x4 x = *LDS_PTR(const f32x4, Rt + r_f32 + j * 1024 + fsw);
                 *reinterpret_cast<f32x4*>(F + j * 256) = x;
             }
-            vm_seq += 4;
+            vm_seq += CF_F32_STORES;
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the tile has left LDS before the next one overwrites it
     };
@@ -235,9 +242,9 @@ __device__ __forceinline__ void cfwd_pp_body(const CFwdArgs& a, const unsigned s
                 tile_yx(E.tpos[i], E.var, yh, yw);
                 const unsigned long msrc = (unsigned long)a.mask3 + (unsigned long)E.out_slot * a.mask_slot +
                     ((unsigned long)((yh + a.mask_lo_h) * a.mask_Wp + (yw + a.mask_lo_w)) * (3UL * a.mask_C) + ct * 32) * 64;
-                dma16(lane16, msrc, lds0 + mask_off + i * 2048);
-                dma16(lane16, msrc + 1024, lds0 + mask_off + i * 2048 + 1024);
-                vm_seq += 2;
+                dma16(lane16, msrc, lds0 + mask_off + i * CF_MASK_TILE_BYTES);
+                dma16(lane16, msrc + 1024, lds0 + mask_off + i * CF_MASK_TILE_BYTES + 1024);
+                vm_seq += CF_MASK_COPIES;
             }
         }
     };
@@ -255,8 +262,8 @@ __device__ __forceinline__ void cfwd_pp_body(const CFwdArgs& a, const unsigned s
         CItem it;
         it.net = __builtin_amdgcn_readfirstlane(p->net); it.bb = __builtin_amdgcn_readfirstlane(p->bb);
         it.var = __builtin_amdgcn_readfirstlane(p->var); it.p0 = __builtin_amdgcn_readfirstlane(p->p0);
-        it.np = __builtin_amdgcn_readfirstlane(p->np); it.pad0 = __builtin_amdgcn_readfirstlane(p->pad0);
-        it.pad1 = __builtin_amdgcn_readfirstlane(p->pad1); it.pad2 = 0;
+        it.np = __builtin_amdgcn_readfirstlane(p->np); it.row = __builtin_amdgcn_readfirstlane(p->row);
+        it.col0 = __builtin_amdgcn_readfirstlane(p->col0); it.pad2 = 0;
         return it;
     };
 
@@ -292,7 +299,7 @@ __device__ __forceinline__ void cfwd_pp_body(const CFwdArgs& a, const unsigned s
                 rec0 = rec1; rec1 = -1;
                 const unsigned char* cur = lds + cb * stage_bytes;
                 cb = cb + 1 == ring ? 0 : cb + 1;
-                // (fragment schedule of k_cfwd: activation halves of tile-step u + 2 and the weight planes of tap q + 1 are
+                // (cf_superstep of convp_fwd_phases.h, typed out: activation halves of tile-step u + 2 and the weight planes of tap q + 1 are
                 // requested in the gaps between the MFMAs of tile-step u.  Moving the barrier in front of the last two tile-steps
                 // and requesting the next stage's first fragments under them -- no drain / refill of the matrix pipe at the
                 // barrier -- was built and measured: same duration, 10-40 more registers, profiles/r6_pp_phases.txt)
@@ -500,7 +507,7 @@ bool convp_pp_built(int NPA, int CT, int NQ, int NT) {
 }
 // LDS behind the ring: one slot per wave triple (turn-around tile, the data gradient's masks)
 size_t convp_pp_epi_bytes(int NT, int epilogue, bool planes_out, bool f32_out) {
-    return 4 * ((planes_out ? 6144 : 0) + (f32_out ? 4096 : 0) + (epilogue == 1 ? (size_t)NT * 2048 : 0));
+    return 4 * (cf_turn_bytes(planes_out, f32_out) + (epilogue == 1 ? (size_t)NT * CF_MASK_TILE_BYTES : 0));
 }
 
 int convp_launch_fwd_pp(const CFwdArgs& a, int NPA, int CT, int NQ, int NT, int n_items, int n_wg, size_t stage_bytes, int ring,

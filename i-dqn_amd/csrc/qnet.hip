@@ -35,6 +35,7 @@
 #include "dp_internal.h"
 #include "per_step_args.h"
 #include "per_group_kernels.h"
+#include "convp_fwd_phases.h"
 #include "convp_items.h"
 
 namespace {
@@ -1102,8 +1103,7 @@ int plan_fwd_target(int role, int n_nets, int nb, const RoleGeom& g, int target,
     long npos_total = 0;
     for (int v = 0; v < g.n_var; ++v) npos_total += (long)g.var[v].OH * g.var[v].OW;
     const int per_slot = std::max(1, target / (n_nets * nb));
-    std::vector<CItem> items;
-    int np_all = 0;
+    int n_items = 0, np_all = 0;
     long stage_max = 0;
     // ranges per variant: proportional to its positions, rounded DOWN (one workgroup more than CUs would run alone after
     // all the others), leftovers to the variants with the most positions per range
@@ -1130,7 +1130,7 @@ int plan_fwd_target(int role, int n_nets, int nb, const RoleGeom& g, int target,
         for (;; ++R) {
             const int np = (npos + R - 1) / R;
             bool ok = (np * g.CT + 3) / 4 <= nt_max;
-            const long masks = role >= 3 ? 4L * ((np * g.CT + 3) / 4) * 2048 : 0;  // the data gradient's mask tiles
+            const long masks = role >= 3 ? 4L * ((np * g.CT + 3) / 4) * CF_MASK_TILE_BYTES : 0;  // the data gradient's mask tiles
             for (int r = 0, p0 = 0; ok && r < R; ++r) {
                 const int n = npos / R + (r < npos % R ? 1 : 0);
                 int rows;
@@ -1145,10 +1145,7 @@ int plan_fwd_target(int role, int n_nets, int nb, const RoleGeom& g, int target,
                 for (int r = 0, p0 = 0; r < R; ++r) {
                     const int cnt = npos / R + (r < npos % R ? 1 : 0);
                     if (cnt == 0) continue;
-                    CItem it;
-                    memset(&it, 0, sizeof(it));
-                    it.net = n; it.bb = bb; it.var = v; it.p0 = p0; it.np = cnt;
-                    items.push_back(it);
+                    ++n_items;
                     int rows;
                     stage_max = std::max(stage_max, fwd_stage_bytes(g, OW, p0, cnt, &rows));
                     IDQN_REQUIRE(rows <= CP_MAX_STRIPS, "plane conv: %d positions span %d rows", cnt, rows);
@@ -1159,7 +1156,7 @@ int plan_fwd_target(int role, int n_nets, int nb, const RoleGeom& g, int target,
     // The kernel derives item b arithmetically: slot = b / items_per_slot (net-major: consecutive workgroups, which the
     // XCD-contiguous remap keeps on one XCD, share a net's weights), then variant and balanced range inside the slot.
     pl = FwdPlan();
-    pl.n_items = (int)items.size();
+    pl.n_items = n_items;
     for (int v = 0; v < g.n_var; ++v) {
         pl.r_begin[v] = pl.items_per_slot;
         pl.r_cnt[v] = Rv[v];
@@ -1269,23 +1266,13 @@ int plan_fwd_pp(idqn_handle_s* h, int role, int n_nets, int nb, const RoleGeom& 
         if (best.n_items == 0 || cost < best_cost) { best = pl; best_cost = cost; }
     }
     if (best.n_items > 0) {
-        // the item table, in launch order: index b -> (slot, range) as the one-item kernels derive it (net-major, or range-major
-        // where the nets share their input), range -> (variant, output row, column part)
+        // the item table, in the launch order of the one-item kernels (convp_items.h)
+        CFwdArgs ta;
+        memset(&ta, 0, sizeof(ta));
+        ta.items_per_slot = best.items_per_slot; ta.row_parts = best.row_parts; ta.range_major = role == 0; ta.nb = nb; ta.n_var = g.n_var;
+        for (int v = 0; v < g.n_var; ++v) { ta.r_begin[v] = best.r_begin[v]; ta.r_cnt[v] = best.r_cnt[v]; ta.var[v] = g.var[v]; }
         std::vector<CItem> tab((size_t)best.n_items);
-        const int n_slots = n_nets * nb;
-        for (int b = 0; b < best.n_items; ++b) {
-            const bool range_major = role == 0;
-            const int rr = range_major ? b / n_slots : b % best.items_per_slot, slot = range_major ? b % n_slots : b / best.items_per_slot;
-            int vi = 0;
-            for (int i = 1; i < g.n_var; ++i) if (rr >= best.r_begin[i]) vi = i;
-            const int r = rr - best.r_begin[vi], OW = g.var[vi].OW;
-            const int row = r / best.row_parts, part = r % best.row_parts, base = OW / best.row_parts, rem = OW % best.row_parts;
-            CItem& it = tab[b];
-            memset(&it, 0, sizeof(it));
-            it.net = slot / nb; it.bb = slot % nb; it.var = vi;
-            it.pad0 = row; it.pad1 = part * base + std::min(part, rem);
-            it.p0 = row * OW + it.pad1; it.np = base + (part < rem ? 1 : 0);
-        }
+        IDQN_REQUIRE(convp_fill_pp_items(ta, best.n_items, tab.data()), "persistent plane conv: role %d ranges are no row cut", role);
         IDQN_HIP_CHECK(hipMalloc((void**)&best.items_dev, tab.size() * sizeof(CItem)));
         h->owned.push_back((void*)best.items_dev);
         IDQN_HIP_CHECK(hipMemcpy(best.items_dev, tab.data(), tab.size() * sizeof(CItem), hipMemcpyHostToDevice));
