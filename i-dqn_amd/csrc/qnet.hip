@@ -440,6 +440,18 @@ void tl_mark(idqn_handle_s* h, hipStream_t q, const char* name) {
     h->tl_name[h->tl_used++] = name;
 }
 
+// the timeline is on for a call made with IDQN_F_PROFILE_ALL (its events are made on the first such call); the start marker
+int tl_begin(idqn_handle_s* h, uint32_t flags, hipStream_t q) {
+    h->tl_on = (flags & IDQN_F_PROFILE_ALL) != 0;
+    if (h->tl_on && h->tl_ev.empty()) {
+        h->tl_ev.resize(2048);
+        h->tl_name.resize(2048);
+        for (auto& e : h->tl_ev) IDQN_HIP_CHECK(hipEventCreate(&e));
+    }
+    tl_mark(h, q, nullptr);
+    return IDQN_OK;
+}
+
 // The online nets' Dense_0 kernels are streamed three times per step (forward; fused update: read and written).  While they fit the
 // 256 MB memory-side cache beside the step's other traffic -- K * F * J * 4 <= 84 MB: K <= 5 at the Nature width -- the forward reads
 // them and the update stores them with the default policy, so that part of them is found on chip again; everything read or written
@@ -2151,13 +2163,7 @@ extern "C" int idqn_learn_on_batch(idqn_handle_t h, const void* state_dev, const
     const bool grads_only = (flags & IDQN_F_GRADS_ONLY) || stop0 || stopb, profile = flags & IDQN_F_PROFILE;
     IDQN_REQUIRE(!(stop0 || stopb) || h->cfg.arch == IDQN_ARCH_CNN, "the IDQN_F_STOP_* flags belong to the cnn path");
     h->pend_B = 0; h->pend_stage = 0;
-    h->tl_on = (flags & IDQN_F_PROFILE_ALL) != 0;
-    if (h->tl_on && h->tl_ev.empty()) {
-        h->tl_ev.resize(2048);
-        h->tl_name.resize(2048);
-        for (auto& e : h->tl_ev) IDQN_HIP_CHECK(hipEventCreate(&e));
-    }
-    tl_mark(h, q, nullptr);
+    if (const int rc = tl_begin(h, flags, q)) return rc;
     int rc;
     if (h->gc.on) {
         IDQN_REQUIRE(!(stop0 || stopb), "the IDQN_F_STOP_* flags belong to the MFMA cnn path");
@@ -2249,6 +2255,7 @@ extern "C" int idqn_learn_on_batch(idqn_handle_t h, const void* state_dev, const
             IDQN_HIP_CHECK(hipEventRecord(h->ev[h->ev_used + 1], q));
             h->ev_used += 2;
         }
+        tl_mark(h, q, h->dominant);
         IDQN_HIP_CHECK(hipGetLastError());
         if (!grads_only && !par && (rc = launch_adam(h, 0, h->L.head_stride, 0, 0, false, q))) return rc;
     }
@@ -2502,11 +2509,15 @@ extern "C" int idqn_learn_on_replay_fc_dev(idqn_handle_t h, const uint8_t* frame
                               stack, batch_mean_divisor, flags, stream);
 }
 
-// The handle's host-argument staging ring (idqn_learn_steps_on_replay_fc's slots, idqn_per_learn_on_replay's uniforms): `bytes`
+// The handle's host-argument staging ring (idqn_learn_steps_on_replay_fc's slots, the uniforms of idqn_per_learn_on_replay and
+// idqn_per_learn_steps_on_replay): `bytes`
 // <= STEPS_BLOCK_BYTES of ordinary host memory are copied into the next pinned block and their upload into the block's device
 // twin, h->steps_dev[*blk], is enqueued on q.  A block is rewritten only after the event steps_stage_guard recorded behind the
 // launch that read it has passed, so back-to-back calls need no synchronisation.
-static constexpr size_t STEPS_BLOCK_BYTES = (size_t)IDQN_MAX_STEPS_PER_CALL * RPS_PAR_SLOTS * 4;
+// A block holds the largest of them: idqn_per_learn_steps_on_replay's IDQN_MAX_STEPS_PER_CALL x PER_STEP_MAX_N float64 uniforms.
+static constexpr size_t STEPS_SLOTS_BYTES = (size_t)IDQN_MAX_STEPS_PER_CALL * RPS_PAR_SLOTS * 4;  // the slots of one idqn_learn_steps_on_replay_fc call
+static constexpr size_t STEPS_BLOCK_BYTES = (size_t)IDQN_MAX_STEPS_PER_CALL * PER_STEP_MAX_N * 8;
+static_assert(STEPS_BLOCK_BYTES >= STEPS_SLOTS_BYTES, "the slots fit a block too");
 static int steps_stage(idqn_handle_t h, const void* host, size_t bytes, hipStream_t q, int* blk_out) {
     const int blk = h->steps_next;
     if (!h->steps_pin[blk]) {
@@ -2662,6 +2673,81 @@ extern "C" int idqn_per_learn_on_replay(idqn_handle_t h, const idqn_per_step_t* 
                           per->alpha, per->priorities_dev, per->max_priority_dev, per->tree_scratch_dev, stream);
 }
 
+// n_steps consecutive prioritized learner steps on the frame ring as ONE C call (include/idqn_hip.h).  Between two steps the
+// write-back of step i and the draw of step i + 1 are adjacent launches of which the first is one workgroup and the second must
+// read the tree the first leaves: they are ONE launch, k_per_turn (per_turn_kernels.h).  Enqueued: one upload of the n_steps rows
+// of uniforms (staging ring) -> k_per_draw on row 0 -> for every step the replay-sourced step of the handle's family on that
+// step's rows of leaves, weights and |TD| -> k_per_turn behind every step but the last -> k_per_write_back: 2 n_steps + 1
+// launches beside the steps' own where n_steps calls of idqn_per_learn_on_replay make 3 n_steps and n_steps uploads.
+// Every refusal -- this call's and the dispatched entry's -- comes before anything is enqueued, allocated or staged.
+extern "C" int idqn_per_learn_steps_on_replay(idqn_handle_t h, const idqn_per_steps_t* per, const uint8_t* frame_ring_dev, int64_t n_frames,
+                                              int64_t frame_bytes, const int32_t* rows_dev, int32_t n_steps, int32_t batch, int32_t stack,
+                                              int32_t batch_mean_divisor, uint32_t flags, void* stream) {
+    const char* fn = "idqn_per_learn_steps_on_replay";
+    IDQN_REQUIRE(h && per && per->weights_dev && per->td_abs_dev, "%s: null pointer", fn);
+    IDQN_REQUIRE(h->iqn.N == 0, "%s: handles with quantile heads are not served (n_quantiles = %d): idqn_per_learn_on_replay, step by step", fn,
+                 h->iqn.N);
+    IDQN_REQUIRE(n_steps >= 1 && n_steps <= IDQN_MAX_STEPS_PER_CALL, "%s: n_steps %d not in [1, %d]", fn, n_steps, IDQN_MAX_STEPS_PER_CALL);
+    IDQN_REQUIRE(!(flags & ~(IDQN_F_PROFILE | IDQN_F_PROFILE_ALL)), "%s: only the profile flags are supported (got 0x%x)", fn, flags);
+    IDQN_REQUIRE(!h->is_weight && !h->td_abs,
+                 "%s: the handle has prioritized-replay buffers set (idqn_set_per_buffers): the call sets its own for its duration", fn);
+    IDQN_REQUIRE(batch >= 1 && batch <= PER_STEP_MAX_N && batch <= h->cfg.max_batch, "%s: batch %d not in [1, min(%d, %d)]", fn, batch,
+                 PER_STEP_MAX_N, h->cfg.max_batch);
+    const char* bad = per_draw_args_error(per->nodes_dev, per->depth, per->uniforms_host, batch, per->n_items, per->leaves_dev, per->weights_dev);
+    if (!bad) bad = per_write_back_args_error(per->nodes_dev, per->depth, per->leaves_dev, per->td_abs_dev, h->cfg.n_heads, batch, per->tree_scratch_dev);
+    IDQN_REQUIRE(!bad, "%s: %s (depth %d, batch %d, n_items %ld)", fn, bad, per->depth, batch, (long)per->n_items);
+    const bool plane = h->cfg.arch == IDQN_ARCH_CNN && h->planes && !h->gc.on;
+    if (plane) {
+        if (const int rc = replay_check(h, fn, frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, per->leaves_dev, batch, stack, nullptr, flags))
+            return rc;
+        IDQN_REQUIRE(batch_mean_divisor >= batch, "%s: mean divisor %d < batch %d", fn, batch_mean_divisor, batch);
+    } else {
+        long obs_elems;
+        if (const int rc = replay_fc_check(h, fn, frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, per->leaves_dev, batch, stack,
+                                           batch_mean_divisor, flags, &obs_elems))
+            return rc;
+    }
+    hipStream_t q = (hipStream_t)stream;
+    const int K = h->cfg.n_heads;
+    int blk = -1, rc;
+    if ((rc = steps_stage(h, per->uniforms_host, (size_t)n_steps * batch * 8, q, &blk))) return rc;
+    const double* u = (const double*)h->steps_dev[blk];
+    if ((rc = tl_begin(h, flags, q))) return rc;
+    if ((rc = per_draw(per->nodes_dev, per->depth, u, batch, per->stratified, per->n_items, per->beta, per->leaves_dev, per->weights_dev, stream)))
+        return rc;
+    tl_mark(h, q, "k_per_draw");
+    for (int i = 0; i < n_steps; ++i) {
+        const long o = (long)i * batch;
+        int32_t* leaves = per->leaves_dev + o;
+        float* td = per->td_abs_dev + o * K;
+        double* pri = per->priorities_dev ? per->priorities_dev + o : nullptr;
+        h->is_weight = per->weights_dev + o; h->td_abs = td;
+        if (plane)
+            rc = learn_on_replay(h, fn, frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, leaves, batch, stack, nullptr, batch_mean_divisor,
+                                 flags, stream);
+        else
+            rc = learn_on_replay_fc(h, fn, frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, leaves, batch, stack, batch_mean_divisor, flags,
+                                    stream);
+        h->is_weight = nullptr; h->td_abs = nullptr;
+        if (rc) return rc;
+        if (i + 1 < n_steps) {
+            if ((rc = per_turn(per->nodes_dev, per->depth, leaves, td, K, batch, per->reduce_max, per->eps, per->alpha, pri, per->max_priority_dev,
+                               per->tree_scratch_dev, u + o + batch, per->stratified, per->n_items, per->beta, leaves + batch,
+                               per->weights_dev + o + batch, stream)))
+                return rc;
+            tl_mark(h, q, "k_per_turn");
+        } else {
+            if ((rc = per_write_back(per->nodes_dev, per->depth, leaves, td, K, batch, per->reduce_max, per->eps, per->alpha, pri,
+                                     per->max_priority_dev, per->tree_scratch_dev, stream)))
+                return rc;
+            tl_mark(h, q, "k_per_write_back");
+        }
+        // the last launch that reads the staged uniforms: k_per_draw of a single step, else the last k_per_turn
+        if (i == std::max(0, n_steps - 2) && (rc = steps_stage_guard(h, blk, q))) return rc;
+    }
+    return IDQN_OK;
+}
+
 // One i-IQN gradient step (include/idqn_hip.h).  With idqn_set_per_buffers the loss launch takes the importance weights and
 // writes the per-sample mean |pairwise TD error| (k_iqn_loss<true>); without them it is the plain launch.
 extern "C" int idqn_iqn_learn_on_batch(idqn_handle_t h, const void* state_dev, const void* next_state_dev,
@@ -2678,13 +2764,7 @@ extern "C" int idqn_iqn_learn_on_batch(idqn_handle_t h, const void* state_dev, c
     const int K = h->cfg.n_heads, A = h->cfg.n_actions;
     const int nb = cdiv(batch, 32), NB = w.N * nb;  // blocks per virtual net: fraction q of sample block s is block s N + q
     h->pend_B = 0; h->pend_stage = 0;
-    h->tl_on = (flags & IDQN_F_PROFILE_ALL) != 0;
-    if (h->tl_on && h->tl_ev.empty()) {
-        h->tl_ev.resize(2048);
-        h->tl_name.resize(2048);
-        for (auto& e : h->tl_ev) IDQN_HIP_CHECK(hipEventCreate(&e));
-    }
-    tl_mark(h, q, nullptr);
+    if (const int rc = tl_begin(h, flags, q)) return rc;
     int rc;
     // trunk of the 2K nets (online on s, target on s'), then the fraction blocks of the 3K virtual nets
     if ((rc = cnn_forward(h, h->train, (const uint8_t*)state_dev, (const uint8_t*)next_state_dev, batch, q, false))) return rc;
@@ -3707,7 +3787,7 @@ extern "C" int idqn_group_create(const idqn_handle_t* members, int32_t n_members
     G->slots_off = ((size_t)n_members * sizeof(FcGroupMember) + 15) & ~(size_t)15;
     // the prioritized call (idqn_group_per_learn_on_replay_fc) puts its tree records and uniforms where the slots go
     G->uni_off = G->slots_off + (((size_t)n_members * sizeof(PerGroupMember) + 15) & ~(size_t)15);
-    G->block_bytes = std::max(G->slots_off + (size_t)n_members * STEPS_BLOCK_BYTES, G->uni_off + (size_t)n_members * PER_GROUP_MAX_N * 8);
+    G->block_bytes = std::max(G->slots_off + (size_t)n_members * STEPS_SLOTS_BYTES, G->uni_off + (size_t)n_members * PER_GROUP_MAX_N * 8);
     *out = G;
     return IDQN_OK;
 }

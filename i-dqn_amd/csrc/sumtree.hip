@@ -19,6 +19,7 @@
 #include "sumtree_device.h"
 #include "per_step_args.h"
 #include "per_step_kernels.h"
+#include "per_turn_kernels.h"
 
 static thread_local char g_err[512] = "";
 void idqn_set_error(const char* fmt, ...) {
@@ -30,8 +31,8 @@ void idqn_set_error(const char* fmt, ...) {
 extern "C" const char* idqn_last_error(void) { return g_err; }
 // 2: idqn_config_t.n_quantiles, the i-IQN entry points; 3: sumtree_query_host(n_live), the idqn_dp_* family; 4: idqn_learn_on_replay.
 // Still 4 after idqn_learn_on_replay_dev, idqn_dp_learn_on_replay and per_priorities_from_td_gathered, and idqn_learn_on_replay
-// accepting the IDQN_F_STOP_* flags, and after per_draw, per_write_back and idqn_per_learn_on_replay: additions only -- no existing
-// signature, struct or behaviour changed (backward compatible).
+// accepting the IDQN_F_STOP_* flags, and after per_draw, per_write_back and idqn_per_learn_on_replay, and after per_turn and
+// idqn_per_learn_steps_on_replay: additions only -- no existing signature, struct or behaviour changed (backward compatible).
 extern "C" int idqn_abi_version(void) { return 4; }
 
 __global__ __launch_bounds__(ST_THREADS) void k_sumtree_set(double* __restrict__ nodes, int depth,
@@ -506,6 +507,23 @@ extern "C" int per_write_back(double* nodes_dev, int32_t depth, const int32_t* l
     while (m < n) m <<= 1;
     hipLaunchKernelGGL(k_per_write_back, dim3(1), dim3(ST_THREADS), 0, (hipStream_t)stream, nodes_dev, depth, leaves_dev, td_abs_dev,
                        n_heads, n, m, reduce_max, eps, alpha, priorities_out_dev, max_priority_dev, (double*)scratch_dev);
+    IDQN_HIP_CHECK(hipGetLastError());
+    return IDQN_OK;
+}
+
+// per_write_back on (leaves, |TD|) followed by per_draw on the next uniforms as ONE launch of one workgroup (per_turn_kernels.h).
+extern "C" int per_turn(double* nodes_dev, int32_t depth, const int32_t* leaves_dev, const float* td_abs_dev, int32_t n_heads, int32_t n,
+                        int32_t reduce_max, double eps, double alpha, double* priorities_out_dev, double* max_priority_dev,
+                        void* scratch_dev, const double* next_uniforms_dev, int32_t stratified, int64_t n_items, double beta,
+                        int32_t* next_leaves_out_dev, float* next_weights_out_dev, void* stream) {
+    const char* bad = per_write_back_args_error(nodes_dev, depth, leaves_dev, td_abs_dev, n_heads, n, scratch_dev);
+    if (!bad) bad = per_draw_args_error(nodes_dev, depth, next_uniforms_dev, n, n_items, next_leaves_out_dev, next_weights_out_dev);
+    IDQN_REQUIRE(!bad, "per_turn: %s (depth %d, n %d, n_heads %d, n_items %ld)", bad, depth, n, n_heads, (long)n_items);
+    int m = 1;
+    while (m < n) m <<= 1;
+    hipLaunchKernelGGL(k_per_turn, dim3(1), dim3(ST_THREADS), 0, (hipStream_t)stream, nodes_dev, depth, leaves_dev, td_abs_dev, n_heads, n,
+                       m, reduce_max, eps, alpha, priorities_out_dev, max_priority_dev, (double*)scratch_dev, next_uniforms_dev, stratified,
+                       (double)n_items, beta, next_leaves_out_dev, next_weights_out_dev);
     IDQN_HIP_CHECK(hipGetLastError());
     return IDQN_OK;
 }

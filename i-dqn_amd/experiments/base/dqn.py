@@ -92,10 +92,15 @@ class VectorTrainer:
     environment that stepped and ``update_online_params`` / ``update_target_params`` run at every one of those values
     (after ``n_initial_samples``), so the gradient-step and target-update schedule per environment step is the single
     trainer's.  Once an epoch's budget is spent, an environment that ends its episode waits (it is passed to the buffer as
-    ``None``) until all have: an epoch ends with every environment on an episode boundary."""
+    ``None``) until all have: an epoch ends with every environment on an episode boundary.
 
-    def __init__(self, key, p, agent, envs, rb, save_fn=None):
+    ``learner``: a ``PrioritizedLearner`` on ``agent`` and ``rb`` (slimdqn/sample_collection/per.py).  The gradient step of the
+    schedule is then ``learner.step()`` -- the vector step's run of them ``learner.update_params_many`` -- and the target
+    operations stay the agent's own."""
+
+    def __init__(self, key, p, agent, envs, rb, save_fn=None, learner=None):
         self.key, self.p, self.agent, self.envs, self.rb, self.save_fn = key, p, agent, list(envs), rb, save_fn
+        self.learner = learner
         self.epsilon = linear_schedule(1.0, p["epsilon_end"], p["epsilon_duration"])
         self.total_steps = 0
         self.history = []  # one list of per-environment EpochStats per epoch
@@ -108,10 +113,18 @@ class VectorTrainer:
         return collect_vector_samples(keys, self.envs, self.agent, self.rb, self.p, self.epsilon, self.total_steps, active)
 
     def _gradient_step(self):
-        self.agent.update_online_params(self.total_steps, self.rb)
+        if self.learner is None:
+            self.agent.update_online_params(self.total_steps, self.rb)
+        elif self.total_steps % self.agent.update_to_data == 0:
+            self.learner.step()
         updated, logs = self.agent.update_target_params(self.total_steps)
         if updated:
             self.p["wandb"].log({"n_training_steps": self.total_steps, **logs})
+
+    def _update_params_many(self, first, n_steps):
+        if self.learner is not None:
+            return self.learner.update_params_many(first, n_steps)
+        return self.agent.update_params_many(first, n_steps, self.rb)
 
     def run_epoch(self, index):
         n_envs, budget, done = len(self.envs), self.p["n_training_steps_per_epoch"], 0
@@ -130,12 +143,12 @@ class VectorTrainer:
                         stats[i].open_episode()
                     else:
                         active[i] = False
-            if hasattr(self.agent, "update_params_many") and self.p.get("fuse_gradient_steps", True):
+            if (self.learner is not None or hasattr(self.agent, "update_params_many")) and self.p.get("fuse_gradient_steps", True):
                 # the vector step's gradient steps as one call; a target update's record follows the run that call closes
                 first = max(self.total_steps, self.p["n_initial_samples"]) + 1
                 self.total_steps += stepped
                 if self.total_steps >= first:
-                    for step, logs in self.agent.update_params_many(first, self.total_steps - first + 1, self.rb):
+                    for step, logs in self._update_params_many(first, self.total_steps - first + 1):
                         self.p["wandb"].log({"n_training_steps": step, **logs})
             else:
                 for _ in range(stepped):
@@ -163,7 +176,7 @@ class VectorTrainer:
         return self._per_epoch("returns"), self._per_epoch("lengths")
 
 
-def train_vector(key, p: dict, agent, envs, rb, save_fn=None):
+def train_vector(key, p: dict, agent, envs, rb, save_fn=None, learner=None):
     """``train`` for a list of environments and a ``VectorReplayBuffer``; returns (returns, lengths) per epoch, the
     environments' episodes concatenated in environment order."""
-    return VectorTrainer(key, p, agent, envs, rb, save_fn).run()
+    return VectorTrainer(key, p, agent, envs, rb, save_fn, learner=learner).run()

@@ -59,6 +59,11 @@ class PerStep(C.Structure):
     ]
 
 
+class PerSteps(C.Structure):
+    """idqn_per_steps_t: ``PerStep`` without ``tau_dev``; the uniforms and the outputs hold one row per step."""
+    _fields_ = PerStep._fields_[:-1]
+
+
 class GroupRing(C.Structure):
     """idqn_group_ring_t: one member's replay frame ring, as ``idqn_learn_on_replay_fc`` takes it."""
     _fields_ = [("frames_dev", C.c_void_p), ("n_frames", C.c_int64), ("frame_bytes", C.c_int64), ("rows_dev", C.c_void_p),
@@ -124,6 +129,10 @@ SYMBOLS = {
     "per_write_back": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P, _P, _P, _P]),
     "idqn_per_learn_on_replay": (C.c_int, [_P, C.POINTER(PerStep), _P, C.c_int64, C.c_int64, _P, C.c_int32, C.c_int32, C.c_int32,
                                            C.c_uint32, _P]),
+    "per_turn": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P, _P, _P, _P, C.c_int32, C.c_int64,
+                           C.c_double, _P, _P, _P]),
+    "idqn_per_learn_steps_on_replay": (C.c_int, [_P, C.POINTER(PerSteps), _P, C.c_int64, C.c_int64, _P, C.c_int32, C.c_int32, C.c_int32,
+                                                 C.c_int32, C.c_uint32, _P]),
     "idqn_target_update": (C.c_int, [_P, _P]),
     "idqn_target_sync": (C.c_int, [_P, _P]),
     "idqn_q_values": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P]),

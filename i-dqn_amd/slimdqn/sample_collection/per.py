@@ -21,6 +21,9 @@ Design (Schaul et al. 2016, proportional variant), all on the GPU, no host synch
   general-shape cnn agents) skip it the same way through ``idqn_learn_on_replay_fc_dev``.
 * Where the agent's replay-sourced conditions hold, the whole chain is ONE C call, ``idqn_per_learn_on_replay`` (two fused
   kernels around the replay-sourced step), byte-identical to the chain; ``fuse_per_step`` / ``fuse_per_family`` below.
+* n steps are ONE C call as well, ``idqn_per_learn_steps_on_replay`` (``PrioritizedLearner.steps``): the write-back of a step and
+  the draw of the next are one launch (``k_per_turn``), the uniforms of all steps one upload; byte-identical to n ``step()`` calls.
+  ``PrioritizedLearner.update_params_many`` is the trainer-side loop over it (``VectorTrainer(..., learner=...)``).
 * ``PrioritizedGroupLearner``: the prioritized step of the S MLP agents of an ``AgentGroup`` as ONE C call,
   ``idqn_group_per_learn_on_replay_fc`` (three launches for all members), byte-identical per member to the member's own step.
 """
@@ -30,7 +33,7 @@ import os
 import numpy as np
 
 from slimdqn import _hip
-from slimdqn.networks._agent import DeviceAgent
+from slimdqn.networks._agent import DeviceAgent, plan_step_runs
 from slimdqn.sample_collection import sum_tree
 
 
@@ -140,9 +143,12 @@ class PrioritizedLearner:
         return not (len(f) == 4 and agent._obs[2] == 4 and min(agent._obs[:2]) >= 8 and net.n_actions <= 32
                     and all(x in (32, 64) for x in f[:3]) and f[3] % 128 == 0 and 128 <= f[3] <= 512)
 
-    def _fused_route(self):
-        """``(ring view, family)`` when this step goes through ``idqn_per_learn_on_replay``, else None; read on every call."""
+    def _fused_route(self, defaults=None):
+        """``(ring view, family)`` when this step goes through ``idqn_per_learn_on_replay``, else None; read on every call.
+        ``defaults``: the per-family switches that apply (``fuse_per_family``; ``steps`` passes ``fuse_per_steps_family``)."""
         from slimdqn.networks.iiqn import iIQN
+
+        defaults = self.fuse_per_family if defaults is None else defaults
 
         agent, rb = self.agent, self.rb
         if not self.fuse_per_step or os.environ.get("IDQN_PER_FUSED", "1") == "0" or self.__dict__.get("_fused_ok") is False:
@@ -151,11 +157,11 @@ class PrioritizedLearner:
             return None
         if isinstance(agent, iIQN):
             view = self._replay_sourced() if type(agent)._learn is iIQN._learn else None
-            return (view, "iqn") if view is not None and self.fuse_per_family["iqn"] else None
+            return (view, "iqn") if view is not None and defaults.get("iqn") else None
         if type(agent)._learn is not DeviceAgent._learn:
             return None
         family = "fc" if agent._arch == "fc" else ("gcnn" if self._general_shape(agent) else "plane")
-        if not self.fuse_per_family[family]:
+        if not defaults.get(family):
             return None
         if agent._replay_fusable(rb):
             view = rb.ring_view()
@@ -218,6 +224,113 @@ class PrioritizedLearner:
                     agent._replay_fc_ok = True
                 return agent._losses
         return self._step_chain(u, taus)
+
+    # n steps as ONE C call per ``MAX_STEPS_PER_CALL`` rows of uniforms (``idqn_per_learn_steps_on_replay``: one upload, k_per_draw,
+    # then step / k_per_turn alternating, k_per_write_back), byte-identical to n ``step_with_uniforms`` calls on the same rows.
+    # Taken where the one-call step would be (``_fused_route``'s conditions, under ``fuse_per_steps_family`` instead of
+    # ``fuse_per_family``; i-IQN agents are not served) for runs of at least ``per_steps_min`` steps at batches of at most
+    # ``per_steps_max_batch`` samples; ``IDQN_PER_STEPS=0`` switches
+    # it off.  ``_steps_ok`` (unset: not tried; False: the entry refused this handle the first time -- text in ``steps_refusal`` --
+    # the rows go through ``step_with_uniforms`` one by one from then on; True: it served).
+    # Defaults by the rule "the call is a family's default at the n where its median lies below the minimum of the chain of n
+    # ``idqn_per_learn_on_replay`` calls on the same commit" (tools/bench_per_steps.py -> profiles/per_steps.json; B = 32, us per
+    # gradient step, call against chain).  n = 1 is SLOWER everywhere (LunarLander net 51.2 against 47.6, [520] 342.9 against
+    # 341.6, Atari shape K = 5 277.8 against 277.4): ``per_steps_min`` = 2.  From n = 2 on the call wins: LunarLander net 43.9 /
+    # 41.5 / 40.8 / 40.6 at n = 2 / 5 / 10 / 32 against 47.6; [520] 336.6 ... 333.4 against 341.6; Atari shape 272.4 ... 269.5
+    # against 277.3: MLP and plane-path cnn on.  General-shape cnn: not measured, off.  k_per_turn alone beats the launch pair at
+    # n = 32 (14.4 against 16.1 us) and is SLOWER at n = 256 (61.5 against 31.1 us: 16 descents in turn per wave where k_per_draw
+    # spreads them over 64 workgroups), and no whole step was measured past B = 32: ``per_steps_max_batch`` keeps larger batches on
+    # the single steps.
+    per_steps_min = 2
+    per_steps_max_batch = 32
+    fuse_per_steps_family = {"plane": True, "fc": True, "gcnn": False}
+
+    def _steps_route(self, n):
+        """``(ring view, family)`` when a run of ``n`` steps goes through ``idqn_per_learn_steps_on_replay``, else None."""
+        if n < self.per_steps_min or os.environ.get("IDQN_PER_STEPS", "1") == "0" or self.__dict__.get("_steps_ok") is False:
+            return None
+        if self.rb._batch_size > self.per_steps_max_batch:
+            return None
+        return self._fused_route(self.fuse_per_steps_family)
+
+    def _steps_fused(self, view, U):
+        """The library's code for the n-step call on ring ``view`` with uniforms ``U`` (float64 [m][B], host, contiguous)."""
+        import torch
+
+        rb, tree, agent = self.rb, self.sampler._sum_tree, self.agent
+        B, K, m = rb._batch_size, agent._K, U.shape[0]
+        frames, n_frames, frame_bytes, rows, stack = view[:5]
+        agent._ensure_handle(B)
+        rows_out = self.__dict__.get("_steps_rows")
+        if rows_out is None:  # one row per step: leaves, weights, |TD|, priorities
+            M = _hip.MAX_STEPS_PER_CALL
+            rows_out = self._steps_rows = (torch.empty((M, B), dtype=torch.int32, device="cuda"),
+                                           torch.empty((M, B), dtype=torch.float32, device="cuda"),
+                                           torch.zeros((M, K, B), dtype=torch.float32, device="cuda"),
+                                           torch.empty((M, B), dtype=torch.float64, device="cuda"))
+        p = self.__dict__.get("_per_steps_args")
+        if p is None:
+            p = self._per_steps_args = _hip.PerSteps()
+        vp = lambda t: None if t is None else int(t.data_ptr())  # noqa: E731
+        p.nodes_dev, p.depth, p.n_items = vp(tree._nodes_dev), tree._depth, len(self.sampler)
+        p.uniforms_host = U.ctypes.data
+        p.stratified, p.reduce_max, p.beta, p.eps, p.alpha = self.stratified, self.reduce_max, self.beta, self.eps, self.sampler._alpha
+        p.max_priority_dev = vp(self.sampler._max_priority_dev)
+        p.leaves_dev, p.weights_dev, p.td_abs_dev, p.priorities_dev = (vp(t) for t in rows_out)
+        p.tree_scratch_dev = vp(tree._scratch)
+        rc = _hip.lib().idqn_per_learn_steps_on_replay(agent._handle, C.byref(p), _hip.ptr(frames), int(n_frames), int(frame_bytes),
+                                                       _hip.ptr(rows), m, B, int(stack), B, 0, _hip.current_stream())
+        if rc == 0:  # the learner's own buffers are the last step's rows, as m ``step()`` calls leave them
+            self._leaves, self._weights, self._td_abs, self._priorities = (t[m - 1] for t in rows_out)
+        return rc
+
+    def steps_with_uniforms(self, U):
+        """``step_with_uniforms`` on every row of ``U`` (float64 [n][B] in [0, 1)), in order; returns the per-head losses of the
+        last step (device tensor, not synchronised).  Every row goes through exactly one route."""
+        U = np.ascontiguousarray(U, np.float64)
+        n, i = U.shape[0], 0
+        route = self._steps_route(n)
+        while route is not None and i < n:
+            m = min(_hip.MAX_STEPS_PER_CALL, n - i)
+            rc = self._steps_fused(route[0], U[i : i + m])
+            if rc == _hip.E_INVALID and self.__dict__.get("_steps_ok") is None:
+                self._steps_ok = False  # not this handle: single steps from now on -- the same rows, nothing more drawn
+                self.steps_refusal = _hip.lib().idqn_last_error().decode(errors="replace")
+                break
+            _hip.check(rc, "idqn_per_learn_steps_on_replay")
+            self._steps_ok = True
+            if route[1] == "fc":  # the agent's replay-sourced entry served (the flag its own routes keep)
+                self.agent._replay_fc_ok = True
+            i += m
+        for u in U[i:]:
+            self.step_with_uniforms(u)
+        return self.agent._losses
+
+    def steps(self, n):
+        """``n`` prioritized gradient steps: the sampler's generator is drawn n times first, in order -- the state n ``step()``
+        calls leave (a prioritized draw takes uniforms only, so it does not depend on the steps between) -- then the steps run,
+        as one call where ``steps_with_uniforms`` allows it."""
+        n = int(n)
+        if n <= 0:
+            return self.agent._losses
+        assert self.rb.add_count, "No samples in replay buffer!"
+        B = self.rb._batch_size
+        return self.steps_with_uniforms(np.stack([self.sampler._rng_key.random(B) for _ in range(n)]))
+
+    def update_params_many(self, first_step, n_steps):
+        """``[(step, logs)]`` of the target updates of the loop ``if s % update_to_data == 0: step(); update_target_params(s)``
+        over ``n_steps`` steps from ``first_step``, with the same effect and order: ``plan_step_runs`` with the agent's schedule,
+        every run's gradient steps through ``steps``, the target operation the agent's own.  The losses reach the agent's
+        ``cumulated_losses`` as ``step()`` adds them: on the device, inside the step."""
+        agent, out = self.agent, []
+        for n_grad, op, last in plan_step_runs(first_step, n_steps, agent.update_to_data, agent.target_update_frequency,
+                                               getattr(agent, "target_sync_frequency", None)):
+            self.steps(n_grad)
+            if op is not None:
+                updated, logs = agent.update_target_params(last)
+                if updated:
+                    out.append((last, logs))
+        return out
 
     def _step_chain(self, u, taus=None):
         """The step as a chain of calls on uniforms ``u`` (and, for an i-IQN agent, fractions ``taus`` already drawn)."""

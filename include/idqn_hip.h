@@ -566,6 +566,42 @@ typedef struct idqn_per_step {
 int idqn_per_learn_on_replay(idqn_handle_t h, const idqn_per_step_t* per, const uint8_t* frame_ring_dev, int64_t n_frames,
                              int64_t frame_bytes, const int32_t* rows_dev, int32_t batch, int32_t stack,
                              int32_t batch_mean_divisor, uint32_t flags, void* stream);
+/* per_write_back on (leaves_dev, td_abs_dev) followed by per_draw on next_uniforms_dev as ONE launch of one workgroup, n in
+ * [1, 256] (k_per_turn): between two consecutive prioritized steps the two launches are adjacent, the first is one workgroup
+ * and the second must read the tree the first leaves.  The node array, max_priority_dev[0] (may be NULL), priorities_out_dev
+ * (may be NULL), next_leaves_out_dev (clamped to [0, n_items - 1]) and next_weights_out_dev afterwards equal, byte for byte,
+ * what the two calls leave.  The descents run one wave each, 16 at a time; no arrival counter and no waiting between
+ * workgroups: there is one.  Arguments and restrictions: those of per_write_back and per_draw.                              */
+int per_turn(double* nodes_dev, int32_t depth, const int32_t* leaves_dev, const float* td_abs_dev, int32_t n_heads, int32_t n,
+             int32_t reduce_max, double eps, double alpha, double* priorities_out_dev, double* max_priority_dev, void* scratch_dev,
+             const double* next_uniforms_dev, int32_t stratified, int64_t n_items, double beta, int32_t* next_leaves_out_dev,
+             float* next_weights_out_dev, void* stream);
+/* n_steps consecutive prioritized learner steps on the HBM frame ring as ONE call.  Handle state (online parameters, both
+ * moments, count, losses, cum_losses), tree nodes, max_priority_dev and every output row afterwards equal, byte for byte,
+ * n_steps calls of idqn_per_learn_on_replay on the rows of uniforms_host on the same stream.  Enqueued: ONE upload of the
+ * uniforms, per_draw on row 0, then for every step the replay-sourced step of the handle's family (as idqn_per_learn_on_replay
+ * dispatches it; the one-launch MLP step stays one launch per step) on that step's rows, per_turn behind every step but the
+ * last, per_write_back behind the last: 2 n_steps + 1 launches around the steps where the single calls make 3 n_steps.
+ *   uniforms_host: float64 [n_steps][batch] in [0, 1), ordinary HOST memory, read before the call returns (the handle's pinned
+ *     staging blocks, IDQN_STEPS_STAGING_DEPTH of them, each reused only after the launch that read it has finished).
+ *   leaves_dev int32 [n_steps][batch], weights_dev float [n_steps][batch], td_abs_dev float [n_steps][K][batch], priorities_dev
+ *     float64 [n_steps][batch] (may be NULL): one row per step, each step's row as idqn_per_learn_on_replay leaves it.
+ * Restrictions (IDQN_E_INVALID otherwise, nothing enqueued, allocated or staged): handles with quantile heads are not served;
+ * n_steps in [1, IDQN_MAX_STEPS_PER_CALL]; everything idqn_per_learn_on_replay refuses; no prioritized-replay buffers set on
+ * the handle; flags IDQN_F_PROFILE / IDQN_F_PROFILE_ALL only (with the latter idqn_profile_table lists the launches above
+ * as k_per_draw, k_per_turn and k_per_write_back beside the steps' own).                                                    */
+typedef struct idqn_per_steps {
+    double* nodes_dev; int32_t depth; int64_t n_items;
+    const double* uniforms_host;   /* [n_steps][batch] in [0, 1), ordinary HOST memory, read before the call returns */
+    int32_t stratified, reduce_max; double beta, eps, alpha;
+    double* max_priority_dev;      /* may be NULL */
+    int32_t* leaves_dev /* [n_steps][batch] */; float* weights_dev /* [n_steps][batch] */; float* td_abs_dev /* [n_steps][K][batch] */;
+    double* priorities_dev;        /* [n_steps][batch]; may be NULL */
+    void* tree_scratch_dev;        /* as sumtree_set */
+} idqn_per_steps_t;
+int idqn_per_learn_steps_on_replay(idqn_handle_t h, const idqn_per_steps_t* per, const uint8_t* frame_ring_dev, int64_t n_frames,
+                                   int64_t frame_bytes, const int32_t* rows_dev, int32_t n_steps, int32_t batch, int32_t stack,
+                                   int32_t batch_mean_divisor, uint32_t flags, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Replay store in HBM (slimdqn/sample_collection/replay_buffer.py:202-230).  The store the product uses is the
