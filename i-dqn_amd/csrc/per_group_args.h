@@ -18,9 +18,7 @@ static inline const char* per_group_args_error(const idqn_per_step_t* per, int32
         const idqn_per_step_t& p = per[g];
         *g_out = g;
         if (p.tau_dev) return "tau_dev is set: a group serves MLP members, which take no fractions";
-        const char* bad = per_draw_args_error(p.nodes_dev, p.depth, p.uniforms_host, batch, p.n_items, p.leaves_dev, p.weights_dev);
-        if (!bad) bad = per_write_back_args_error(p.nodes_dev, p.depth, p.leaves_dev, p.td_abs_dev, n_heads, batch, p.tree_scratch_dev);
-        if (bad) return bad;
+        if (const char* bad = per_step_args_error(per_sampler_of(p, p.uniforms_host, n_heads), batch)) return bad;  // (uniforms: NULL or not)
     }
     for (int g = 1; g < n_members; ++g)
         for (int j = 0; j < g; ++j) {

@@ -2625,61 +2625,92 @@ extern "C" int idqn_iqn_learn_on_replay_dev(idqn_handle_t h, const uint8_t* fram
                            stack, tau_dev, batch, flags, stream);
 }
 
-// One prioritized learner step on the frame ring as ONE C call (include/idqn_hip.h): uniforms (staging ring) -> k_per_draw -> the
-// replay-sourced step of the handle's family on the leaves, weights and |TD| in force for that step only -> k_per_write_back.
-// Every refusal -- this call's and the dispatched entry's -- comes before anything is enqueued, allocated or staged.
-extern "C" int idqn_per_learn_on_replay(idqn_handle_t h, const idqn_per_step_t* per, const uint8_t* frame_ring_dev, int64_t n_frames,
-                                        int64_t frame_bytes, const int32_t* rows_dev, int32_t batch, int32_t stack,
-                                        int32_t batch_mean_divisor, uint32_t flags, void* stream) {
-    const char* fn = "idqn_per_learn_on_replay";
-    IDQN_REQUIRE(h && per && per->weights_dev && per->td_abs_dev, "%s: null pointer", fn);
+// n_steps consecutive prioritized learner steps on the frame ring, the driver of idqn_per_learn_on_replay (n_steps == 1) and
+// idqn_per_learn_steps_on_replay; P is idqn_per_step_t or idqn_per_steps_t (the same fields; tau_dev is the former's).  Between two
+// steps the write-back of step i and the draw of step i + 1 are adjacent launches of which the first is one workgroup and the
+// second must read the tree the first leaves: they are ONE launch, k_per_turn (per_turn_kernels.h).  Enqueued: one upload of the
+// n_steps rows of uniforms (staging ring) -> k_per_draw on row 0 -> for every step the replay-sourced step of the handle's family
+// on that step's rows of leaves, weights and |TD|, in force for that step only -> k_per_turn behind every step but the last ->
+// k_per_write_back: 2 n_steps + 1 launches beside the steps' own.  `marks`: the sampler launches appear in the step timeline
+// (IDQN_F_PROFILE_ALL; the single step has never listed them, and its callers read the table of the step alone).
+// Every refusal -- the entries', this one's and the dispatched step's -- comes before anything is enqueued, allocated or staged.
+template <class P>
+static int per_learn_on_replay(idqn_handle_t h, const char* fn, const P& per, const float* tau_dev, const uint8_t* frame_ring_dev, int64_t n_frames,
+                               int64_t frame_bytes, const int32_t* rows_dev, int32_t n_steps, int32_t batch, int32_t stack,
+                               int32_t batch_mean_divisor, uint32_t flags, void* stream, bool marks) {
     IDQN_REQUIRE(!(flags & ~(IDQN_F_PROFILE | IDQN_F_PROFILE_ALL)), "%s: only the profile flags are supported (got 0x%x)", fn, flags);
     IDQN_REQUIRE(!h->is_weight && !h->td_abs,
                  "%s: the handle has prioritized-replay buffers set (idqn_set_per_buffers): the call sets its own for its duration", fn);
     IDQN_REQUIRE(batch >= 1 && batch <= PER_STEP_MAX_N && batch <= h->cfg.max_batch, "%s: batch %d not in [1, min(%d, %d)]", fn, batch,
                  PER_STEP_MAX_N, h->cfg.max_batch);
-    const char* bad = per_draw_args_error(per->nodes_dev, per->depth, per->uniforms_host, batch, per->n_items, per->leaves_dev, per->weights_dev);
-    if (!bad) bad = per_write_back_args_error(per->nodes_dev, per->depth, per->leaves_dev, per->td_abs_dev, h->cfg.n_heads, batch, per->tree_scratch_dev);
-    IDQN_REQUIRE(!bad, "%s: %s (depth %d, batch %d, n_items %ld)", fn, bad, per->depth, batch, (long)per->n_items);
+    const int K = h->cfg.n_heads;
+    const char* bad = per_step_args_error(per_sampler_of(per, per.uniforms_host, K), batch);  // (uniforms: NULL or not)
+    IDQN_REQUIRE(!bad, "%s: %s (depth %d, batch %d, n_items %ld)", fn, bad, per.depth, batch, (long)per.n_items);
     const bool quantile = h->iqn.N > 0, plane = h->cfg.arch == IDQN_ARCH_CNN && h->planes && !h->gc.on;
-    IDQN_REQUIRE(quantile == (per->tau_dev != nullptr), "%s: tau_dev goes with quantile heads (the handle has n_quantiles = %d)", fn, h->iqn.N);
+    IDQN_REQUIRE(quantile == (tau_dev != nullptr), "%s: tau_dev goes with quantile heads (the handle has n_quantiles = %d)", fn, h->iqn.N);
     if (quantile || plane) {
-        if (const int rc = replay_check(h, fn, frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, per->leaves_dev, batch, stack, per->tau_dev, flags))
+        if (const int rc = replay_check(h, fn, frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, per.leaves_dev, batch, stack, tau_dev, flags))
             return rc;
         IDQN_REQUIRE(quantile || batch_mean_divisor >= batch, "%s: mean divisor %d < batch %d", fn, batch_mean_divisor, batch);
     } else {
         long obs_elems;
-        if (const int rc = replay_fc_check(h, fn, frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, per->leaves_dev, batch, stack,
+        if (const int rc = replay_fc_check(h, fn, frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, per.leaves_dev, batch, stack,
                                            batch_mean_divisor, flags, &obs_elems))
             return rc;
     }
     hipStream_t q = (hipStream_t)stream;
     int blk = -1, rc;
-    if ((rc = steps_stage(h, per->uniforms_host, (size_t)batch * 8, q, &blk))) return rc;
-    if ((rc = per_draw(per->nodes_dev, per->depth, (const double*)h->steps_dev[blk], batch, per->stratified, per->n_items, per->beta,
-                       per->leaves_dev, per->weights_dev, stream)))
+    if ((rc = steps_stage(h, per.uniforms_host, (size_t)n_steps * batch * 8, q, &blk))) return rc;
+    const double* u = (const double*)h->steps_dev[blk];
+    if (marks && (rc = tl_begin(h, flags, q))) return rc;
+    if ((rc = per_draw(per.nodes_dev, per.depth, u, batch, per.stratified, per.n_items, per.beta, per.leaves_dev, per.weights_dev, stream)))
         return rc;
-    if ((rc = steps_stage_guard(h, blk, q))) return rc;
-    h->is_weight = per->weights_dev; h->td_abs = per->td_abs_dev;
-    if (quantile || plane)
-        rc = learn_on_replay(h, fn, frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, per->leaves_dev, batch, stack, per->tau_dev,
-                             quantile ? batch : batch_mean_divisor, flags, stream);
-    else
-        rc = learn_on_replay_fc(h, fn, frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, per->leaves_dev, batch, stack,
-                                batch_mean_divisor, flags, stream);
-    h->is_weight = nullptr; h->td_abs = nullptr;
-    if (rc) return rc;
-    return per_write_back(per->nodes_dev, per->depth, per->leaves_dev, per->td_abs_dev, h->cfg.n_heads, batch, per->reduce_max, per->eps,
-                          per->alpha, per->priorities_dev, per->max_priority_dev, per->tree_scratch_dev, stream);
+    if (marks) tl_mark(h, q, "k_per_draw");
+    // the last launch that reads the staged uniforms: k_per_draw of a single step, else the last k_per_turn
+    if (n_steps == 1 && (rc = steps_stage_guard(h, blk, q))) return rc;
+    for (int i = 0; i < n_steps; ++i) {
+        const long o = (long)i * batch;
+        int32_t* leaves = per.leaves_dev + o;
+        float* td = per.td_abs_dev + o * K;
+        double* pri = per.priorities_dev ? per.priorities_dev + o : nullptr;
+        h->is_weight = per.weights_dev + o; h->td_abs = td;
+        if (quantile || plane)
+            rc = learn_on_replay(h, fn, frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, leaves, batch, stack, tau_dev,
+                                 quantile ? batch : batch_mean_divisor, flags, stream);
+        else
+            rc = learn_on_replay_fc(h, fn, frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, leaves, batch, stack, batch_mean_divisor, flags,
+                                    stream);
+        h->is_weight = nullptr; h->td_abs = nullptr;
+        if (rc) return rc;
+        if (i + 1 < n_steps) {
+            if ((rc = per_turn(per.nodes_dev, per.depth, leaves, td, K, batch, per.reduce_max, per.eps, per.alpha, pri, per.max_priority_dev,
+                               per.tree_scratch_dev, u + o + batch, per.stratified, per.n_items, per.beta, leaves + batch,
+                               per.weights_dev + o + batch, stream)))
+                return rc;
+            if (marks) tl_mark(h, q, "k_per_turn");
+            if (i + 2 == n_steps && (rc = steps_stage_guard(h, blk, q))) return rc;
+        } else {
+            if ((rc = per_write_back(per.nodes_dev, per.depth, leaves, td, K, batch, per.reduce_max, per.eps, per.alpha, pri,
+                                     per.max_priority_dev, per.tree_scratch_dev, stream)))
+                return rc;
+            if (marks) tl_mark(h, q, "k_per_write_back");
+        }
+    }
+    return IDQN_OK;
 }
 
-// n_steps consecutive prioritized learner steps on the frame ring as ONE C call (include/idqn_hip.h).  Between two steps the
-// write-back of step i and the draw of step i + 1 are adjacent launches of which the first is one workgroup and the second must
-// read the tree the first leaves: they are ONE launch, k_per_turn (per_turn_kernels.h).  Enqueued: one upload of the n_steps rows
-// of uniforms (staging ring) -> k_per_draw on row 0 -> for every step the replay-sourced step of the handle's family on that
-// step's rows of leaves, weights and |TD| -> k_per_turn behind every step but the last -> k_per_write_back: 2 n_steps + 1
-// launches beside the steps' own where n_steps calls of idqn_per_learn_on_replay make 3 n_steps and n_steps uploads.
-// Every refusal -- this call's and the dispatched entry's -- comes before anything is enqueued, allocated or staged.
+// One prioritized learner step as ONE C call (include/idqn_hip.h): the driver at one step; handles with quantile heads take tau_dev.
+extern "C" int idqn_per_learn_on_replay(idqn_handle_t h, const idqn_per_step_t* per, const uint8_t* frame_ring_dev, int64_t n_frames,
+                                        int64_t frame_bytes, const int32_t* rows_dev, int32_t batch, int32_t stack,
+                                        int32_t batch_mean_divisor, uint32_t flags, void* stream) {
+    const char* fn = "idqn_per_learn_on_replay";
+    IDQN_REQUIRE(h && per && per->weights_dev && per->td_abs_dev, "%s: null pointer", fn);
+    return per_learn_on_replay(h, fn, *per, per->tau_dev, frame_ring_dev, n_frames, frame_bytes, rows_dev, 1, batch, stack, batch_mean_divisor, flags,
+                               stream, false);
+}
+
+// n_steps of them as ONE C call (include/idqn_hip.h): the driver, where n_steps calls of idqn_per_learn_on_replay make 3 n_steps
+// sampler launches and n_steps uploads; handles with quantile heads are not served.
 extern "C" int idqn_per_learn_steps_on_replay(idqn_handle_t h, const idqn_per_steps_t* per, const uint8_t* frame_ring_dev, int64_t n_frames,
                                               int64_t frame_bytes, const int32_t* rows_dev, int32_t n_steps, int32_t batch, int32_t stack,
                                               int32_t batch_mean_divisor, uint32_t flags, void* stream) {
@@ -2688,64 +2719,8 @@ extern "C" int idqn_per_learn_steps_on_replay(idqn_handle_t h, const idqn_per_st
     IDQN_REQUIRE(h->iqn.N == 0, "%s: handles with quantile heads are not served (n_quantiles = %d): idqn_per_learn_on_replay, step by step", fn,
                  h->iqn.N);
     IDQN_REQUIRE(n_steps >= 1 && n_steps <= IDQN_MAX_STEPS_PER_CALL, "%s: n_steps %d not in [1, %d]", fn, n_steps, IDQN_MAX_STEPS_PER_CALL);
-    IDQN_REQUIRE(!(flags & ~(IDQN_F_PROFILE | IDQN_F_PROFILE_ALL)), "%s: only the profile flags are supported (got 0x%x)", fn, flags);
-    IDQN_REQUIRE(!h->is_weight && !h->td_abs,
-                 "%s: the handle has prioritized-replay buffers set (idqn_set_per_buffers): the call sets its own for its duration", fn);
-    IDQN_REQUIRE(batch >= 1 && batch <= PER_STEP_MAX_N && batch <= h->cfg.max_batch, "%s: batch %d not in [1, min(%d, %d)]", fn, batch,
-                 PER_STEP_MAX_N, h->cfg.max_batch);
-    const char* bad = per_draw_args_error(per->nodes_dev, per->depth, per->uniforms_host, batch, per->n_items, per->leaves_dev, per->weights_dev);
-    if (!bad) bad = per_write_back_args_error(per->nodes_dev, per->depth, per->leaves_dev, per->td_abs_dev, h->cfg.n_heads, batch, per->tree_scratch_dev);
-    IDQN_REQUIRE(!bad, "%s: %s (depth %d, batch %d, n_items %ld)", fn, bad, per->depth, batch, (long)per->n_items);
-    const bool plane = h->cfg.arch == IDQN_ARCH_CNN && h->planes && !h->gc.on;
-    if (plane) {
-        if (const int rc = replay_check(h, fn, frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, per->leaves_dev, batch, stack, nullptr, flags))
-            return rc;
-        IDQN_REQUIRE(batch_mean_divisor >= batch, "%s: mean divisor %d < batch %d", fn, batch_mean_divisor, batch);
-    } else {
-        long obs_elems;
-        if (const int rc = replay_fc_check(h, fn, frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, per->leaves_dev, batch, stack,
-                                           batch_mean_divisor, flags, &obs_elems))
-            return rc;
-    }
-    hipStream_t q = (hipStream_t)stream;
-    const int K = h->cfg.n_heads;
-    int blk = -1, rc;
-    if ((rc = steps_stage(h, per->uniforms_host, (size_t)n_steps * batch * 8, q, &blk))) return rc;
-    const double* u = (const double*)h->steps_dev[blk];
-    if ((rc = tl_begin(h, flags, q))) return rc;
-    if ((rc = per_draw(per->nodes_dev, per->depth, u, batch, per->stratified, per->n_items, per->beta, per->leaves_dev, per->weights_dev, stream)))
-        return rc;
-    tl_mark(h, q, "k_per_draw");
-    for (int i = 0; i < n_steps; ++i) {
-        const long o = (long)i * batch;
-        int32_t* leaves = per->leaves_dev + o;
-        float* td = per->td_abs_dev + o * K;
-        double* pri = per->priorities_dev ? per->priorities_dev + o : nullptr;
-        h->is_weight = per->weights_dev + o; h->td_abs = td;
-        if (plane)
-            rc = learn_on_replay(h, fn, frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, leaves, batch, stack, nullptr, batch_mean_divisor,
-                                 flags, stream);
-        else
-            rc = learn_on_replay_fc(h, fn, frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, leaves, batch, stack, batch_mean_divisor, flags,
-                                    stream);
-        h->is_weight = nullptr; h->td_abs = nullptr;
-        if (rc) return rc;
-        if (i + 1 < n_steps) {
-            if ((rc = per_turn(per->nodes_dev, per->depth, leaves, td, K, batch, per->reduce_max, per->eps, per->alpha, pri, per->max_priority_dev,
-                               per->tree_scratch_dev, u + o + batch, per->stratified, per->n_items, per->beta, leaves + batch,
-                               per->weights_dev + o + batch, stream)))
-                return rc;
-            tl_mark(h, q, "k_per_turn");
-        } else {
-            if ((rc = per_write_back(per->nodes_dev, per->depth, leaves, td, K, batch, per->reduce_max, per->eps, per->alpha, pri,
-                                     per->max_priority_dev, per->tree_scratch_dev, stream)))
-                return rc;
-            tl_mark(h, q, "k_per_write_back");
-        }
-        // the last launch that reads the staged uniforms: k_per_draw of a single step, else the last k_per_turn
-        if (i == std::max(0, n_steps - 2) && (rc = steps_stage_guard(h, blk, q))) return rc;
-    }
-    return IDQN_OK;
+    return per_learn_on_replay(h, fn, *per, nullptr, frame_ring_dev, n_frames, frame_bytes, rows_dev, n_steps, batch, stack, batch_mean_divisor,
+                               flags, stream, true);
 }
 
 // One i-IQN gradient step (include/idqn_hip.h).  With idqn_set_per_buffers the loss launch takes the importance weights and
@@ -3786,7 +3761,7 @@ extern "C" int idqn_group_create(const idqn_handle_t* members, int32_t n_members
     G->m.assign(members, members + n_members);
     G->slots_off = ((size_t)n_members * sizeof(FcGroupMember) + 15) & ~(size_t)15;
     // the prioritized call (idqn_group_per_learn_on_replay_fc) puts its tree records and uniforms where the slots go
-    G->uni_off = G->slots_off + (((size_t)n_members * sizeof(PerGroupMember) + 15) & ~(size_t)15);
+    G->uni_off = G->slots_off + (((size_t)n_members * sizeof(PerSampler) + 15) & ~(size_t)15);
     G->block_bytes = std::max(G->slots_off + (size_t)n_members * STEPS_SLOTS_BYTES, G->uni_off + (size_t)n_members * PER_GROUP_MAX_N * 8);
     *out = G;
     return IDQN_OK;
@@ -3881,7 +3856,7 @@ extern "C" int idqn_group_learn_on_replay_fc(idqn_group_t G, const idqn_group_ri
     return group_launch(G, rings, slots_host, batch, 0, batch, mean_divisor, (flags & IDQN_F_GRADS_ONLY) != 0, (hipStream_t)stream);
 }
 
-// The prioritized step of every member as ONE call (include/idqn_hip.h): block = {FcGroupMember[S], PerGroupMember[S], uniforms
+// The prioritized step of every member as ONE call (include/idqn_hip.h): block = {FcGroupMember[S], PerSampler[S], uniforms
 // [S][batch]} in the group's staging ring -> one copy -> k_per_group_draw (S) -> k_fc_group_step (K, S) on the members' leaves,
 // weights and |TD| (they travel in the table: the members' own h->is_weight / h->td_abs stay unset) -> k_per_group_write_back (S).
 // Every refusal comes before anything is enqueued, allocated or staged.
@@ -3918,7 +3893,7 @@ extern "C" int idqn_group_per_learn_on_replay_fc(idqn_group_t G, const idqn_grou
     if (G->busy[blk]) IDQN_HIP_CHECK(hipEventSynchronize(G->ev[blk]));  // the launches that read this block are done
     G->busy[blk] = false;
     FcGroupMember* tab = (FcGroupMember*)G->pin[blk];
-    PerGroupMember* ptab = (PerGroupMember*)(G->pin[blk] + G->slots_off);
+    PerSampler* ptab = (PerSampler*)(G->pin[blk] + G->slots_off);
     double* uni_pin = (double*)(G->pin[blk] + G->uni_off);
     const double* uni_dev = (const double*)(G->dev[blk] + G->uni_off);
     for (int g = 0; g < S; ++g) {
@@ -3927,23 +3902,16 @@ extern "C" int idqn_group_per_learn_on_replay_fc(idqn_group_t G, const idqn_grou
         group_fill_member(tab[g], G->m[g], rings[g], false, batch, mean_divisor, false, p.leaves_dev);
         tab[g].a.is_weight = p.weights_dev;
         tab[g].a.td_abs = p.td_abs_dev;
-        PerGroupMember& m = ptab[g];
-        memset(&m, 0, sizeof(m));
-        m.nodes = p.nodes_dev; m.uniforms = uni_dev + (size_t)g * batch; m.leaves = p.leaves_dev; m.weights = p.weights_dev;
-        m.td_abs = p.td_abs_dev; m.priorities = p.priorities_dev; m.max_dev = p.max_priority_dev; m.scratch = (double*)p.tree_scratch_dev;
-        m.n_items = (double)p.n_items; m.beta = p.beta; m.eps = p.eps; m.alpha = p.alpha;
-        m.depth = p.depth; m.stratified = p.stratified; m.reduce_max = p.reduce_max; m.K = K;
+        ptab[g] = per_sampler_of(p, uni_dev + (size_t)g * batch, K);
     }
     IDQN_HIP_CHECK(hipMemcpyAsync(G->dev[blk], G->pin[blk], G->uni_off + (size_t)S * batch * 8, hipMemcpyHostToDevice, q));
     G->next = (blk + 1) % IDQN_STEPS_STAGING_DEPTH;
     const idqn_handle_t h0 = G->m[0];
-    const PerGroupMember* ptab_dev = (const PerGroupMember*)(G->dev[blk] + G->slots_off);
-    int m2 = 1;
-    while (m2 < batch) m2 <<= 1;
+    const PerSampler* ptab_dev = (const PerSampler*)(G->dev[blk] + G->slots_off);
     hipLaunchKernelGGL(k_per_group_draw, dim3((unsigned)S), dim3(PER_GROUP_DRAW_T), 0, q, ptab_dev, (int)batch);
     hipLaunchKernelGGL(k_fc_group_step, dim3((unsigned)K, (unsigned)S), dim3(FCM_T), (size_t)h0->fcp_plan_.floats * 4, q,
                        (const FcGroupMember*)G->dev[blk], 1);
-    hipLaunchKernelGGL(k_per_group_write_back, dim3((unsigned)S), dim3(ST_THREADS), 0, q, ptab_dev, (int)batch, m2);
+    hipLaunchKernelGGL(k_per_group_write_back, dim3((unsigned)S), dim3(ST_THREADS), 0, q, ptab_dev, (int)batch, st_pow2_at_least(batch));
     IDQN_HIP_CHECK(hipGetLastError());
     IDQN_HIP_CHECK(hipEventRecord(G->ev[blk], q));
     G->busy[blk] = true;

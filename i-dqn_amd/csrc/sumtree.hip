@@ -17,7 +17,6 @@
 
 #include "common.h"
 #include "sumtree_device.h"
-#include "per_step_args.h"
 #include "per_step_kernels.h"
 #include "per_turn_kernels.h"
 
@@ -109,10 +108,8 @@ extern "C" int sumtree_set(double* nodes_dev, int32_t depth, const int32_t* indi
     IDQN_REQUIRE(nodes_dev && indices_dev && values_dev && scratch_dev, "sumtree_set: null pointer");
     IDQN_REQUIRE(depth >= 1 && depth <= 31, "sumtree_set: depth %d out of range", depth);
     IDQN_REQUIRE(n >= 1 && n <= ST_MAX_N, "sumtree_set: n = %d, must be in [1, %d]", n, ST_MAX_N);
-    int m = 1;
-    while (m < n) m <<= 1;
     hipLaunchKernelGGL(k_sumtree_set, dim3(1), dim3(ST_THREADS), 0, (hipStream_t)stream, nodes_dev, depth, indices_dev,
-                       values_dev, n, m, (double*)scratch_dev);
+                       values_dev, n, st_pow2_at_least(n), (double*)scratch_dev);
     IDQN_HIP_CHECK(hipGetLastError());
     return IDQN_OK;
 }
@@ -461,7 +458,8 @@ extern "C" int per_priorities_from_td_gathered(const float* td_all_dev, int32_t 
 }
 
 // ---------------------------------------------------------------------------------------------------
-// The two ends of a prioritized learner step as one launch each (per_step_kernels.h; include/idqn_hip.h).
+// The two ends of a prioritized learner step as one launch each, and the turn between two steps (per_step_kernels.h,
+// per_turn_kernels.h: the phases of per_phases.h; include/idqn_hip.h).
 // ---------------------------------------------------------------------------------------------------
 // k_per_draw's arrival counter: one per stream (launches on a stream run one after the other and each leaves its counter at
 // zero), made on the stream's first call and kept for the life of the process.
@@ -486,14 +484,16 @@ static int per_draw_counter(hipStream_t q, unsigned** out) {
     return IDQN_OK;
 }
 
+// Each entry: check the record (per_step_args.h), launch on it.
 extern "C" int per_draw(const double* nodes_dev, int32_t depth, const double* uniforms_dev, int32_t n, int32_t stratified,
                         int64_t n_items, double beta, int32_t* leaves_out_dev, float* weights_out_dev, void* stream) {
-    const char* bad = per_draw_args_error(nodes_dev, depth, uniforms_dev, n, n_items, leaves_out_dev, weights_out_dev);
+    const PerSampler s = per_sampler(nodes_dev, depth, n_items, uniforms_dev, stratified, beta, leaves_out_dev, weights_out_dev, nullptr, 0, 0,
+                                     0.0, 0.0, nullptr, nullptr, nullptr);
+    const char* bad = per_draw_args_error(s, n);
     IDQN_REQUIRE(!bad, "per_draw: %s (depth %d, n %d, n_items %ld)", bad, depth, n, (long)n_items);
     unsigned* arrivals = nullptr;
     if (const int rc = per_draw_counter((hipStream_t)stream, &arrivals)) return rc;
-    hipLaunchKernelGGL(k_per_draw, dim3(cdiv(n, 4)), dim3(256), 0, (hipStream_t)stream, nodes_dev, depth, uniforms_dev, n, stratified,
-                       (double)n_items, beta, leaves_out_dev, weights_out_dev, arrivals);
+    hipLaunchKernelGGL(k_per_draw, dim3(cdiv(n, 4)), dim3(PER_STEP_MAX_N), 0, (hipStream_t)stream, s, n, arrivals);
     IDQN_HIP_CHECK(hipGetLastError());
     return IDQN_OK;
 }
@@ -501,12 +501,11 @@ extern "C" int per_draw(const double* nodes_dev, int32_t depth, const double* un
 extern "C" int per_write_back(double* nodes_dev, int32_t depth, const int32_t* leaves_dev, const float* td_abs_dev, int32_t n_heads,
                               int32_t n, int32_t reduce_max, double eps, double alpha, double* priorities_out_dev,
                               double* max_priority_dev, void* scratch_dev, void* stream) {
-    const char* bad = per_write_back_args_error(nodes_dev, depth, leaves_dev, td_abs_dev, n_heads, n, scratch_dev);
+    const PerSampler s = per_sampler(nodes_dev, depth, 0, nullptr, 0, 0.0, leaves_dev, nullptr, td_abs_dev, n_heads, reduce_max, eps, alpha,
+                                     priorities_out_dev, max_priority_dev, scratch_dev);
+    const char* bad = per_write_back_args_error(s, n);
     IDQN_REQUIRE(!bad, "per_write_back: %s (depth %d, n %d, n_heads %d)", bad, depth, n, n_heads);
-    int m = 1;
-    while (m < n) m <<= 1;
-    hipLaunchKernelGGL(k_per_write_back, dim3(1), dim3(ST_THREADS), 0, (hipStream_t)stream, nodes_dev, depth, leaves_dev, td_abs_dev,
-                       n_heads, n, m, reduce_max, eps, alpha, priorities_out_dev, max_priority_dev, (double*)scratch_dev);
+    hipLaunchKernelGGL(k_per_write_back, dim3(1), dim3(ST_THREADS), 0, (hipStream_t)stream, s, n, st_pow2_at_least(n));
     IDQN_HIP_CHECK(hipGetLastError());
     return IDQN_OK;
 }
@@ -516,13 +515,15 @@ extern "C" int per_turn(double* nodes_dev, int32_t depth, const int32_t* leaves_
                         int32_t reduce_max, double eps, double alpha, double* priorities_out_dev, double* max_priority_dev,
                         void* scratch_dev, const double* next_uniforms_dev, int32_t stratified, int64_t n_items, double beta,
                         int32_t* next_leaves_out_dev, float* next_weights_out_dev, void* stream) {
-    const char* bad = per_write_back_args_error(nodes_dev, depth, leaves_dev, td_abs_dev, n_heads, n, scratch_dev);
-    if (!bad) bad = per_draw_args_error(nodes_dev, depth, next_uniforms_dev, n, n_items, next_leaves_out_dev, next_weights_out_dev);
+    const PerSampler s = per_sampler(nodes_dev, depth, n_items, nullptr, stratified, beta, leaves_dev, nullptr, td_abs_dev, n_heads, reduce_max, eps,
+                                     alpha, priorities_out_dev, max_priority_dev, scratch_dev);
+    PerSampler next = s;  // (the records k_per_turn builds from its flat arguments)
+    next.uniforms = next_uniforms_dev; next.leaves = next_leaves_out_dev; next.weights = next_weights_out_dev;
+    const char* bad = per_write_back_args_error(s, n);
+    if (!bad) bad = per_draw_args_error(next, n);
     IDQN_REQUIRE(!bad, "per_turn: %s (depth %d, n %d, n_heads %d, n_items %ld)", bad, depth, n, n_heads, (long)n_items);
-    int m = 1;
-    while (m < n) m <<= 1;
     hipLaunchKernelGGL(k_per_turn, dim3(1), dim3(ST_THREADS), 0, (hipStream_t)stream, nodes_dev, depth, leaves_dev, td_abs_dev, n_heads, n,
-                       m, reduce_max, eps, alpha, priorities_out_dev, max_priority_dev, (double*)scratch_dev, next_uniforms_dev, stratified,
+                       st_pow2_at_least(n), reduce_max, eps, alpha, priorities_out_dev, max_priority_dev, (double*)scratch_dev, next_uniforms_dev, stratified,
                        (double)n_items, beta, next_leaves_out_dev, next_weights_out_dev);
     IDQN_HIP_CHECK(hipGetLastError());
     return IDQN_OK;

@@ -1,4 +1,4 @@
-// Device functions the sum-tree kernels (sumtree.hip) and the fused prioritized-replay kernels (per_step_kernels.h) share:
+// Device functions the sum-tree kernels (sumtree.hip) and the phases of the fused prioritized-replay kernels (per_phases.h) share:
 // the wave descent, the body of the batched set, and the target / weight / priority formulas.  One definition each, so the
 // fused kernels are bit-identical to the launches they replace by construction.
 #pragma once
@@ -6,6 +6,12 @@
 
 #define ST_THREADS 1024
 #define ST_MAX_N 4096
+
+static inline int st_pow2_at_least(int n) {  // (host) m of the batched set: n rounded up to a power of two
+    int m = 1;
+    while (m < n) m <<= 1;
+    return m;
+}
 
 // Latency-oriented descent for minibatch-sized queries: ONE WAVE PER QUERY.  The 2^(s+1)-1 nodes of the s <= 5
 // levels below the current node are fetched by the 64 lanes in one round trip, then the wave descends those levels
@@ -232,7 +238,7 @@ struct StValuesGlobal {
     __device__ __forceinline__ double operator()(int i) const { return v[i]; }
 };
 
-// val(i) of the write-back's set (per_write_back_body.h): the priorities the same workgroup has just left in LDS
+// val(i) of the write-back's set (per_write_back_phase, per_phases.h): the priorities the same workgroup has just left in LDS
 struct StValuesLds {
     const double* v;
     __device__ __forceinline__ double operator()(int i) const { return v[i]; }

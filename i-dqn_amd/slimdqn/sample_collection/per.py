@@ -173,9 +173,24 @@ class PrioritizedLearner:
                 return view, family
         return None
 
+    @staticmethod
+    def _vp(t):
+        return None if t is None else int(t.data_ptr())
+
+    def _fill_sampler_args(self, p, u, leaves, weights, td_abs, priorities):
+        """The fields ``_hip.PerStep`` and ``_hip.PerSteps`` have in common, written into ``p``: the tree, the sampler's settings,
+        host uniforms ``u`` and the four output tensors."""
+        tree, vp = self.sampler._sum_tree, self._vp
+        p.nodes_dev, p.depth, p.n_items = vp(tree._nodes_dev), tree._depth, len(self.sampler)
+        p.uniforms_host = u.ctypes.data
+        p.stratified, p.reduce_max, p.beta, p.eps, p.alpha = self.stratified, self.reduce_max, self.beta, self.eps, self.sampler._alpha
+        p.max_priority_dev = vp(self.sampler._max_priority_dev)
+        p.leaves_dev, p.weights_dev, p.td_abs_dev, p.priorities_dev = vp(leaves), vp(weights), vp(td_abs), vp(priorities)
+        p.tree_scratch_dev = vp(tree._scratch)
+
     def _step_fused(self, view, u, taus):
         """The library's code for the one-call step on ring ``view`` with uniforms ``u`` (float64 [B], host)."""
-        rb, tree, agent = self.rb, self.sampler._sum_tree, self.agent
+        rb, agent = self.rb, self.agent
         B = rb._batch_size
         frames, n_frames, frame_bytes, rows, stack = view[:5]
         if taus is not None:
@@ -184,14 +199,8 @@ class PrioritizedLearner:
         p = self.__dict__.get("_per_args")
         if p is None:
             p = self._per_args = _hip.PerStep()
-        vp = lambda t: None if t is None else int(t.data_ptr())  # noqa: E731
-        p.nodes_dev, p.depth, p.n_items = vp(tree._nodes_dev), tree._depth, len(self.sampler)
-        p.uniforms_host = u.ctypes.data
-        p.stratified, p.reduce_max, p.beta, p.eps, p.alpha = self.stratified, self.reduce_max, self.beta, self.eps, self.sampler._alpha
-        p.max_priority_dev = vp(self.sampler._max_priority_dev)
-        p.leaves_dev, p.weights_dev, p.td_abs_dev = vp(self._leaves), vp(self._weights), vp(self._td_abs)
-        p.priorities_dev, p.tree_scratch_dev = vp(self._priorities), vp(tree._scratch)
-        p.tau_dev = vp(agent._tau_dev) if taus is not None else None
+        self._fill_sampler_args(p, u, self._leaves, self._weights, self._td_abs, self._priorities)
+        p.tau_dev = self._vp(agent._tau_dev) if taus is not None else None
         return _hip.lib().idqn_per_learn_on_replay(agent._handle, C.byref(p), _hip.ptr(frames), int(n_frames), int(frame_bytes),
                                                    _hip.ptr(rows), B, int(stack), B, 0, _hip.current_stream())
 
@@ -257,7 +266,7 @@ class PrioritizedLearner:
         """The library's code for the n-step call on ring ``view`` with uniforms ``U`` (float64 [m][B], host, contiguous)."""
         import torch
 
-        rb, tree, agent = self.rb, self.sampler._sum_tree, self.agent
+        rb, agent = self.rb, self.agent
         B, K, m = rb._batch_size, agent._K, U.shape[0]
         frames, n_frames, frame_bytes, rows, stack = view[:5]
         agent._ensure_handle(B)
@@ -271,13 +280,7 @@ class PrioritizedLearner:
         p = self.__dict__.get("_per_steps_args")
         if p is None:
             p = self._per_steps_args = _hip.PerSteps()
-        vp = lambda t: None if t is None else int(t.data_ptr())  # noqa: E731
-        p.nodes_dev, p.depth, p.n_items = vp(tree._nodes_dev), tree._depth, len(self.sampler)
-        p.uniforms_host = U.ctypes.data
-        p.stratified, p.reduce_max, p.beta, p.eps, p.alpha = self.stratified, self.reduce_max, self.beta, self.eps, self.sampler._alpha
-        p.max_priority_dev = vp(self.sampler._max_priority_dev)
-        p.leaves_dev, p.weights_dev, p.td_abs_dev, p.priorities_dev = (vp(t) for t in rows_out)
-        p.tree_scratch_dev = vp(tree._scratch)
+        self._fill_sampler_args(p, U, *rows_out)
         rc = _hip.lib().idqn_per_learn_steps_on_replay(agent._handle, C.byref(p), _hip.ptr(frames), int(n_frames), int(frame_bytes),
                                                        _hip.ptr(rows), m, B, int(stack), B, 0, _hip.current_stream())
         if rc == 0:  # the learner's own buffers are the last step's rows, as m ``step()`` calls leave them
@@ -435,15 +438,9 @@ class PrioritizedGroupLearner:
         per = self.__dict__.get("_per_args")
         if per is None:
             per = self._per_args = (_hip.PerStep * len(self.learners))()
-        vp = lambda t: None if t is None else int(t.data_ptr())  # noqa: E731
         for p, lr, u in zip(per, self.learners, us):
-            tree = lr.sampler._sum_tree
-            p.nodes_dev, p.depth, p.n_items = vp(tree._nodes_dev), tree._depth, len(lr.sampler)
-            p.uniforms_host = u.ctypes.data
-            p.stratified, p.reduce_max, p.beta, p.eps, p.alpha = lr.stratified, lr.reduce_max, lr.beta, lr.eps, lr.sampler._alpha
-            p.max_priority_dev = vp(lr.sampler._max_priority_dev)
-            p.leaves_dev, p.weights_dev, p.td_abs_dev = vp(lr._leaves), vp(lr._weights), vp(lr._td_abs)
-            p.priorities_dev, p.tree_scratch_dev, p.tau_dev = vp(lr._priorities), vp(tree._scratch), None
+            lr._fill_sampler_args(p, u, lr._leaves, lr._weights, lr._td_abs, lr._priorities)
+            p.tau_dev = None
         return _hip.lib().idqn_group_per_learn_on_replay_fc(g, self.group._rings(views), per, B, B, 0, _hip.current_stream())
 
     def step(self):

@@ -400,8 +400,8 @@ int idqn_group_learn_steps_on_replay_fc(idqn_group_t group, const idqn_group_rin
  * pointers, the S tree records and the S x batch uniforms travel in ONE pinned block of the group's staging ring (the event
  * guard of the other learner entries): one asynchronous copy, then THREE launches -- k_per_group_draw (grid S: the draws and
  * weights of every member), k_fc_group_step (grid (K, S), slots = member g's leaves_dev) and k_per_group_write_back (grid S)
- * (csrc/per_group_kernels.h).  No host synchronisation, no allocation after the first call, no per-member launch; the
- * members' own prioritized-replay pointers (idqn_set_per_buffers) stay unset throughout.
+ * (csrc/per_group_kernels.h: the phases of csrc/per_phases.h on record g).  No host synchronisation, no allocation after the
+ * first call, no per-member launch; the members' own prioritized-replay pointers (idqn_set_per_buffers) stay unset throughout.
  * CONTRACT: for every member, online parameters, moments, count, losses, cum_losses, tree nodes, max_priority_dev, leaves,
  * weights, |TD| and priorities after the call equal, byte for byte, what idqn_per_learn_on_replay leaves on that member
  * alone for the same uniforms on the same stream.

@@ -212,7 +212,7 @@ def test_base_four_calls_back_to_back(K, each):
     assert len({d["_leaves"].cpu().numpy().tobytes() for d in last}) == 3, "the members' descents were meant to differ"
 
 
-@pytest.mark.parametrize("B_seq", [[5, 5], [1, 1], [32, 5, 32]])
+@pytest.mark.parametrize("B_seq", [[5, 5], [1, 1], [32, 5, 32], [16, 17]])
 def test_ragged_and_minimal_batches(B_seq):
     """Pad lanes and the workgroup shape: batches that fill no wave round, and a small batch after a full one on one group."""
     members, twins = _sets(2, B=max(B_seq))

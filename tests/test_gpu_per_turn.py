@@ -9,7 +9,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-NS = [1, 4, 5, 32, 33, 256]
+NS = [1, 4, 5, 16, 17, 32, 33, 256]  # 16, 17: a full round of the 16 waves, and one descent into the second round
 EPS, ALPHA, BETA = 1e-3, 0.6, 0.4
 
 

@@ -1,5 +1,5 @@
 """What the prioritized step of a seed group costs as one call (``idqn_group_per_learn_on_replay_fc``: k_per_group_draw, the group
-step, k_per_group_write_back -- csrc/per_group_kernels.h) against its members stepped one after the other, on the LunarLander
+step, k_per_group_write_back -- csrc/per_group_kernels.h, csrc/per_phases.h) against its members stepped one after the other, on the LunarLander
 net (fc, obs 8, [100, 100], A = 4, K = 3, B = 32) at S = 1, 2, 4, 8, 16, 32 members:
 
   group   one ``PrioritizedGroupLearner.step()`` through the group call (S host draws, one C call, three launches)
