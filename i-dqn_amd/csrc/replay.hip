@@ -350,3 +350,26 @@ extern "C" int replay_group_add_step(int32_t n_members, const replay_group_membe
     IDQN_HIP_CHECK(hipGetLastError());
     return IDQN_OK;
 }
+
+// One vector step of a seed group of VectorReplayBuffers as one call (include/idqn_hip.h, replay_group_add_many); the checks are
+// host C++ of their own (replay_group_many_args.h) and run before the block is written and before anything is enqueued.
+#include "replay_group_many_args.h"
+static_assert(REPLAY_MANY_MAX_MEMBERS == REPLAY_GROUP_MAX_MEMBERS && REPLAY_MANY_MAX_IN == REPLAY_STEP_MAX_IN &&
+                  REPLAY_MANY_MAX_WRITES == REPLAY_STEP_MAX_WRITES && REPLAY_MANY_MAX_ROWS == REPLAY_STEP_MAX_ROWS,
+              "replay_group_add_many takes replay_add_step's limits per member");
+
+extern "C" int replay_group_add_many(int32_t n_members, const replay_group_many_member_t* members, void* block_host_pinned,
+                                     void* block_staging_dev, int64_t block_bytes, void* stream) {
+    int g = -1, j = -1;
+    const char* bad = replay_group_many_args_error(n_members, members, block_host_pinned, block_staging_dev, block_bytes, &g, &j);
+    IDQN_REQUIRE(!bad, "replay_group_add_many: member %d (with member %d): %s", g, j, bad ? bad : "");
+    int width = 0;
+    for (int i = 0; i < n_members; ++i)
+        width = std::max(width, members[i].n_writes * replay_group_chunks((long)members[i].frame_bytes) + (int)cdiv((long)members[i].n_rows * 8, 256));
+    memmove(block_host_pinned, members, (size_t)n_members * sizeof(replay_group_many_member_t));  // the records travel at the head of the block
+    IDQN_HIP_CHECK(hipMemcpyAsync(block_staging_dev, block_host_pinned, (size_t)block_bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
+    hipLaunchKernelGGL(k_replay_group_add_many, dim3(width, n_members), dim3(256), 0, (hipStream_t)stream,
+                       (const uint8_t*)block_staging_dev, (long)block_bytes);
+    IDQN_HIP_CHECK(hipGetLastError());
+    return IDQN_OK;
+}

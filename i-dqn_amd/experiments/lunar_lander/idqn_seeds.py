@@ -1,39 +1,55 @@
 """`python experiments/lunar_lander/idqn_seeds.py -en NAME --first_seed A --last_seed B ...` -- the seeds A .. B of
 `experiments/lunar_lander/idqn.py` in ONE process (the reference's `launch_job/lunar_lander/train.sh` starts one process per
 seed): one acting call and one learner call per step for all of them (experiments/base/seeds.py).  Every other flag is the
-single-seed entry point's, unchanged; `-s` is set per seed.  ``envs`` defaults to the synthetic stand-in environment."""
+single-seed entry point's, unchanged; `-s` is set per seed.  ``envs`` defaults to the synthetic stand-in environment.
+`--n_envs E` (default 1: the path above, unchanged) gives every seed E environments and a `VectorReplayBuffer`: S x E time lines
+per lock-step iteration (`SeedVectorTrainer`); ``envs`` is then a list of E environments per seed."""
 import argparse
 import sys
 
 from experiments.base.launch import ENVIRONMENTS, default_environment, make_agent, observation_dim
-from experiments.base.seeds import train_seeds
+from experiments.base.seeds import train_seeds, train_seeds_vector
 from experiments.base.utils import prepare_logs, save_data
 from slimdqn import prng
 from slimdqn.sample_collection.replay_buffer import ReplayBuffer
 from slimdqn.sample_collection.samplers import UniformSamplingDistribution
+from slimdqn.sample_collection.vector_replay_buffer import MAX_ENVS, VectorReplayBuffer
 
 
 def run(argvs=sys.argv[1:], envs=None, save_root=None):
     ap = argparse.ArgumentParser(add_help=False)
     ap.add_argument("--first_seed", type=int, required=True)
     ap.add_argument("--last_seed", type=int, required=True)
+    ap.add_argument("--n_envs", type=int, default=1)
     own, rest = ap.parse_known_args(argvs)
     seeds = list(range(own.first_seed, own.last_seed + 1))
     if not 1 <= len(seeds) <= 32:
         raise SystemExit(f"--first_seed .. --last_seed must name 1..32 seeds, got {len(seeds)}")
+    E = own.n_envs
+    if not 1 <= E <= MAX_ENVS:
+        raise SystemExit(f"--n_envs must be in 1..{MAX_ENVS}, got {E}")
     consts = ENVIRONMENTS["lunar_lander"]
     ps, keys, agents, rbs = [], [], [], []
-    envs = list(envs) if envs is not None else [default_environment("lunar_lander", s) for s in seeds]
+    if envs is not None:
+        envs = list(envs)
+    elif E == 1:
+        envs = [default_environment("lunar_lander", s) for s in seeds]
+    else:  # environment e of seed s: a stream of its own
+        envs = [[default_environment("lunar_lander", 1000 * e + s) for e in range(E)] for s in seeds]
     for seed, env in zip(seeds, envs):  # the wiring of experiments/base/launch.py, per seed
         p = prepare_logs("lunar_lander", "idqn", list(rest) + ["-s", str(seed)], save_root)
         agent_key, train_key = prng.split(prng.PRNGKey(p["seed"]))
-        rb = ReplayBuffer(UniformSamplingDistribution(p["seed"]), batch_size=p["batch_size"], max_capacity=p["replay_buffer_capacity"],
-                          stack_size=consts["stack_size"], update_horizon=p["update_horizon"], gamma=p["gamma"],
-                          clipping=consts["clipping"], compress=True)
+        shared = dict(batch_size=p["batch_size"], max_capacity=p["replay_buffer_capacity"], stack_size=consts["stack_size"],
+                      update_horizon=p["update_horizon"], gamma=p["gamma"], clipping=consts["clipping"], compress=True)
+        if E == 1:
+            rb = ReplayBuffer(UniformSamplingDistribution(p["seed"]), **shared)
+        else:
+            rb = VectorReplayBuffer(UniformSamplingDistribution(p["seed"]), n_envs=E, **shared)
         rb.reuse_sample_buffers = True
-        agents.append(make_agent("idqn", agent_key, observation_dim("lunar_lander", env), env.n_actions, p, consts["adam_eps"]))
+        env0 = env if E == 1 else env[0]
+        agents.append(make_agent("idqn", agent_key, observation_dim("lunar_lander", env0), env0.n_actions, p, consts["adam_eps"]))
         ps.append(p), keys.append(train_key), rbs.append(rb)
-    train_seeds(keys, ps, agents, envs, rbs, save_fn=save_data)
+    (train_seeds if E == 1 else train_seeds_vector)(keys, ps, agents, envs, rbs, save_fn=save_data)
     return ps, agents
 
 

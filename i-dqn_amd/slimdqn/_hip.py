@@ -77,6 +77,13 @@ class GroupAddMember(C.Structure):
                 ("rows_offset", C.c_int64)]
 
 
+class GroupAddManyMember(C.Structure):
+    """replay_group_many_member_t: one member's record of ``replay_group_add_many`` (80 bytes)."""
+    _fields_ = [("ring_dev", C.c_void_p), ("rows_dev", C.c_void_p), ("n_frames", C.c_int64), ("frame_bytes", C.c_int64),
+                ("capacity", C.c_int64), ("n_in", C.c_int32), ("n_writes", C.c_int32), ("n_rows", C.c_int32), ("reserved", C.c_int32),
+                ("pairs_offset", C.c_int64), ("rows_offset", C.c_int64), ("frames_offset", C.c_int64)]
+
+
 # every exported symbol of include/idqn_hip.h: (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -164,6 +171,7 @@ SYMBOLS = {
     "replay_add_frame": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P]),
     "replay_add_step": (C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int64, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
     "replay_group_add_step": (C.c_int, [C.c_int32, _P, _P, _P, C.c_int64, _P]),
+    "replay_group_add_many": (C.c_int, [C.c_int32, _P, _P, _P, C.c_int64, _P]),
     "replay_ring_regrow": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P]),
     "replay_gather_scalars": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, _P, _P, _P]),
 }

@@ -165,3 +165,135 @@ class GroupCollector:
         blk["event"].record()
         blk["used"] = True
         self._turn += 1
+
+
+VECTOR_RECORD_BYTES = 80  # sizeof(replay_group_many_member_t)
+
+
+class GroupVectorCollector(GroupCollector):
+    """``GroupCollector`` for members that are ``VectorReplayBuffer`` objects: one vector step of S seeds, E_g time lines each, as
+    ONE call (``replay_group_add_many``, csrc/replay_group_kernels.h).  ``add_many`` runs the host half of every member's
+    ``add_many`` (``VectorReplayBuffer._add_many_host``: allocation, the segment plan, ring growth, the sampler, the counters), in
+    member order, and sends all device halves as one pinned block, one asynchronous copy and one launch:
+
+        replay_group_many_member_t [n]   the member records (ring, rows, sizes, counts, where its tables and frames lie)
+        per member, 4-byte aligned       int32 [n_writes][2] (frame index, ring slot) pairs; int32 [n_rows] element slots +
+                                         int32 [n_rows][8] rows
+        per member, 16-byte aligned      its new frames, [n_in][frame_bytes]
+
+    Afterwards every buffer is in the state its own ``add_many`` would have left.  The staging ring (``DEPTH`` pinned / device block
+    pairs, one event each) is ``GroupCollector``'s."""
+
+    # The group sizes S (members that step in a call) at which the one call is the default: those where its median lay below the
+    # minimum of the S solo ``add_many`` calls at E = 2 AND at E = 8 (tools/bench_group_vector_collect.py ->
+    # profiles/group_vector_collect.json: true at S = 2, 4, 8 and 16 with a margin that grows with S -- 78.4 against 90.0 us at
+    # S = 2, E = 2; 987.8 against 1196.4 us at S = 16, E = 8 -- so the sizes between the measured ones are taken with them; at
+    # S = 1 the call is the slower leg, 49.6 against 46.1 us at E = 2 and 86.0 against 82.4 us at E = 8; S = 17 .. 32 were not
+    # measured and stay off).  Other sizes run the members' own ``add_many``; ``force=True`` / ``False`` overrides the table.
+    group_add_many_sizes = frozenset(range(2, 17))
+
+    def __init__(self, replay_buffers, force=None):
+        self.replay_buffers = list(replay_buffers)
+        self.force = force
+        self._vector = [self._is_vector(rb) for rb in self.replay_buffers]
+        self._static = [None] * len(self.replay_buffers)
+        self._blocks, self._block_bytes, self._turn = [], 0, 0
+        self.group_calls = 0
+
+    @staticmethod
+    def _is_vector(rb) -> bool:
+        """A ``VectorReplayBuffer`` whose ``add_many`` and its two halves are the class's own."""
+        from slimdqn.sample_collection.vector_replay_buffer import VectorReplayBuffer as V
+
+        t = type(rb)
+        return (isinstance(rb, V) and t.add_many is V.add_many and t._add_many_host is V._add_many_host and t._plan_many is V._plan_many
+                and t._finish_many is V._finish_many and t._issue_step is V._issue_step and t._issue is V._issue)
+
+    def _route(self, n) -> bool:
+        if self.__dict__.get("_group_add_many_ok") is False or not 1 <= n <= _hip.REPLAY_GROUP_MAX_MEMBERS:
+            return False
+        return bool(self.force) if self.force is not None else n in self.group_add_many_sizes
+
+    @staticmethod
+    def _solo(rb, entries, **kwargs) -> None:
+        """A member's own route: ``add_many``, or -- a buffer without one -- ``add`` per entry."""
+        if hasattr(rb, "add_many"):
+            rb.add_many(entries, **kwargs)
+        else:
+            for tr in entries:
+                if tr is not None:
+                    rb.add(tr, **kwargs)
+
+    def add_many(self, transitions, members=None, **kwargs) -> None:
+        """``transitions[i]``: the list of E entries (a transition or ``None`` each) of buffer ``members[i]`` (default: one list per
+        buffer, in order); ``kwargs`` go to every sampler's ``add`` as through ``rb.add_many(entries, **kwargs)``."""
+        rbs = self.replay_buffers
+        members = range(len(transitions)) if members is None else list(members)
+        assert len(members) == len(transitions) and len(set(members)) == len(members), "one list of entries per named buffer"
+        stepping = sum(1 for m, trs in zip(members, transitions) if self._vector[m] and any(tr is not None for tr in trs))
+        if not self._route(stepping):
+            for m, trs in zip(members, transitions):
+                self._solo(rbs[m], trs, **kwargs)
+            return
+        # the host half of every member's add_many, in member order; whoever cannot join sends its device half itself, now
+        joint, nbytes = [], 0
+        for m, trs in zip(members, transitions):
+            rb = rbs[m]
+            if not self._vector[m]:
+                self._solo(rb, trs, **kwargs)
+                continue
+            grown = rb._plan.n_growths
+            host = rb._add_many_host(trs, **kwargs)
+            if host is None:  # (no environment of this member stepped)
+                continue
+            frames, writes, slots = host
+            if rb._plan.n_growths != grown or len(slots) > _hip.REPLAY_STEP_MAX_ROWS:
+                rb._issue_step(frames, writes, slots)
+                continue
+            joint.append((m, rb, frames, writes, slots))
+            nbytes += 8 * len(writes) + 36 * len(slots) + ((len(frames) * rb._frame_bytes + 15) & ~15)
+        if not joint:
+            return
+        n = len(joint)
+        head = VECTOR_RECORD_BYTES * n
+        nbytes += head + 16
+        self._ensure_blocks(nbytes)
+        blk = self._blocks[self._turn % self.DEPTH]
+        if blk["used"]:
+            blk["event"].synchronize()  # the copy that last read this block (DEPTH calls ago) has passed
+        u8, i32, i64 = blk["u8"], blk["i32"], blk["i64"]
+        at, tables = head, []  # the tables first (4-byte granules), then the frames (16-byte aligned)
+        for _, rb, _, writes, slots in joint:
+            w, k, o = len(writes), len(slots), at >> 2
+            if w:
+                i32[o:o + 2 * w] = np.asarray(writes, np.int32).reshape(-1)
+            o += 2 * w
+            if k:
+                i32[o:o + k] = slots
+                i32[o + k:o + 9 * k] = rb._plan.rows[slots].reshape(-1)
+            tables.append((at, at + 8 * w))
+            at += 8 * w + 36 * k
+        for j, (m, rb, frames, writes, slots) in enumerate(joint):
+            at = (at + 15) & ~15
+            fb = rb._frame_bytes
+            for i, f in enumerate(frames):
+                u8[at + i * fb:at + (i + 1) * fb] = f.view(np.uint8).reshape(-1)
+            # replay_group_many_member_t: five int64, (n_in, n_writes) and (n_rows, 0) as int32 pairs, three offsets
+            i64[10 * j:10 * j + 10] = self._record_head(m, rb) + (len(frames) | (len(writes) << 32), len(slots)) + tables[j] + (at,)
+            at += len(frames) * fb
+        assert at <= nbytes <= self._block_bytes
+        lib, q = _hip.lib(), _hip.current_stream()
+        rc = lib.replay_group_add_many(n, blk["host"], blk["host"], blk["dev"], at, q)
+        if rc == _hip.E_INVALID and self.__dict__.get("_group_add_many_ok") is None:
+            # not this library / these buffers: the members' own add_many from now on, and the device half of THIS call by
+            # their own replay_add_step calls (the entry refuses before it writes or enqueues anything)
+            self._group_add_many_ok = False
+            for _, rb, frames, writes, slots in joint:
+                rb._issue_step(frames, writes, slots)
+            return
+        _hip.check(rc, "replay_group_add_many")
+        self._group_add_many_ok = True
+        self.group_calls += 1
+        blk["event"].record()
+        blk["used"] = True
+        self._turn += 1

@@ -284,17 +284,14 @@ class VectorReplayBuffer(ReplayBuffer):
         return blk
 
     # ---- reference API -------------------------------------------------------------------------------
-    def add_many(self, transitions: Sequence[Optional[TransitionElement]], **kwargs: Any) -> None:
-        """One transition per environment (``None``: that environment does not step): E frames and their elements go to
-        the device in one ``replay_add_step`` call (more only when a step makes more than 128 rows); ``kwargs`` go to the
-        sampler's ``add`` of every new key, as in ``ReplayBuffer.add``."""
-        from slimdqn import _hip
-
+    def _plan_many(self, transitions: Sequence[Optional[TransitionElement]]):
+        """The host work of a vector step up to the device call: allocation at the first frame, ``plan_step``, ring growth and
+        the de-duplicated slot list.  ``(frames, step, slots)``, or None when no environment stepped."""
         if len(transitions) != self._n_envs:
             raise ValueError(f"add_many takes {self._n_envs} entries (a transition or None per environment), got {len(transitions)}")
         frames = [np.ascontiguousarray(tr.observation) for tr in transitions if tr is not None]
         if not frames:
-            return
+            return None
         if self._frames is None:
             self._allocate(frames[0])
         for f in frames:
@@ -302,18 +299,50 @@ class VectorReplayBuffer(ReplayBuffer):
         step = self._plan.plan_step(transitions)
         if step.growth is not None:
             self._apply_growth(step.growth)
+        # a slot named twice within one step (a buffer smaller than a step's elements) keeps its last key's row
+        slots = list(dict.fromkeys(int(k % self._max_capacity) for k in reversed(step.keys)))[::-1]
+        return frames, step, slots
+
+    def _finish_many(self, step, **kwargs: Any) -> None:
+        """The sampler's ``add`` / ``remove`` of the step's keys, then the counter: what ``add_many`` does after its device call."""
+        self._plan.apply_sampler(self._sampling_distribution, step.keys, **kwargs)
+        self._add_count = self._plan.add_count
+
+    def _add_many_host(self, transitions: Sequence[Optional[TransitionElement]], **kwargs: Any):
+        """``add_many`` without its device call (the seam ``ReplayBuffer._add_host`` is for ``add``): returns ``(frames, writes,
+        slots)`` -- the new frames in environment order, the (frame index, ring slot) pairs and the de-duplicated element slots,
+        whose rows are ``self._plan.rows[slots]`` -- for a caller that sends them itself (``_issue_step``, or
+        ``slimdqn.sample_collection.group_replay.GroupVectorCollector``); None when no environment stepped."""
+        planned = self._plan_many(transitions)
+        if planned is None:
+            return None
+        frames, step, slots = planned
+        self._finish_many(step, **kwargs)
+        return frames, step.writes, slots
+
+    def _issue_step(self, frames, writes, slots) -> None:
+        """The device half of a vector step: one ``replay_add_step`` call (more only when the step makes more than 128 rows)."""
+        from slimdqn import _hip
+
         blk = self._claim_half()
         for i, f in enumerate(frames):
             blk["frames"][i] = f.view(np.uint8).reshape(-1)
-        # a slot named twice within one step (a buffer smaller than a step's elements) keeps its last key's row
-        slots = list(dict.fromkeys(int(k % self._max_capacity) for k in reversed(step.keys)))[::-1]
         R = _hip.REPLAY_STEP_MAX_ROWS
-        self._issue(len(frames), step.writes, slots[:R], True)
+        self._issue(len(frames), writes, slots[:R], True)
         for lo in range(R, len(slots), R):
             self._claim_half()
             self._issue(0, (), slots[lo : lo + R], False)
-        self._plan.apply_sampler(self._sampling_distribution, step.keys, **kwargs)
-        self._add_count = self._plan.add_count
+
+    def add_many(self, transitions: Sequence[Optional[TransitionElement]], **kwargs: Any) -> None:
+        """One transition per environment (``None``: that environment does not step): E frames and their elements go to
+        the device in one ``replay_add_step`` call (more only when a step makes more than 128 rows); ``kwargs`` go to the
+        sampler's ``add`` of every new key, as in ``ReplayBuffer.add``."""
+        planned = self._plan_many(transitions)
+        if planned is None:
+            return
+        frames, step, slots = planned
+        self._issue_step(frames, step.writes, slots)
+        self._finish_many(step, **kwargs)
 
     def add(self, transition: TransitionElement, **kwargs: Any) -> None:
         if self._n_envs != 1:

@@ -683,6 +683,36 @@ typedef struct replay_group_member_t {
 } replay_group_member_t;
 int replay_group_add_step(int32_t n_members, const replay_group_member_t* members, void* block_host_pinned,
                           void* block_staging_dev, int64_t block_bytes, void* stream);
+/* One vector step of a SEED GROUP whose members are vector buffers: S SEPARATE segmented frame rings (the layout of
+ * replay_add_step: E * L slots, mirror slots below a segment's first main slot), which may differ in frame_bytes, n_frames,
+ * capacity, E and stack, each take the n_in <= 32 new frames, n_writes <= 64 (source index, destination slot) pairs and
+ * n_rows <= 128 element rows of ONE replay_add_step call.  This call replaces those S calls: the caller fills ONE PINNED block, the
+ * call copies `members` to its head, copies block_bytes of it asynchronously into block_staging_dev (caller-owned, at least as
+ * large) and ONE launch, grid (work items, S), writes every frame to its one or two ring slots and every row to its table.
+ * Block layout, both sides:
+ *   replay_group_many_member_t [n_members]  from byte 0 (written by the call)
+ *   per member, behind the records:         int32 [n_writes][2] (source frame index, destination ring slot) at pairs_offset,
+ *                                           int32 [n_rows] destination element slots + int32 [n_rows][8] the rows at rows_offset
+ *                                           (both multiples of 4; replay_gather_stacked documents the row);
+ *                                           uint8 [n_in][frame_bytes] its new frames at frames_offset (a multiple of 16)
+ * Frames move 16 B per lane when the member's frame_bytes % 16 == 0 and source and destination are 16-byte aligned, else 4 B,
+ * else bytes.  IDQN_E_INVALID before anything is enqueued (and before the block is written): a null pointer, n_members outside
+ * [1, 32], a block that is not 16-byte aligned, a count outside its limit, a member with neither a write nor a row, a table or
+ * the frames misaligned or outside [80 * n_members, block_bytes), a source index outside [0, n_in), a ring slot outside
+ * [0, n_frames), an element slot outside [0, capacity), a ring slot or an element slot named twice within a member, two members
+ * naming the same ring or the same row table.  The pinned block and the staging block may be refilled once the stream has passed
+ * this call.                                                                                                                    */
+typedef struct replay_group_many_member_t {
+    void* ring_dev;        /* [n_frames][frame_bytes] */
+    int32_t* rows_dev;     /* [capacity][8] */
+    int64_t n_frames, frame_bytes, capacity;
+    int32_t n_in, n_writes, n_rows, reserved;
+    int64_t pairs_offset;  /* byte offsets in the block: the pair table, */
+    int64_t rows_offset;   /* the slot + row table, */
+    int64_t frames_offset; /* the new frames */
+} replay_group_many_member_t;
+int replay_group_add_many(int32_t n_members, const replay_group_many_member_t* members, void* block_host_pinned,
+                          void* block_staging_dev, int64_t block_bytes, void* stream);
 /* Growth of the frame ring (no reference counterpart: the reference's host dict grows by itself,
  * replay_buffer.py:206-213): the live frames, transition indices [first_t, first_t + count), are copied from slot
  * t % old_n of the old ring to slot t % new_n of the new one (count <= old_n <= new_n, distinct buffers).             */
