@@ -1,6 +1,6 @@
 // The two phases of a prioritized sampler end (PerSampler, per_step_args.h), each stated once for the kernels that run them:
-//   write-back  |TD| -> priorities -> running maximum -> the tree      k_per_write_back, k_per_group_write_back, k_per_turn
-//   draw        uniforms -> leaves == replay slots, clamped -> weights  k_per_draw, k_per_group_draw, k_per_turn
+//   write-back  |TD| -> priorities -> running maximum -> the tree      k_per_write_back, k_per_group_write_back, k_per_turn, k_per_group_turn
+//   draw        uniforms -> leaves == replay slots, clamped -> weights  k_per_draw, k_per_group_draw, k_per_turn, k_per_group_turn
 // Both are built from the device functions of sumtree_device.h that the separate launches (k_per_priorities + k_sumtree_set,
 // k_per_sample + k_per_weights) are built from, in the same order per element, so a kernel that calls them leaves those
 // launches' bytes.  A kernel binds its record, does the synchronisation that is its own -- an election between workgroups, the
@@ -8,6 +8,16 @@
 #pragma once
 #include "per_step_args.h"
 #include "sumtree_device.h"
+
+// THE ORDER BETWEEN TWO PHASES OF ONE WORKGROUP (k_per_turn, k_per_group_turn): every wave's stores have completed before any
+// wave's loads are issued, and the compiler neither keeps a value in a register across nor moves a load up: workgroup-scope
+// release fence (the wave waits for its outstanding stores), the workgroup barrier, workgroup-scope acquire fence; plain vector
+// loads after it
+__device__ __forceinline__ void per_turn_fence() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __syncthreads();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
 
 // WRITE-BACK, one workgroup of ST_THREADS threads.  Thread i < n computes priority i (k_per_priorities' arithmetic) into LDS --
 // and into s.priorities when the caller wants them; the running maximum is the workgroup's maximum (an LDS integer maximum of

@@ -6,15 +6,7 @@
 #pragma once
 #include "per_phases.h"
 
-// every wave's stores have completed before any wave's loads are issued, and the compiler neither keeps a value in a register
-// across nor moves a load up: workgroup-scope release fence (the wave waits for its outstanding stores), the workgroup barrier,
-// workgroup-scope acquire fence; plain vector loads after it
-__device__ __forceinline__ void per_turn_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __syncthreads();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
+// (per_turn_fence, the order between two phases of one workgroup: per_phases.h)
 // One workgroup of ST_THREADS threads (16 waves).  The kernel keeps its flat scalar arguments and builds the record of step i in
 // registers: with the record passed by value, as k_per_draw and k_per_write_back take it, the same instruction sequence measured
 // 0.3 us (n = 32) to 0.6 us (n = 256) slower (profiles/per_phases_refactor.json).  The draw of step i + 1 is on the same tree with

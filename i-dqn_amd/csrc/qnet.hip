@@ -35,6 +35,7 @@
 #include "dp_internal.h"
 #include "per_step_args.h"
 #include "per_group_kernels.h"
+#include "per_group_steps_args.h"
 #include "convp_fwd_phases.h"
 #include "convp_items.h"
 
@@ -3730,6 +3731,14 @@ struct idqn_group_s {
     hipEvent_t ev[IDQN_STEPS_STAGING_DEPTH] = {};
     bool busy[IDQN_STEPS_STAGING_DEPTH] = {};
     int next = 0;
+    // idqn_group_per_learn_steps_on_replay_fc's blocks are larger (n_steps records per member, n_steps rows of uniforms): a ring
+    // of their own, same depth and event guard, made whole by that entry's first call; the ring above keeps its size and use
+    size_t ps_block_bytes = 0;
+    uint8_t* ps_pin[IDQN_STEPS_STAGING_DEPTH] = {};
+    uint8_t* ps_dev[IDQN_STEPS_STAGING_DEPTH] = {};
+    hipEvent_t ps_ev[IDQN_STEPS_STAGING_DEPTH] = {};
+    bool ps_busy[IDQN_STEPS_STAGING_DEPTH] = {};
+    int ps_next = 0;
     ActManySlot many;
     std::vector<void*> owned;
 };
@@ -3763,6 +3772,7 @@ extern "C" int idqn_group_create(const idqn_handle_t* members, int32_t n_members
     // the prioritized call (idqn_group_per_learn_on_replay_fc) puts its tree records and uniforms where the slots go
     G->uni_off = G->slots_off + (((size_t)n_members * sizeof(PerSampler) + 15) & ~(size_t)15);
     G->block_bytes = std::max(G->slots_off + (size_t)n_members * STEPS_SLOTS_BYTES, G->uni_off + (size_t)n_members * PER_GROUP_MAX_N * 8);
+    G->ps_block_bytes = per_group_steps_block(sizeof(FcGroupMember), n_members, IDQN_MAX_STEPS_PER_CALL, PER_GROUP_MAX_N).bytes;
     *out = G;
     return IDQN_OK;
 }
@@ -3778,6 +3788,9 @@ extern "C" int idqn_group_destroy(idqn_group_t G) {
         if (G->pin[i]) (void)hipHostFree(G->pin[i]);
         if (G->dev[i]) (void)hipFree(G->dev[i]);
         if (G->ev[i]) (void)hipEventDestroy(G->ev[i]);
+        if (G->ps_pin[i]) (void)hipHostFree(G->ps_pin[i]);
+        if (G->ps_dev[i]) (void)hipFree(G->ps_dev[i]);
+        if (G->ps_ev[i]) (void)hipEventDestroy(G->ps_ev[i]);
     }
     delete G;
     return IDQN_OK;
@@ -3915,6 +3928,90 @@ extern "C" int idqn_group_per_learn_on_replay_fc(idqn_group_t G, const idqn_grou
     IDQN_HIP_CHECK(hipGetLastError());
     IDQN_HIP_CHECK(hipEventRecord(G->ev[blk], q));
     G->busy[blk] = true;
+    return IDQN_OK;
+}
+
+// n_steps prioritized steps of every member as ONE call (include/idqn_hip.h): block = {FcGroupMember[n_steps][S], PerSampler
+// [n_steps][S], uniforms [S][n_steps][batch]} (per_group_steps_args.h) in the entry's own staging ring -> one copy ->
+// k_per_group_draw (S) on row 0 -> for every step k_fc_group_step (K, S) on that step's records -> k_per_group_turn (S) behind
+// every step but the last -> k_per_group_write_back (S): 2 n_steps + 1 launches.  The persistent k_fc_group_steps cannot serve:
+// every step's draw depends on the previous step's |TD|.  At n_steps == 1 this is idqn_group_per_learn_on_replay_fc's sequence.
+// Every refusal comes before anything is enqueued, allocated or staged.
+extern "C" int idqn_group_per_learn_steps_on_replay_fc(idqn_group_t G, const idqn_group_ring_t* rings, const idqn_per_steps_t* per, int32_t n_steps,
+                                                       int32_t batch, int32_t mean_divisor, uint32_t flags, void* stream) {
+    const char* fn = "idqn_group_per_learn_steps_on_replay_fc";
+    IDQN_REQUIRE(G && rings && per, "%s: null pointer", fn);
+    IDQN_REQUIRE(n_steps >= 1 && n_steps <= IDQN_MAX_STEPS_PER_CALL, "%s: n_steps %d not in [1, %d]", fn, n_steps, IDQN_MAX_STEPS_PER_CALL);
+    IDQN_REQUIRE(batch >= 1 && batch <= PER_GROUP_MAX_N, "%s: batch %d not in [1, %d]: a group runs the one-launch step", fn, batch, PER_GROUP_MAX_N);
+    IDQN_REQUIRE(flags == 0, "%s: takes no flags (got 0x%x): profile or split a member's steps alone", fn, flags);
+    const int S = (int)G->m.size(), K = G->m[0]->cfg.n_heads;
+    for (int g = 0; g < S; ++g)
+        IDQN_REQUIRE(!G->m[g]->is_weight && !G->m[g]->td_abs,
+                     "%s: member %d has prioritized-replay buffers set (idqn_set_per_buffers): the call carries the members' weights and |TD| itself", fn, g);
+    int bad_g = -1, bad_j = -1;
+    const char* bad = per_group_steps_args_error(per, S, n_steps, batch, K, &bad_g, &bad_j);
+    IDQN_REQUIRE(!bad || bad_j < 0, "%s: members %d and %d: %s", fn, bad_j, bad_g, bad ? bad : "");
+    IDQN_REQUIRE(!bad, "%s: member %d: %s (depth %d, batch %d, n_items %ld)", fn, bad_g, bad, bad_g >= 0 ? per[bad_g].depth : 0, batch,
+                 bad_g >= 0 ? (long)per[bad_g].n_items : 0L);
+    for (int g = 0; g < S; ++g) {
+        const idqn_group_ring_t& r = rings[g];
+        long obs_elems;
+        if (const int rc = replay_fc_check(G->m[g], fn, (const uint8_t*)r.frames_dev, r.n_frames, r.frame_bytes, r.rows_dev, nullptr, per[g].leaves_dev, batch,
+                                           r.stack, mean_divisor, flags, &obs_elems))
+            return rc;
+    }
+    hipStream_t q = (hipStream_t)stream;
+    if (!G->ps_ev[IDQN_STEPS_STAGING_DEPTH - 1])  // the first call makes the whole ring: nothing is allocated later
+        for (int i = 0; i < IDQN_STEPS_STAGING_DEPTH; ++i) {
+            if (!G->ps_pin[i]) IDQN_HIP_CHECK(hipHostMalloc((void**)&G->ps_pin[i], G->ps_block_bytes, hipHostMallocDefault));
+            if (!G->ps_dev[i]) IDQN_HIP_CHECK(hipMalloc((void**)&G->ps_dev[i], G->ps_block_bytes));
+            if (!G->ps_ev[i]) IDQN_HIP_CHECK(hipEventCreateWithFlags(&G->ps_ev[i], hipEventDisableTiming));
+        }
+    const int blk = G->ps_next;
+    if (G->ps_busy[blk]) IDQN_HIP_CHECK(hipEventSynchronize(G->ps_ev[blk]));  // the launches that read this block are done
+    G->ps_busy[blk] = false;
+    const PerGroupStepsBlock lay = per_group_steps_block(sizeof(FcGroupMember), S, n_steps, batch);
+    uint8_t *pin = G->ps_pin[blk], *dev = G->ps_dev[blk];
+    FcGroupMember* tab = (FcGroupMember*)pin;
+    PerSampler* ptab = (PerSampler*)(pin + lay.samplers_off);
+    double* uni_pin = (double*)(pin + lay.uniforms_off);
+    const double* uni_dev = (const double*)(dev + lay.uniforms_off);
+    for (int g = 0; g < S; ++g) {
+        const idqn_per_steps_t& p = per[g];
+        const size_t rows = (size_t)g * n_steps * batch;  // member g's rows of uniforms
+        memcpy(uni_pin + rows, p.uniforms_host, (size_t)n_steps * batch * 8);
+        group_fill_member(tab[g], G->m[g], rings[g], false, batch, mean_divisor, false, p.leaves_dev);
+        for (int i = 0; i < n_steps; ++i) {  // step i's records: that step's rows of leaves (== slots), weights, |TD|, priorities
+            const long o = (long)i * batch;
+            FcGroupMember& m = tab[(size_t)i * S + g];
+            if (i) m = tab[g];
+            m.src.sl.slot = p.leaves_dev + o;
+            m.a.is_weight = p.weights_dev + o;
+            m.a.td_abs = p.td_abs_dev + o * K;
+            PerSampler& s = ptab[(size_t)i * S + g];
+            s = per_sampler_of(p, uni_dev + rows + o, K);
+            s.leaves += o; s.weights += o; s.td_abs += o * K;
+            if (s.priorities) s.priorities += o;
+        }
+    }
+    IDQN_HIP_CHECK(hipMemcpyAsync(dev, pin, lay.bytes, hipMemcpyHostToDevice, q));
+    G->ps_next = (blk + 1) % IDQN_STEPS_STAGING_DEPTH;
+    const idqn_handle_t h0 = G->m[0];
+    const FcGroupMember* tab_dev = (const FcGroupMember*)dev;
+    const PerSampler* ptab_dev = (const PerSampler*)(dev + lay.samplers_off);
+    const int m2 = st_pow2_at_least(batch);
+    hipLaunchKernelGGL(k_per_group_draw, dim3((unsigned)S), dim3(PER_GROUP_DRAW_T), 0, q, ptab_dev, (int)batch);
+    for (int i = 0; i < n_steps; ++i) {
+        hipLaunchKernelGGL(k_fc_group_step, dim3((unsigned)K, (unsigned)S), dim3(FCM_T), (size_t)h0->fcp_plan_.floats * 4, q, tab_dev + (size_t)i * S, 1);
+        if (i + 1 < n_steps)
+            hipLaunchKernelGGL(k_per_group_turn, dim3((unsigned)S), dim3(ST_THREADS), 0, q, ptab_dev + (size_t)i * S, ptab_dev + (size_t)(i + 1) * S,
+                               (int)batch, m2);
+        else
+            hipLaunchKernelGGL(k_per_group_write_back, dim3((unsigned)S), dim3(ST_THREADS), 0, q, ptab_dev + (size_t)i * S, (int)batch, m2);
+    }
+    IDQN_HIP_CHECK(hipGetLastError());
+    IDQN_HIP_CHECK(hipEventRecord(G->ps_ev[blk], q));
+    G->ps_busy[blk] = true;
     return IDQN_OK;
 }
 

@@ -175,8 +175,8 @@ class _VectorSeed:
     def per_epoch(self, field):
         return [[x for s in epoch for x in getattr(s, field)] for epoch in self.history]
 
-    def fused(self):
-        return hasattr(self.agent, "update_params_many") and self.p.get("fuse_gradient_steps", True)
+    def fused(self, learner=None):
+        return (learner is not None or hasattr(self.agent, "update_params_many")) and self.p.get("fuse_gradient_steps", True)
 
 
 class SeedVectorTrainer:
@@ -186,15 +186,21 @@ class SeedVectorTrainer:
     order), the S ``add_many`` are ONE ``GroupVectorCollector.add_many``, and where every seed learns over the same run of
     steps the E gradient steps of all of them are ONE ``AgentGroup.update_params_many`` (the persistent group kernel).  A seed
     whose last epoch has ended stops stepping; from then on, and wherever the seeds' runs differ, every seed is driven through
-    its own agent.  No ``learner=``: the prioritized group call makes one step per call and has no n-step form."""
+    its own agent.
 
-    def __init__(self, keys, p, agents, envs, replay_buffers, save_fn=None, group=None, collector=None):
+    ``learner``: a ``slimdqn.sample_collection.per.PrioritizedGroupLearner`` over the same agents (the same ``group``) and
+    buffers.  The gradient steps of a run that every seed owes are then ``learner.update_params_many`` (the n-step prioritized
+    group call, ``idqn_group_per_learn_steps_on_replay_fc``, where its sizes allow); where the runs differ, every seed's own
+    ``learner.learners[i].update_params_many``; the non-fused path steps ``learner.learners[i].step()``.  The target operations
+    stay the agents' own.  None: every line behaves as without the argument."""
+
+    def __init__(self, keys, p, agents, envs, replay_buffers, save_fn=None, group=None, collector=None, learner=None):
         ps = list(p) if isinstance(p, (list, tuple)) else [p] * len(agents)
         assert len(keys) == len(ps) == len(agents) == len(envs) == len(replay_buffers)
         self.seeds = [_VectorSeed(*t) for t in zip(keys, ps, agents, envs, replay_buffers)]
         self.group = group if group is not None else AgentGroup(agents)
         self.collector = collector if collector is not None else GroupVectorCollector(replay_buffers)
-        self.save_fn = save_fn
+        self.save_fn, self.learner = save_fn, learner
 
     def _select_actions(self, live):
         """``select_actions`` of every live seed on its own keys (one split per environment that steps); the greedy states of
@@ -254,8 +260,12 @@ class SeedVectorTrainer:
                     env.reset()
         return out
 
-    def _gradient_step(self, s):
-        s.agent.update_online_params(s.total_steps, s.rb)
+    def _gradient_step(self, i):
+        s = self.seeds[i]
+        if self.learner is None:
+            s.agent.update_online_params(s.total_steps, s.rb)
+        elif s.total_steps % s.agent.update_to_data == 0:
+            self.learner.learners[i].step()
         updated, logs = s.agent.update_target_params(s.total_steps)
         if updated:
             s.p["wandb"].log({"n_training_steps": s.total_steps, **logs})
@@ -267,7 +277,12 @@ class SeedVectorTrainer:
             return
         if len(runs) == len(self.seeds) and len(set(runs.values())) == 1:
             first, n = next(iter(runs.values()))
-            results = self.group.update_params_many(first, n, [s.rb for s in self.seeds])
+            if self.learner is not None:
+                results = self.learner.update_params_many(first, n)
+            else:
+                results = self.group.update_params_many(first, n, [s.rb for s in self.seeds])
+        elif self.learner is not None:
+            results = [self.learner.learners[i].update_params_many(*runs[i]) for i in sorted(runs)]
         else:
             results = [self.seeds[i].agent.update_params_many(*runs[i], self.seeds[i].rb) for i in sorted(runs)]
         for i, result in zip(sorted(runs), results):
@@ -312,7 +327,7 @@ class SeedVectorTrainer:
                             s.stats[e].open_episode()
                         else:  # the budget is spent: this environment waits for the others' episode ends
                             s.active[e] = False
-                if s.fused():
+                if s.fused(self.learner):
                     first = max(s.total_steps, s.p["n_initial_samples"]) + 1
                     s.total_steps += n_stepped
                     if s.total_steps >= first:
@@ -321,7 +336,7 @@ class SeedVectorTrainer:
                     for _ in range(n_stepped):
                         s.total_steps += 1
                         if s.total_steps > s.p["n_initial_samples"]:
-                            self._gradient_step(s)
+                            self._gradient_step(i)
             self._gradient_runs(runs)
             for i in live:
                 if not any(self.seeds[i].active):
@@ -330,7 +345,9 @@ class SeedVectorTrainer:
         return [(s.per_epoch("returns"), s.per_epoch("lengths")) for s in self.seeds]
 
 
-def train_seeds_vector(keys, p, agents, envs, replay_buffers, save_fn=None):
+def train_seeds_vector(keys, p, agents, envs, replay_buffers, save_fn=None, learner=None):
     """``experiments.base.dqn.train_vector`` for S seeds in one process: ``envs[i]`` is seed i's list of E environments and
-    ``replay_buffers[i]`` its ``VectorReplayBuffer(n_envs=E)``; returns ``(returns, lengths)`` per epoch, per seed."""
-    return SeedVectorTrainer(keys, p, agents, envs, replay_buffers, save_fn).run()
+    ``replay_buffers[i]`` its ``VectorReplayBuffer(n_envs=E)``; returns ``(returns, lengths)`` per epoch, per seed.  ``learner``:
+    a ``PrioritizedGroupLearner`` over the same agents and buffers; the trainer then runs on the learner's ``AgentGroup``."""
+    group = learner.group if learner is not None else None
+    return SeedVectorTrainer(keys, p, agents, envs, replay_buffers, save_fn, group=group, learner=learner).run()

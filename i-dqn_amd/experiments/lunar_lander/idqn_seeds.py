@@ -3,14 +3,18 @@
 seed): one acting call and one learner call per step for all of them (experiments/base/seeds.py).  Every other flag is the
 single-seed entry point's, unchanged; `-s` is set per seed.  ``envs`` defaults to the synthetic stand-in environment.
 `--n_envs E` (default 1: the path above, unchanged) gives every seed E environments and a `VectorReplayBuffer`: S x E time lines
-per lock-step iteration (`SeedVectorTrainer`); ``envs`` is then a list of E environments per seed."""
+per lock-step iteration (`SeedVectorTrainer`); ``envs`` is then a list of E environments per seed.
+`--prioritized` gives every seed a `SlotPrioritizedSampler` buffer and the seeds one `PrioritizedGroupLearner` (prioritized
+replay, slimdqn/sample_collection/per.py): the gradient steps are then the learner's, on either trainer."""
 import argparse
 import sys
 
 from experiments.base.launch import ENVIRONMENTS, default_environment, make_agent, observation_dim
-from experiments.base.seeds import train_seeds, train_seeds_vector
+from experiments.base.seeds import SeedTrainer, train_seeds_vector
 from experiments.base.utils import prepare_logs, save_data
 from slimdqn import prng
+from slimdqn.networks.group import AgentGroup
+from slimdqn.sample_collection.per import PrioritizedGroupLearner, SlotPrioritizedSampler
 from slimdqn.sample_collection.replay_buffer import ReplayBuffer
 from slimdqn.sample_collection.samplers import UniformSamplingDistribution
 from slimdqn.sample_collection.vector_replay_buffer import MAX_ENVS, VectorReplayBuffer
@@ -21,6 +25,7 @@ def run(argvs=sys.argv[1:], envs=None, save_root=None):
     ap.add_argument("--first_seed", type=int, required=True)
     ap.add_argument("--last_seed", type=int, required=True)
     ap.add_argument("--n_envs", type=int, default=1)
+    ap.add_argument("--prioritized", action="store_true")
     own, rest = ap.parse_known_args(argvs)
     seeds = list(range(own.first_seed, own.last_seed + 1))
     if not 1 <= len(seeds) <= 32:
@@ -41,15 +46,23 @@ def run(argvs=sys.argv[1:], envs=None, save_root=None):
         agent_key, train_key = prng.split(prng.PRNGKey(p["seed"]))
         shared = dict(batch_size=p["batch_size"], max_capacity=p["replay_buffer_capacity"], stack_size=consts["stack_size"],
                       update_horizon=p["update_horizon"], gamma=p["gamma"], clipping=consts["clipping"], compress=True)
-        if E == 1:
-            rb = ReplayBuffer(UniformSamplingDistribution(p["seed"]), **shared)
+        if own.prioritized:
+            sampler = SlotPrioritizedSampler(p["seed"], p["replay_buffer_capacity"])
         else:
-            rb = VectorReplayBuffer(UniformSamplingDistribution(p["seed"]), n_envs=E, **shared)
+            sampler = UniformSamplingDistribution(p["seed"])
+        if E == 1:
+            rb = ReplayBuffer(sampler, **shared)
+        else:
+            rb = VectorReplayBuffer(sampler, n_envs=E, **shared)
         rb.reuse_sample_buffers = True
         env0 = env if E == 1 else env[0]
         agents.append(make_agent("idqn", agent_key, observation_dim("lunar_lander", env0), env0.n_actions, p, consts["adam_eps"]))
         ps.append(p), keys.append(train_key), rbs.append(rb)
-    (train_seeds if E == 1 else train_seeds_vector)(keys, ps, agents, envs, rbs, save_fn=save_data)
+    learner = PrioritizedGroupLearner(AgentGroup(agents), rbs) if own.prioritized else None
+    if E == 1:
+        SeedTrainer(keys, ps, agents, envs, rbs, save_data, group=learner.group if learner else None, learner=learner).run()
+    else:
+        train_seeds_vector(keys, ps, agents, envs, rbs, save_fn=save_data, learner=learner)
     return ps, agents
 
 

@@ -25,7 +25,10 @@ Design (Schaul et al. 2016, proportional variant), all on the GPU, no host synch
   the draw of the next are one launch (``k_per_turn``), the uniforms of all steps one upload; byte-identical to n ``step()`` calls.
   ``PrioritizedLearner.update_params_many`` is the trainer-side loop over it (``VectorTrainer(..., learner=...)``).
 * ``PrioritizedGroupLearner``: the prioritized step of the S MLP agents of an ``AgentGroup`` as ONE C call,
-  ``idqn_group_per_learn_on_replay_fc`` (three launches for all members), byte-identical per member to the member's own step.
+  ``idqn_group_per_learn_on_replay_fc`` (three launches for all members), byte-identical per member to the member's own step;
+  n steps of all members as ONE C call, ``idqn_group_per_learn_steps_on_replay_fc`` (``PrioritizedGroupLearner.steps``: the S
+  write-backs of a step and the S draws of the next are one launch, ``k_per_group_turn``), byte-identical to n ``step()`` calls.
+  ``PrioritizedGroupLearner.update_params_many`` is the trainer-side loop over it (``SeedVectorTrainer(..., learner=...)``).
 """
 import ctypes as C
 import os
@@ -262,21 +265,27 @@ class PrioritizedLearner:
             return None
         return self._fused_route(self.fuse_per_steps_family)
 
-    def _steps_fused(self, view, U):
-        """The library's code for the n-step call on ring ``view`` with uniforms ``U`` (float64 [m][B], host, contiguous)."""
-        import torch
-
-        rb, agent = self.rb, self.agent
-        B, K, m = rb._batch_size, agent._K, U.shape[0]
-        frames, n_frames, frame_bytes, rows, stack = view[:5]
-        agent._ensure_handle(B)
+    def _ensure_steps_rows(self):
+        """The row buffers of the n-step calls (this learner's and ``PrioritizedGroupLearner``'s), one row per step:
+        ``(leaves, weights, |TD|, priorities)`` of ``[MAX_STEPS_PER_CALL][...]``, made on first use."""
         rows_out = self.__dict__.get("_steps_rows")
-        if rows_out is None:  # one row per step: leaves, weights, |TD|, priorities
-            M = _hip.MAX_STEPS_PER_CALL
+        if rows_out is None:
+            import torch
+
+            M, B, K = _hip.MAX_STEPS_PER_CALL, self.rb._batch_size, self.agent._K
             rows_out = self._steps_rows = (torch.empty((M, B), dtype=torch.int32, device="cuda"),
                                            torch.empty((M, B), dtype=torch.float32, device="cuda"),
                                            torch.zeros((M, K, B), dtype=torch.float32, device="cuda"),
                                            torch.empty((M, B), dtype=torch.float64, device="cuda"))
+        return rows_out
+
+    def _steps_fused(self, view, U):
+        """The library's code for the n-step call on ring ``view`` with uniforms ``U`` (float64 [m][B], host, contiguous)."""
+        rb, agent = self.rb, self.agent
+        B, m = rb._batch_size, U.shape[0]
+        frames, n_frames, frame_bytes, rows, stack = view[:5]
+        agent._ensure_handle(B)
+        rows_out = self._ensure_steps_rows()
         p = self.__dict__.get("_per_steps_args")
         if p is None:
             p = self._per_steps_args = _hip.PerSteps()
@@ -414,12 +423,13 @@ class PrioritizedGroupLearner:
         self.learners = [PrioritizedLearner(a, rb, beta=b, eps=e, reduce=r, stratified=s) for a, rb, b, e, r, s in
                          zip(group.agents, rbs, per_member(beta), per_member(eps), per_member(reduce), per_member(stratified))]
 
-    def _group_route(self):
-        """The members' ring views when this step goes through the group call, else None; read on every call."""
+    def _group_route(self, sizes=None):
+        """The members' ring views when this step goes through the group call, else None; read on every call.  ``sizes``: the
+        size set that applies (``group_per_sizes``; ``steps`` passes ``group_per_steps_sizes``)."""
         group = self.group
         if os.environ.get("IDQN_PER_FUSED", "1") == "0" or self.__dict__.get("_group_per_ok") is False:
             return None
-        if len(group.agents) not in self.group_per_sizes or not group._stock():
+        if len(group.agents) not in (self.group_per_sizes if sizes is None else sizes) or not group._stock():
             return None
         if len({rb._batch_size for rb in self.rbs}) != 1 or self.rbs[0]._batch_size > 32:
             return None
@@ -448,7 +458,12 @@ class PrioritizedGroupLearner:
         synchronised)."""
         for rb in self.rbs:
             assert rb.add_count, "No samples in replay buffer!"
-        us = [np.ascontiguousarray(lr.sampler._rng_key.random(lr.rb._batch_size)) for lr in self.learners]  # member order
+        return self.step_with_uniforms([lr.sampler._rng_key.random(lr.rb._batch_size) for lr in self.learners])  # member order
+
+    def step_with_uniforms(self, us):
+        """``step()`` on uniforms ``us`` ([S] float64 arrays of [B] in [0, 1)) that the caller has drawn from the members' sampler
+        generators already -- what ``steps_with_uniforms`` runs per row where the n-step group call does not serve."""
+        us = [np.ascontiguousarray(u, np.float64) for u in us]
         views = self._group_route()
         if views is not None:
             rc = self._step_group(views, us)
@@ -463,3 +478,99 @@ class PrioritizedGroupLearner:
                     a._replay_fc_ok = True
                 return [a._losses for a in self.group.agents]
         return [lr.step_with_uniforms(u) for lr, u in zip(self.learners, us)]
+
+    # n steps of every member as ONE C call per ``MAX_STEPS_PER_CALL`` rows (``idqn_group_per_learn_steps_on_replay_fc``: one
+    # upload, k_per_group_draw, then the group step / k_per_group_turn alternating, k_per_group_write_back), byte-identical per
+    # member to n ``step_with_uniforms`` calls on the same rows.  Taken under ``_group_route``'s conditions with the size set
+    # ``group_per_steps_sizes`` for runs of at least ``group_per_steps_min`` steps; ``IDQN_PER_STEPS=0`` switches it off.
+    # ``_group_per_steps_ok`` (unset: not tried; False: the entry refused these members the first time -- text in
+    # ``group_per_steps_refusal`` -- the rows go through ``step_with_uniforms`` one by one from then on; True: it served).
+    # Defaults by the standing rule "a size (S, n) is on only where the call's median lies below the minimum of the chain of n
+    # ``idqn_group_per_learn_on_replay_fc`` calls on the same commit" (tools/bench_group_per_steps.py ->
+    # profiles/group_per_steps.json; LunarLander net, B = 32, us per gradient step of all S members, call against chain).  n = 1
+    # is SLOWER at every S >= 2 (S = 2 51.3 against 50.0, 8 111.7 against 66.8, 32 378.2 against 211.1: the same launches behind
+    # more host work per call): ``group_per_steps_min`` = 2.  From n = 2 on the call wins at every measured S: S = 2 45.8 / 43.2 /
+    # 42.5 / 43.9 at n = 2 / 5 / 8 / 32 against 49.8; S = 4 46.5 ... 43.9 against 49.8; S = 8 62.5 ... 46.5 against 66.2; S = 16
+    # 106.3 ... 50.3 against 112.9; S = 32 199.3 / 96.6 / 71.0 / 54.1 against 206.5 ... 209.0.  Sizes that were not measured stay
+    # off; S = 1 is no group (``AgentGroup._stock``).
+    group_per_steps_sizes = frozenset({2, 4, 8, 16, 32})
+    group_per_steps_min = 2
+
+    def _group_steps_route(self, n):
+        """The members' ring views when a run of ``n`` steps goes through the n-step group call, else None."""
+        if n < self.group_per_steps_min or os.environ.get("IDQN_PER_STEPS", "1") == "0" or self.__dict__.get("_group_per_steps_ok") is False:
+            return None
+        return self._group_route(self.group_per_steps_sizes)
+
+    def _steps_group(self, views, Us):
+        """The library's code for the n-step group call on ring ``views`` with uniforms ``Us`` ([S] float64 arrays of [m][B],
+        host, contiguous), or None when ``idqn_group_create`` refused the members."""
+        B, m = self.rbs[0]._batch_size, Us[0].shape[0]
+        g = self.group._ensure_group(B)
+        if g is None:
+            return None
+        per = self.__dict__.get("_per_steps_args")
+        if per is None:
+            per = self._per_steps_args = (_hip.PerSteps * len(self.learners))()
+        rows = [lr._ensure_steps_rows() for lr in self.learners]
+        for p, lr, U, r in zip(per, self.learners, Us, rows):
+            lr._fill_sampler_args(p, U, *r)
+        rc = _hip.lib().idqn_group_per_learn_steps_on_replay_fc(g, self.group._rings(views), per, m, B, B, 0, _hip.current_stream())
+        if rc == 0:  # the member learners' own buffers are the last step's rows, as m ``step()`` calls leave them
+            for lr, r in zip(self.learners, rows):
+                lr._leaves, lr._weights, lr._td_abs, lr._priorities = (t[m - 1] for t in r)
+        return rc
+
+    def steps_with_uniforms(self, Us):
+        """``step_with_uniforms`` on every row of ``Us`` ([S] float64 arrays of [n][B] in [0, 1)), in order; returns the members'
+        per-head losses of the last step.  Every row goes through exactly one route."""
+        Us = [np.ascontiguousarray(U, np.float64) for U in Us]
+        n, i = Us[0].shape[0], 0
+        views = self._group_steps_route(n)
+        while views is not None and i < n:
+            m = min(_hip.MAX_STEPS_PER_CALL, n - i)
+            rc = self._steps_group(views, [U[i : i + m] for U in Us])
+            if rc is None or (rc == _hip.E_INVALID and self.__dict__.get("_group_per_steps_ok") is None):
+                self._group_per_steps_ok = False  # not these members: single steps from now on -- the same rows, nothing more drawn
+                self.group_per_steps_refusal = "idqn_group_create refused the members" if rc is None else \
+                    _hip.lib().idqn_last_error().decode(errors="replace")
+                break
+            _hip.check(rc, "idqn_group_per_learn_steps_on_replay_fc")
+            self._group_per_steps_ok = True
+            for a in self.group.agents:
+                a._replay_fc_ok = True
+            i += m
+        for j in range(i, n):
+            self.step_with_uniforms([U[j] for U in Us])
+        return [a._losses for a in self.group.agents]
+
+    def steps(self, n):
+        """``n`` prioritized gradient steps of every member: every member's sampler generator is drawn n times first, member by
+        member -- the state n ``step()`` calls leave, since a member's generator is its own -- then the steps run, as one call
+        where ``steps_with_uniforms`` allows it."""
+        n = int(n)
+        if n <= 0:
+            return [a._losses for a in self.group.agents]
+        for rb in self.rbs:
+            assert rb.add_count, "No samples in replay buffer!"
+        return self.steps_with_uniforms([np.stack([lr.sampler._rng_key.random(lr.rb._batch_size) for _ in range(n)]) for lr in self.learners])
+
+    def update_params_many(self, first_step, n_steps):
+        """Per member ``[(step, logs)]`` of the target updates of the loop ``if s % update_to_data == 0: step();
+        update_target_params(s)`` over ``n_steps`` steps from ``first_step``, as ``AgentGroup.update_params_many`` runs it: one
+        ``plan_step_runs`` on the shared schedule, every run's gradient steps through ``steps``, the target operations the
+        members' own.  Members whose schedules differ, or a group that is not stock: every member learner's own
+        ``update_params_many``."""
+        agents = self.group.agents
+        schedule = lambda a: (a.update_to_data, a.target_update_frequency, getattr(a, "target_sync_frequency", None))  # noqa: E731
+        if not self.group._stock() or any(schedule(a) != schedule(agents[0]) for a in agents):
+            return [lr.update_params_many(first_step, n_steps) for lr in self.learners]
+        out = [[] for _ in agents]
+        for n_grad, op, last in plan_step_runs(first_step, n_steps, *schedule(agents[0])):
+            self.steps(n_grad)
+            if op is not None:
+                for o, a in zip(out, agents):
+                    updated, logs = a.update_target_params(last)
+                    if updated:
+                        o.append((last, logs))
+        return out

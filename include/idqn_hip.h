@@ -414,6 +414,35 @@ struct idqn_per_step;
 int idqn_group_per_learn_on_replay_fc(idqn_group_t group, const idqn_group_ring_t* rings /*[S]*/,
                                       const struct idqn_per_step* per /*[S]*/, int32_t batch, int32_t mean_divisor,
                                       uint32_t flags, void* stream);
+/* idqn_per_learn_steps_on_replay for every member at once: n_steps consecutive prioritized steps of S MLP agents as ONE call.
+ * per[g] is member g's idqn_per_steps_t (declared with idqn_per_learn_steps_on_replay below): leaves_dev / weights_dev
+ * [n_steps][batch], td_abs_dev [n_steps][K][batch], priorities_dev [n_steps][batch] (may be NULL), uniforms_host float64
+ * [n_steps][batch] in ordinary host memory, read before the call returns.  n_steps in [1, IDQN_MAX_STEPS_PER_CALL], batch in
+ * [1, 32], no flags.  Enqueued: ONE pinned block and ONE asynchronous copy -- the member records (step i's record of member g
+ * carries that step's slots = row i of the leaves, its weights row and its |TD| row, as idqn_group_per_learn_on_replay_fc sets
+ * them), the tree records and all S x n_steps x batch uniforms -- then k_per_group_draw on row 0, for every step the unchanged
+ * k_fc_group_step (grid (K, S)) on that step's records, k_per_group_turn (grid S: the write-back of step i and the draw of
+ * step i + 1 of member g in one workgroup, csrc/per_group_kernels.h) behind every step but the last, k_per_group_write_back
+ * behind the last: 2 n_steps + 1 launches and one upload for all members, where n_steps calls of
+ * idqn_group_per_learn_on_replay_fc make 3 n_steps launches and n_steps uploads and S calls of idqn_per_learn_steps_on_replay
+ * S (2 n_steps + 1) launches.  At n_steps = 1 the call enqueues exactly what idqn_group_per_learn_on_replay_fc enqueues.  The
+ * persistent k_fc_group_steps cannot serve here: every step's draw depends on the previous step's |TD|, so the sampler has to
+ * run between two steps.  The block is larger than the other group entries' and has a staging ring of its own
+ * (IDQN_STEPS_STAGING_DEPTH blocks sized for n_steps = 32, each reused only after the launches that read it have finished;
+ * all allocated by the first call of this entry, none later); the other entries' ring and bytes are untouched.
+ * CONTRACT: for every member, online parameters, both moments, count, losses, cum_losses, tree nodes, max_priority_dev and
+ * every step's row of leaves, weights, |TD| and priorities after the call equal, byte for byte, n_steps calls of
+ * idqn_group_per_learn_on_replay_fc on the rows of the uniforms on the same stream -- hence also
+ * idqn_per_learn_steps_on_replay on that member alone.
+ * Refuses (IDQN_E_INVALID with idqn_last_error naming the entry and the member, nothing enqueued, allocated, staged or
+ * changed): a NULL pointer other than priorities_dev / max_priority_dev; n_steps or batch out of range; any flag; depth outside
+ * [1, 31]; n_items < 1; a member with idqn_set_per_buffers set; everything idqn_learn_on_replay_fc_dev refuses for a member and
+ * its ring; two members naming the same nodes_dev, leaves_dev, weights_dev, td_abs_dev, tree_scratch_dev or non-NULL
+ * priorities_dev / max_priority_dev.                                                                                        */
+struct idqn_per_steps;
+int idqn_group_per_learn_steps_on_replay_fc(idqn_group_t group, const idqn_group_ring_t* rings /*[S]*/,
+                                            const struct idqn_per_steps* per /*[S]*/, int32_t n_steps, int32_t batch,
+                                            int32_t mean_divisor, uint32_t flags, void* stream);
 /* idqn_act_host_many_fc over the members: state e (float32 rows [n][obs] in PINNED host memory) is evaluated on head
  * heads_host[e] of member member_host[e] (both ordinary host memory, read before the call returns).  Row e of q_out_dev [n][A]
  * and actions_host_pinned[e] are, byte for byte, what idqn_act_host gives on that member for (which, heads_host[e], state e).
