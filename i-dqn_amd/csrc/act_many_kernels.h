@@ -17,6 +17,10 @@
 // Heads, groups and the parameter set are DATA: ActManyTable sits at the head of the pinned block whose tail holds the
 // states and is uploaded by the chain's one copy node, so a captured chain serves every head assignment and both sets.
 // The actions reach the host through act_many_deliver below, shared with iqn_act_many_kernels.h and fc_act_many_kernels.h.
+//
+// ACTING GROUPS (idqn_act_group_host): the same three bodies with the state's parameter base read from ActGroupTable in the
+// uploaded block -- states of different agents in one call.  Each body is stated ONCE, as a __device__ function template over
+// the parameter source (ActManyNets / ActGroupNets); k_act_many_* and k_act_group_* are its two instantiations.
 #pragma once
 #include "common.h"
 
@@ -43,6 +47,29 @@ __device__ __forceinline__ const float* act_many_params(const ActManyNets& m, in
     return (m.tab->which ? m.target : m.online) + (long)head * m.pstride;
 }
 
+// The head of an acting group's block (idqn_act_group_host): ActManyTable as in every many-state chain, then the parameter
+// base of each state's (member, parameter set, head), resolved by the host as FcGroupActTable's are; the n uint8 states follow.
+// A Dense_0 group is a run of states with one (member, head): every state of it names the same base.
+struct ActGroupTable {
+    ActManyTable tab;
+    const float* params[ACT_MANY_MAX];
+};
+static_assert(sizeof(ActGroupTable) == 1024 + 8 * ACT_MANY_MAX, "ActGroupTable is the head of the group's acting block");
+struct ActGroupNets {
+    const ActGroupTable* gt;
+};
+
+// WHERE A PARAMETER BASE COMES FROM is all the three kernel bodies below leave open: one handle's arena by the table's head
+// (ActManyNets), or the group's table of bases (ActGroupNets).  Memory nothing writes during the launch, at uniform addresses.
+__device__ __forceinline__ const ActManyTable* act_many_table(const ActManyNets& m) { return m.tab; }
+__device__ __forceinline__ const float* act_many_state_params(const ActManyNets& m, int e) { return act_many_params(m, m.tab->head[e]); }
+__device__ __forceinline__ const float* act_many_group_params(const ActManyNets& m, int g) { return act_many_params(m, m.tab->g_head[g]); }
+__device__ __forceinline__ const ActManyTable* act_many_table(const ActGroupNets& m) { return &m.gt->tab; }
+__device__ __forceinline__ const float* act_many_state_params(const ActGroupNets& m, int e) { return m.gt->params[e]; }
+__device__ __forceinline__ const float* act_many_group_params(const ActGroupNets& m, int g) {
+    return m.gt->params[m.gt->tab.order[m.gt->tab.g_start[g]]];
+}
+
 // The end of every many-state chain, called by ONE thread of each of the n final workgroups after it has stored its state's
 // action.  mail: {action[ACT_MANY_MAX], sequence number} in mapped, coherent host memory; ctr: the device counters behind it,
 // ctr[0] the sequence number, ctr[1] the workgroups that have finished.  The workgroup that finishes last (an atomic count of
@@ -61,8 +88,9 @@ __device__ __forceinline__ void act_many_deliver(int32_t* action, volatile int32
     }
 }
 
-struct ActManyConvArgs {
-    ActManyNets nets;
+template <class Nets>
+struct ActManyConvArgsT {
+    Nets nets;
     const uint8_t* in_u8;  // layer 0: [n][IH][IW][CI] uint8
     const float* in;       // later layers: [n][IH][IW][CI] f32
     float* out;            // [n][OH][OW][CO] f32, after bias + ReLU
@@ -70,10 +98,12 @@ struct ActManyConvArgs {
     int IH, IW, CI, OH, OW, CO, K, S, PLh, PLw;
     int KS;
 };
+typedef ActManyConvArgsT<ActManyNets> ActManyConvArgs;
+typedef ActManyConvArgsT<ActGroupNets> ActGroupConvArgs;
 
 // k_act_conv with the state in blockIdx.y: grid (ceil(n_out / (256 / KS)), n)
-template <int CIU, int UPT>
-__global__ __launch_bounds__(256) void k_act_many_conv(ActManyConvArgs a) {
+template <int CIU, int UPT, class Nets>
+__device__ __forceinline__ void act_many_conv(const ActManyConvArgsT<Nets>& a) {
     __shared__ float red[256];
     __shared__ float lut[256];
     const int t = threadIdx.x, per = 256 / a.KS, oi = t % per, ks = t / per, e = blockIdx.y;
@@ -83,7 +113,7 @@ __global__ __launch_bounds__(256) void k_act_many_conv(ActManyConvArgs a) {
     }
     const long o = (long)blockIdx.x * per + oi;
     const int n_out = a.OH * a.OW * a.CO, n_in = a.IH * a.IW * a.CI, ccs = a.CI / CIU, n_units = a.K * a.K * ccs;
-    const float* params = act_many_params(a.nets, a.nets.tab->head[e]);
+    const float* params = act_many_state_params(a.nets, e);
     const uint8_t* in_u8 = a.in_u8 ? a.in_u8 + (long)e * n_in : nullptr;
     const float* in = a.in ? a.in + (long)e * n_in : nullptr;
     float acc = 0.f;
@@ -129,23 +159,32 @@ __global__ __launch_bounds__(256) void k_act_many_conv(ActManyConvArgs a) {
         a.out[(long)e * n_out + o] = fmaxf(s + params[a.b_off + co], 0.f);
     }
 }
+template <int CIU, int UPT>
+__global__ __launch_bounds__(256) void k_act_many_conv(ActManyConvArgs a) { act_many_conv<CIU, UPT>(a); }
+template <int CIU, int UPT>
+__global__ __launch_bounds__(256) void k_act_group_conv(ActGroupConvArgs a) { act_many_conv<CIU, UPT>(a); }
 
-struct ActManyDenseArgs {
-    ActManyNets nets;
+template <class Nets>
+struct ActManyDenseArgsT {
+    Nets nets;
     const float* a3;  // [n][F]
     float* part;      // [n][NRG][J]
     long w_off;
     int F, J, NRG;
 };
-// k_act_dense0 per GROUP of states with one head: grid (NRG * J / 128, min(n, K)); blockIdx.y past the call's groups
-// exits at once.  The 16 W0 float4 of a round are loaded once and applied to every state of the chunk.
-__global__ __launch_bounds__(256) void k_act_many_dense0(ActManyDenseArgs a) {
+typedef ActManyDenseArgsT<ActManyNets> ActManyDenseArgs;
+typedef ActManyDenseArgsT<ActGroupNets> ActGroupDenseArgs;
+// k_act_dense0 per GROUP of states with one head (of one member): grid (NRG * J / 128, min(n, K)) -- an acting group:
+// min(n, S K, 32) --; blockIdx.y past the call's groups exits at once.  The 16 W0 float4 of a round are loaded once and
+// applied to every state of the chunk.
+template <class Nets>
+__device__ __forceinline__ void act_many_dense0(const ActManyDenseArgsT<Nets>& a) {
     __shared__ float4 red[ACT_MANY_SC][8][32];
-    const ActManyTable* tb = a.nets.tab;
+    const ActManyTable* tb = act_many_table(a.nets);
     const int g = blockIdx.y;
     if (g >= tb->n_groups) return;
     const int cnt = tb->g_count[g], first = tb->g_start[g];
-    const float* W0 = act_many_params(a.nets, tb->g_head[g]) + a.w_off;
+    const float* W0 = act_many_group_params(a.nets, g) + a.w_off;
     const int t = threadIdx.x, cq = t & 31, rs = t >> 5, nq = a.J / 128;
     const int rg = blockIdx.x / nq, jq = (blockIdx.x - rg * nq) * 128 + cq * 4;
     const int r0 = (int)((long)a.F * rg / a.NRG), r1 = (int)((long)a.F * (rg + 1) / a.NRG);
@@ -196,9 +235,12 @@ __global__ __launch_bounds__(256) void k_act_many_dense0(ActManyDenseArgs a) {
         __syncthreads();  // the next chunk overwrites red
     }
 }
+__global__ __launch_bounds__(256) void k_act_many_dense0(ActManyDenseArgs a) { act_many_dense0(a); }
+__global__ __launch_bounds__(256) void k_act_group_dense0(ActGroupDenseArgs a) { act_many_dense0(a); }
 
-struct ActManyHeadArgs {
-    ActManyNets nets;
+template <class Nets>
+struct ActManyHeadArgsT {
+    Nets nets;
     const float* part;  // [n][NP][J]
     long b0_off, w1_off, b1_off;
     int NP, J, A, n;
@@ -207,13 +249,16 @@ struct ActManyHeadArgs {
     volatile int32_t* mail;  // host mailbox or nullptr, and its device counters: act_many_deliver
     unsigned* ctr;
 };
+typedef ActManyHeadArgsT<ActManyNets> ActManyHeadArgs;
+typedef ActManyHeadArgsT<ActGroupNets> ActGroupHeadArgs;
 // k_act_head, one workgroup of 1024 per state; the actions leave through act_many_deliver.
-__global__ __launch_bounds__(1024) void k_act_many_head(ActManyHeadArgs a) {
+template <class Nets>
+__device__ __forceinline__ void act_many_head(const ActManyHeadArgsT<Nets>& a) {
     __shared__ float hp[4][512];
     __shared__ float hs[512];
     __shared__ float qs[32];
     const int t = threadIdx.x, g = t >> 8, jp = (t & 255) * 2, e = blockIdx.x;
-    const float* params = act_many_params(a.nets, a.nets.tab->head[e]);
+    const float* params = act_many_state_params(a.nets, e);
     const float* part = a.part + (long)e * a.NP * a.J;
     if (jp < a.J) {
         const int p0 = a.NP * g / 4, p1 = a.NP * (g + 1) / 4;
@@ -257,3 +302,5 @@ __global__ __launch_bounds__(1024) void k_act_many_head(ActManyHeadArgs a) {
         if (a.mail) act_many_deliver(a.action, a.mail, a.ctr, a.n);
     }
 }
+__global__ __launch_bounds__(1024) void k_act_many_head(ActManyHeadArgs a) { act_many_head(a); }
+__global__ __launch_bounds__(1024) void k_act_group_head(ActGroupHeadArgs a) { act_many_head(a); }

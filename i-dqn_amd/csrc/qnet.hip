@@ -22,6 +22,7 @@
 
 #include "act_kernels.h"
 #include "act_many_kernels.h"
+#include "act_group_args.h"
 #include "iqn_act_kernels.h"
 #include "iqn_act_many_kernels.h"
 #include "cnn_kernels.h"
@@ -3320,18 +3321,18 @@ extern "C" int idqn_act_host_end(idqn_handle_t h, int32_t* action_host_pinned, v
 // launches follow, and the n actions come back through the slot's mailbox.  One linear hipGraph per (n, buffers) serves every
 // head assignment, both parameter sets and every set of fractions.  Each entry checks its own arguments and domain, fills the
 // block and hands its launches to act_many_run; everything else is shared.
-static int act_many_conv_plan(idqn_handle_t h, int i, int* KS, int* upt) {
+static int act_many_conv_plan(idqn_handle_t h, int i, int* KS, int* upt, const char* fn = "idqn_act_host_many") {
     const ConvL& l = h->conv[i];
     *KS = i == 0 ? 8 : 16;  // as act_trunk
     const int units = l.K * l.K * (l.CI % 32 == 0 ? l.CI / 32 : l.CI / 4);
     *upt = cdiv(units, *KS);
-    IDQN_REQUIRE(l.CI % 32 == 0 ? *upt <= 4 : (l.CI == 4 && *upt <= 8), "idqn_act_host_many: Conv_%d is outside the acting kernels' shapes", i);
+    IDQN_REQUIRE(l.CI % 32 == 0 ? *upt <= 4 : (l.CI == 4 && *upt <= 8), "%s: Conv_%d is outside the acting kernels' shapes", fn, i);
     return IDQN_OK;
 }
-static int act_many_conv_plans(idqn_handle_t h) {  // the entries' check, before anything is enqueued
+static int act_many_conv_plans(idqn_handle_t h, const char* fn = "idqn_act_host_many") {  // the entries' check, before anything is enqueued
     for (int i = 0; i < 3; ++i) {
         int ks = 0, upt = 0;
-        int rc = act_many_conv_plan(h, i, &ks, &upt);
+        int rc = act_many_conv_plan(h, i, &ks, &upt, fn);
         if (rc) return rc;
     }
     return IDQN_OK;
@@ -3405,13 +3406,23 @@ static ActManyNets act_many_nets(idqn_handle_t h) {  // (an IqnActManyBlock begi
     return nets;
 }
 
-// the three k_act_many_conv launches of the cnn and i-IQN chains: uint8 states [n][..] -> out[0] -> out[1] -> out[2]
-static int act_many_convs(idqn_handle_t h, const ActManyNets& nets, const uint8_t* states_u8, float* const out[3], int n, hipStream_t q) {
+// the three conv launches of the cnn and i-IQN chains (k_act_many_conv) and of an acting group (k_act_group_conv: the same body,
+// the parameter bases from the group's table): uint8 states [n][..] -> out[0] -> out[1] -> out[2]
+template <int CIU, int UPT>
+static void act_many_conv_launch(const ActManyConvArgs& a, dim3 grid, hipStream_t q) {
+    hipLaunchKernelGGL((k_act_many_conv<CIU, UPT>), grid, dim3(256), 0, q, a);
+}
+template <int CIU, int UPT>
+static void act_many_conv_launch(const ActGroupConvArgs& a, dim3 grid, hipStream_t q) {
+    hipLaunchKernelGGL((k_act_group_conv<CIU, UPT>), grid, dim3(256), 0, q, a);
+}
+template <class Nets>
+static int act_many_convs(idqn_handle_t h, const Nets& nets, const uint8_t* states_u8, float* const out[3], int n, hipStream_t q) {
     const float* in = nullptr;
     int ih = h->cfg.obs_h, iw = h->cfg.obs_w;
     for (int i = 0; i < 3; ++i) {
         const ConvL& l = h->conv[i];
-        ActManyConvArgs a;
+        ActManyConvArgsT<Nets> a;
         a.nets = nets; a.in_u8 = i == 0 ? states_u8 : nullptr; a.in = in; a.out = out[i];
         a.w_off = l.w_off; a.b_off = l.b_off; a.IH = ih; a.IW = iw; a.CI = l.CI; a.OH = l.OH; a.OW = l.OW; a.CO = l.CO;
         a.K = l.K; a.S = l.S; a.PLh = l.PLh; a.PLw = l.PLw;
@@ -3419,10 +3430,10 @@ static int act_many_convs(idqn_handle_t h, const ActManyNets& nets, const uint8_
         int rc = act_many_conv_plan(h, i, &a.KS, &upt);
         if (rc) return rc;
         const dim3 grid(cdiv((long)l.OH * l.OW * l.CO, 256 / a.KS), n);
-        if (l.CI % 32 != 0) hipLaunchKernelGGL((k_act_many_conv<4, 8>), grid, dim3(256), 0, q, a);
-        else if (upt <= 1) hipLaunchKernelGGL((k_act_many_conv<32, 1>), grid, dim3(256), 0, q, a);
-        else if (upt <= 2) hipLaunchKernelGGL((k_act_many_conv<32, 2>), grid, dim3(256), 0, q, a);
-        else hipLaunchKernelGGL((k_act_many_conv<32, 4>), grid, dim3(256), 0, q, a);
+        if (l.CI % 32 != 0) act_many_conv_launch<4, 8>(a, grid, q);
+        else if (upt <= 1) act_many_conv_launch<32, 1>(a, grid, q);
+        else if (upt <= 2) act_many_conv_launch<32, 2>(a, grid, q);
+        else act_many_conv_launch<32, 4>(a, grid, q);
         in = out[i]; ih = l.OH; iw = l.OW;
     }
     return IDQN_OK;
@@ -4065,6 +4076,110 @@ extern "C" int idqn_group_act_host_fc(idqn_group_t G, int32_t which, const int32
         a.s = (const float*)(s.block + s.head_bytes); a.s_ld = h0->fc.d[0]; a.ws = s.part; a.q_out = q_out_dev;
         a.action = s.action; a.mail = mail_dev; a.ctr = s.ctr; a.n = n;
         hipLaunchKernelGGL(k_fc_group_act_many1, dim3(n), dim3(512), 0, qs, a, (const FcGroupActTable*)s.block);
+        return IDQN_OK;
+    });
+}
+
+// ---- acting groups: the greedy actions of S MFMA-cnn agents in one call (act_many_kernels.h, act_group_args.h) ----------------
+// The chain of idqn_act_host_many -- one copy node, three conv launches, Dense_0 per group of states, the head kernel per state
+// -- with every state's parameter base read from a table in the uploaded block (ActGroupTable: member, parameter set and head
+// resolved here) instead of one handle's arena.  The group owns ONE acting slot and nothing else; it allocates nothing on a
+// member, writes no member memory, and a member may be driven alone between two group calls.  The chain is captured on member
+// 0's capture stream and reads member 0's shapes, which every member shares.
+static_assert(ACT_GROUP_MAX == ACT_MANY_MAX, "act_group_args.h restates ACT_MANY_MAX");
+struct idqn_act_group_s {
+    std::vector<idqn_handle_t> m;
+    ActManySlot many;
+    std::vector<void*> owned;
+};
+
+extern "C" int idqn_act_group_create(const idqn_handle_t* members, int32_t n_members, idqn_act_group_t* out) {
+    const char* fn = "idqn_act_group_create";
+    IDQN_REQUIRE(members && out, "%s: null pointer", fn);
+    IDQN_REQUIRE(n_members >= 1 && n_members <= ACT_MANY_MAX, "%s: %d members, must be in [1, %d]", fn, n_members, ACT_MANY_MAX);
+    IDQN_REQUIRE(!act_generic(), "%s: IDQN_ACT_GENERIC routes acting through the batched forward: no acting groups", fn);
+    for (int g = 0; g < n_members; ++g) {
+        const idqn_handle_t h = members[g];
+        IDQN_REQUIRE(h, "%s: member %d is null", fn, g);
+        IDQN_REQUIRE(h->cfg.n_quantiles == 0 && h->iqn.N == 0, "%s: member %d was created with quantile heads", fn, g);
+        IDQN_REQUIRE(h->cfg.arch == IDQN_ARCH_CNN, "%s: member %d is an MLP (fc) handle: idqn_group_create serves those", fn, g);
+        // (idqn_create sends J > 512 and A > 32 down the general-shape path: named first, under their own texts)
+        const int J_cfg = h->cfg.features[h->cfg.n_features - 1];
+        IDQN_REQUIRE(J_cfg <= 512, "%s: member %d has J = %d > 512: the acting kernels take J = 128 m <= 512", fn, g, J_cfg);
+        IDQN_REQUIRE(h->cfg.n_actions <= 32, "%s: member %d has A = %d > 32 actions: the acting kernels take A <= 32", fn, g, h->cfg.n_actions);
+        IDQN_REQUIRE(!h->gc.on, "%s: member %d is a general-shape cnn handle: outside the single-state MFMA cnn acting path", fn, g);
+        if (const int rc = act_many_conv_plans(h, fn)) return rc;
+        const idqn_config_t &c = h->cfg, &c0 = members[0]->cfg;
+        bool same = c.obs_h == c0.obs_h && c.obs_w == c0.obs_w && c.obs_c == c0.obs_c && c.n_features == c0.n_features &&
+                    c.n_actions == c0.n_actions && c.n_heads == c0.n_heads;
+        for (int i = 0; same && i < c.n_features; ++i) same = c.features[i] == c0.features[i];
+        IDQN_REQUIRE(same, "%s: member %d differs from member 0 in shape (obs, features, n_actions, n_heads)", fn, g);
+        for (int j = 0; j < g; ++j) IDQN_REQUIRE(members[j] != h, "%s: members %d and %d are the same handle", fn, j, g);
+    }
+    IDQN_REQUIRE(((size_t)members[0]->cfg.obs_h * members[0]->cfg.obs_w * members[0]->cfg.obs_c) % 4 == 0, "%s: bytes per state must be a multiple of 4", fn);
+    idqn_act_group_s* G = new idqn_act_group_s();
+    G->m.assign(members, members + n_members);
+    *out = G;
+    return IDQN_OK;
+}
+
+extern "C" int idqn_act_group_destroy(idqn_act_group_t G) {
+    if (!G) return IDQN_OK;
+    (void)hipDeviceSynchronize();
+    for (void* p : G->owned) (void)hipFree(p);
+    for (auto& g : G->many.graphs) (void)hipGraphExecDestroy(g.second);
+    if (G->many.mail) (void)hipHostFree(G->many.mail);
+    if (G->many.pin) (void)hipHostFree(G->many.pin);
+    delete G;
+    return IDQN_OK;
+}
+
+extern "C" int idqn_act_group_host(idqn_act_group_t G, int32_t which, const int32_t* member_host, const int32_t* heads_host,
+                                   const void* states_host_pinned, int32_t n, float* q_out_dev, int32_t* actions_host_pinned, void* stream) {
+    const char* fn = "idqn_act_group_host";
+    IDQN_REQUIRE(G && member_host && heads_host && states_host_pinned && q_out_dev && actions_host_pinned, "%s: null pointer", fn);
+    const idqn_handle_t h0 = G->m[0];
+    const int K = h0->cfg.n_heads, S = (int)G->m.size();
+    int bad = -1;
+    if (const char* why = act_group_args_error(n, S, K, which, member_host, heads_host, &bad)) {
+        if (bad >= 0) IDQN_REQUIRE(false, "%s: %s: state %d, member %d, head %d (%d members, %d heads)", fn, why, bad, member_host[bad], heads_host[bad], S, K);
+        IDQN_REQUIRE(false, "%s: %s (n = %d, which = %d)", fn, why, n, which);
+    }
+    for (int g = 0; g < S; ++g)
+        IDQN_REQUIRE(G->m[g]->act_pending == 0, "%s: member %d has an idqn_act_host_begin still waiting for its _end", fn, g);
+    const size_t sb = (size_t)h0->cfg.obs_h * h0->cfg.obs_w * h0->cfg.obs_c;  // bytes of one state (a multiple of 4: _create)
+    const long NRG = std::max(1, 256 / (h0->J / 128));
+    ActManySlot& s = G->many;
+    if (!s.block) {
+        long fl[4] = {0, 0, 0, ACT_MANY_MAX * NRG * h0->J};
+        for (int i = 0; i < 3; ++i) fl[i] = (long)ACT_MANY_MAX * h0->conv[i].OH * h0->conv[i].OW * h0->conv[i].CO;
+        if (const int rc = act_many_alloc(s, G->owned, sizeof(ActGroupTable), sb, fl, 4)) return rc;
+    }
+    ActGroupTable* gt = (ActGroupTable*)s.pin;
+    ActManyTable* tb = &gt->tab;
+    int32_t g_member[ACT_MANY_MAX];
+    tb->n = n; tb->which = which; tb->pad = 0;
+    tb->n_groups = act_group_build(n, member_host, heads_host, tb->order, g_member, tb->g_head, tb->g_start, tb->g_count);
+    for (int e = 0; e < ACT_MANY_MAX; ++e) {  // (entries past n: state 0's, never read)
+        const int src = e < n ? e : 0;
+        const idqn_handle_t h = G->m[member_host[src]];
+        tb->head[e] = heads_host[src];
+        gt->params[e] = (which ? h->target : h->online) + (long)heads_host[src] * h->L.head_stride;
+    }
+    memcpy(s.pin + sizeof(ActGroupTable), states_host_pinned, (size_t)n * sb);
+    const int max_groups = (int)std::min<long>(std::min<long>(n, (long)S * K), ACT_MANY_MAX);
+    return act_many_run(h0, s, fn, n, sb, q_out_dev, actions_host_pinned, (hipStream_t)stream, [&](hipStream_t qs, int32_t* mail_dev) -> int {
+        ActGroupNets nets;
+        nets.gt = (const ActGroupTable*)s.block;
+        if (const int rc = act_many_convs(h0, nets, s.block + s.head_bytes, s.a, n, qs)) return rc;
+        ActGroupDenseArgs d;
+        d.nets = nets; d.a3 = s.a[2]; d.part = s.part; d.w_off = h0->off_w0; d.F = h0->F; d.J = h0->J; d.NRG = (int)NRG;
+        hipLaunchKernelGGL(k_act_group_dense0, dim3(d.NRG * (h0->J / 128), max_groups), dim3(256), 0, qs, d);
+        ActGroupHeadArgs ha;
+        ha.nets = nets; ha.part = s.part; ha.b0_off = h0->off_b0; ha.w1_off = h0->off_w1; ha.b1_off = h0->off_b1;
+        ha.NP = d.NRG; ha.J = h0->J; ha.A = h0->cfg.n_actions; ha.n = n; ha.q_out = q_out_dev; ha.action = s.action;
+        ha.mail = mail_dev; ha.ctr = s.ctr;
+        hipLaunchKernelGGL(k_act_group_head, dim3(n), dim3(1024), 0, qs, ha);
         return IDQN_OK;
     });
 }

@@ -205,7 +205,8 @@ class SeedVectorTrainer:
     def _select_actions(self, live):
         """``select_actions`` of every live seed on its own keys (one split per environment that steps); the greedy states of
         all seeds share the acting calls.  ``{seed: (stepping environments, their actions)}``."""
-        shared = self.group._stock()  # (else -- i-IQN, cnn or head-parallel members -- every seed's own acting call)
+        # (else -- i-IQN, general-shape cnn or head-parallel members -- every seed's own acting call)
+        shared = self.group._stock() or self.group._stock_act_cnn()
         out, greedy = {}, []
         for i in live:
             s = self.seeds[i]

@@ -160,6 +160,9 @@ SYMBOLS = {
     "idqn_group_per_learn_steps_on_replay_fc": (C.c_int, [_P, C.POINTER(GroupRing), C.POINTER(PerSteps), C.c_int32, C.c_int32, C.c_int32,
                                                           C.c_uint32, _P]),
     "idqn_group_act_host_fc": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P]),
+    "idqn_act_group_create": (C.c_int, [C.POINTER(_P), C.c_int32, C.POINTER(_P)]),
+    "idqn_act_group_destroy": (C.c_int, [_P]),
+    "idqn_act_group_host": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P]),
     "idqn_debug_buffer": (C.c_int, [_P, C.c_char_p, C.POINTER(_P), C.POINTER(C.c_int64)]),
     "idqn_debug_conv_items": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
     "idqn_profile_read": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_char_p]),

@@ -1,4 +1,5 @@
-"""Seed groups: S independent MLP agents (``iDQN`` / ``DQN``) whose learner steps and greedy actions are ONE device call each.
+"""Seed groups: S independent MLP agents (``iDQN`` / ``DQN``) whose learner steps and greedy actions are ONE device call each;
+S Atari-shaped (cnn) agents share the acting call only (``idqn_act_group_host``, ``act_group_sizes``).
 
 The reference runs its seeds as N processes on one device (``launch_job/*/train.sh``).  The one-launch MLP step uses one
 workgroup per head, so S agents are a grid of (K, S) workgroups (``csrc/fc_group_kernels.h``) and every member's parameters,
@@ -29,18 +30,26 @@ class AgentGroup:
     # The sizes S at which a group learner call is taken by default: those where its median lay below the minimum of the S
     # solo calls (tools/bench_seed_group.py -> profiles/seed_group.json).  Other sizes run the members one by one.
     group_sizes = frozenset(range(2, GROUP_MAX + 1))
+    # The sizes S at which Atari-shaped (cnn) members act through ONE ``idqn_act_group_host`` call by default: those where its
+    # median lay below the minimum of the loop of S ``idqn_act_host`` calls (tools/bench_act_group.py -> profiles/act_group.json).
+    # Measured: S = 1, 2, 4, 8, 16, 32; S = 1 was SLOWER (42.7 against 40.8 us).  Sizes that were not measured are off.
+    act_group_sizes = frozenset({2, 4, 8, 16, 32})
 
     def __init__(self, agents):
         self.agents = list(agents)
         if not 1 <= len(self.agents) <= GROUP_MAX:
             raise ValueError(f"a group holds 1..{GROUP_MAX} agents, got {len(self.agents)}")
         self._group, self._group_handles = None, None
+        self._act_group, self._act_group_handles = None, None
 
     # ---- plumbing ----------------------------------------------------------------------------------
     def _destroy_group(self):
         if getattr(self, "_group", None) is not None:
             _hip.lib().idqn_group_destroy(self._group)
             self._group = None
+        if getattr(self, "_act_group", None) is not None:
+            _hip.lib().idqn_act_group_destroy(self._act_group)
+            self._act_group = None
 
     def close(self):
         """Destroys the group object (before its members' handles go away)."""
@@ -76,6 +85,38 @@ class AgentGroup:
             return None
         _hip.check(rc, "idqn_group_create")
         self._group, self._group_handles, self._group_ok = g, handles, True
+        return g
+
+    def _stock_act_cnn(self):
+        """The members are Atari-shaped agents of one shape that act as ``DeviceAgent`` itself does, and an acting group of this
+        size is wanted (the learner routes have a rule of their own, ``_stock``)."""
+        a0 = self.agents[0]
+        return (len(self.agents) in self.act_group_sizes and getattr(self, "_group_act_cnn_ok", True)
+                and all(isinstance(a, DeviceAgent) and a._arch == "cnn" and not getattr(a, "_n_quantiles", 0)
+                        and type(a)._best_action is DeviceAgent._best_action and type(a)._best_actions is DeviceAgent._best_actions
+                        and a._obs == a0._obs and a._K == a0._K and a.network.n_actions == a0.network.n_actions
+                        and list(a.network.features) == list(a0.network.features) for a in self.agents))
+
+    def _ensure_act_group(self):
+        """The acting group over the members' current handles, or None once ``idqn_act_group_create`` has refused them."""
+        if self.__dict__.get("_group_act_cnn_ok") is False:
+            return None
+        for a in self.agents:
+            a._ensure_handle(32)
+        handles = tuple(a._handle.value for a in self.agents)
+        if self._act_group is not None and handles == self._act_group_handles:
+            return self._act_group
+        if self._act_group is not None:  # (a member re-created its handle for a larger batch)
+            _hip.lib().idqn_act_group_destroy(self._act_group)
+            self._act_group = None
+        arr = (C.c_void_p * len(handles))(*handles)
+        g = C.c_void_p()
+        rc = _hip.lib().idqn_act_group_create(arr, len(handles), C.byref(g))
+        if rc == _hip.E_INVALID and self.__dict__.get("_group_act_cnn_ok") is None:
+            self._group_act_cnn_ok = False  # not these handles (general shapes, J > 512, ...): the members' own calls from now on
+            return None
+        _hip.check(rc, "idqn_act_group_create")
+        self._act_group, self._act_group_handles = g, handles
         return g
 
     @staticmethod
@@ -225,6 +266,27 @@ class AgentGroup:
                 self._group_act_ok = True
                 return self._out_np[:n].astype(np.int64)
             self._group_act_ok = False
+        group = self._ensure_act_group() if self._stock_act_cnn() else None
+        if group is not None:
+            import torch
+
+            a0 = self.agents[0]
+            if not hasattr(self, "_pin_u8"):
+                self._pin_u8 = torch.empty((32, int(np.prod(a0._obs))), dtype=torch.uint8).pin_memory()
+                self._pin_u8_np = self._pin_u8.numpy()
+                self._out = torch.zeros(32, dtype=torch.int32).pin_memory()
+                self._out_np = self._out.numpy()
+                self.q_out = torch.zeros((32, a0.network.n_actions), dtype=torch.float32, device="cuda")
+            for i, s in enumerate(states):
+                self._pin_u8_np[i] = np.asarray(getattr(s, "tensor", s)).reshape(-1)  # casts as DeviceAgent._best_action does
+            rc = _hip.lib().idqn_act_group_host(group, int(which), members.ctypes.data, heads.ctypes.data,
+                                                C.c_void_p(self._pin_u8.data_ptr()), n, _hip.ptr(self.q_out),
+                                                C.c_void_p(self._out.data_ptr()), _hip.current_stream())
+            if rc != _hip.E_INVALID or self.__dict__.get("_group_act_cnn_ok") is not None:
+                _hip.check(rc, "idqn_act_group_host")
+                self._group_act_cnn_ok = True
+                return self._out_np[:n].astype(np.int64)
+            self._group_act_cnn_ok = False
         return np.array([int(self.agents[m]._best_action(int(which), int(h), s).item()) for m, h, s in zip(members, heads, states)],
                         np.int64)
 

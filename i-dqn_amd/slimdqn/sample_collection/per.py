@@ -105,10 +105,13 @@ class PrioritizedLearner:
         self._u_pin = torch.empty(B, dtype=torch.float64).pin_memory()
         self._u_ev = None
         self._u_dev = torch.empty(B, dtype=torch.float64, device="cuda")
-        self._leaves = torch.empty(B, dtype=torch.int32, device="cuda")
-        self._weights = torch.empty(B, dtype=torch.float32, device="cuda")
+        # (zeros, not empty: a step of fewer than B samples leaves the lanes past it unwritten, and what they hold must not
+        # depend on what the allocator handed out before -- tests/test_gpu_group_per.py::test_ragged_and_minimal_batches compares
+        # the whole rows of two learners after a batch of 16 in rows of 17)
+        self._leaves = torch.zeros(B, dtype=torch.int32, device="cuda")
+        self._weights = torch.zeros(B, dtype=torch.float32, device="cuda")
         self._td_abs = torch.zeros((K, B), dtype=torch.float32, device="cuda")
-        self._priorities = torch.empty(B, dtype=torch.float64, device="cuda")
+        self._priorities = torch.zeros(B, dtype=torch.float64, device="cuda")
 
     def _replay_sourced(self):
         """The buffer's ring view for an i-IQN agent whose replay-sourced step can read it (the agent's own conditions, its

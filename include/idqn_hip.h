@@ -453,6 +453,27 @@ int idqn_group_per_learn_steps_on_replay_fc(idqn_group_t group, const idqn_group
 int idqn_group_act_host_fc(idqn_group_t group, int32_t which, const int32_t* member_host, const int32_t* heads_host,
                            const void* states_host_pinned, int32_t n, float* q_out_dev, int32_t* actions_host_pinned, void* stream);
 
+/* Acting groups: the greedy actions of S Atari-shaped (MFMA cnn) agents in one call.  The members are 1..32 handles of the
+ * domain idqn_act_host_many accepts.  The group owns ONE acting slot (pinned block and its device copy, conv activations and
+ * Dense_0 partials for 32 states, mailbox and counters, graph map); it allocates nothing on a member, writes no member memory,
+ * and a member may be driven alone between two group calls.  Destroy the group before its members.
+ * idqn_act_group_create refuses (IDQN_E_INVALID, nothing changed): n_members outside [1, 32]; IDQN_ACT_GENERIC; a member that is
+ * null, an fc handle, a handle with quantile heads, one with J > 512 or A > 32, any other general-shape cnn handle; a member that differs from member 0 in observation, features, n_actions or n_heads; a handle named twice.       */
+typedef struct idqn_act_group_s* idqn_act_group_t;
+int idqn_act_group_create(const idqn_handle_t* members, int32_t n_members, idqn_act_group_t* out);
+int idqn_act_group_destroy(idqn_act_group_t group);
+/* idqn_act_host_many over the members: state e (uint8 [n][H][W][C] in PINNED host memory) is evaluated on head heads_host[e] of
+ * member member_host[e] (both ordinary host memory, read before the call returns) with the online (which = 0) or target (1)
+ * parameters.  Row e of q_out_dev [n][A] and actions_host_pinned[e] are, byte for byte, what idqn_act_host gives on that member
+ * for (which, heads_host[e], state e).  One copy node and five launches -- three conv layers, Dense_0 per run of states with
+ * one (member, head) (such states share the W0 stream in register chunks of 8; the same head on two members does not), the
+ * head kernel per state; the per-state parameter bases travel in the uploaded block, so one hipGraph per (n, buffers) serves
+ * every member and head assignment and both sets.  The actions come back through the slot's mailbox; IDQN_ACT_GRAPH=0 and
+ * IDQN_ACT_POLL=0 as for idqn_act_host_many.  IDQN_E_INVALID before anything is enqueued: a null pointer, n outside [1, 32],
+ * which not 0 / 1, a member outside [0, S), a head outside [0, K), a member with an idqn_act_host_begin still pending.      */
+int idqn_act_group_host(idqn_act_group_t group, int32_t which, const int32_t* member_host, const int32_t* heads_host,
+                        const void* states_host_pinned, int32_t n, float* q_out_dev, int32_t* actions_host_pinned, void* stream);
+
 /* Test / debug access to internal activation buffers by name (device pointer + byte size).        */
 int idqn_debug_buffer(idqn_handle_t h, const char* name, void** ptr_dev, int64_t* nbytes);
 
