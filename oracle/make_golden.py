@@ -1,6 +1,6 @@
 """Generates the committed golden vectors under tests/golden/ (run in the BUILD container only).
 
-    PYTHONDONTWRITEBYTECODE=1 python -m oracle.make_golden [--int] [--replay] [--fp]
+    PYTHONDONTWRITEBYTECODE=1 python -m oracle.make_golden [--int] [--int-edges] [--replay] [--fp]
 
 --replay  imports the reference's ``slimdqn/sample_collection/replay_buffer.py`` and ``samplers.py`` as-is.  The three
        modules replay_buffer.py imports at its top and that are not installed (``jax``, ``flax.struct``, ``snappy``) are
@@ -18,6 +18,11 @@
        records operation traces: inputs AND the reference's outputs (node arrays, roots, query
        results, sampled keys, index maps).  Only data is written; no reference source travels.
        -> tests/golden/int_path_sumtree.npz, int_path_samplers.npz
+--int-edges  imports the reference's ``sum_tree.py`` the same way and runs every ``sumtree_set`` row of the edge table
+       (tests/sumtree_edges.py: pre-fill, then the measured set) through it.  Per row: the sha256 of the node array, the root,
+       ``max_recorded_priority`` and the reference's ``query`` output for seeded in-range targets.  The inputs are regenerated
+       from the table, so only results are written; written without time stamps, so a second run gives the same bytes.
+       -> tests/golden/int_path_sumtree_edges.npz
 --iqn  the same for the i-IQN extension (``oracle/iqn_ref.py``; the reference has no quantile code at all).
        -> tests/golden/fp_path_iqn_*.json
 --fp   writes expected losses / gradient / post-Adam probes of the fp64 numpy restatement
@@ -101,6 +106,28 @@ def capture_sumtree():
     out["meta_json"] = np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8)
     np.savez_compressed(os.path.join(GOLDEN, "int_path_sumtree.npz"), **out)
     print("wrote int_path_sumtree.npz", len(out), "arrays")
+
+
+def capture_sumtree_edges():
+    from slimdqn.sample_collection import sum_tree  # the reference, imported as-is
+
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
+    import sumtree_edges as E
+
+    rows = E.SET_ROWS
+    out = {"rows": np.asarray([(r.capacity, r.n, E.LEAF_KINDS.index(r.kind), r.salt) for r in rows], np.int64),
+           "digests": np.zeros((len(rows), 32), np.uint8), "roots": np.zeros(len(rows), np.float64),
+           "maxp": np.zeros(len(rows), np.float64), "q_out": np.full((len(rows), E.N_QUERY), -1, np.int32)}
+    for i, row in enumerate(rows):
+        tree = E.run_set_row(sum_tree.SumTree, row)
+        out["digests"][i] = np.frombuffer(hashlib.sha256(tree._nodes.tobytes()).digest(), np.uint8)
+        out["roots"][i] = tree.root
+        out["maxp"][i] = tree.max_recorded_priority
+        targets = E.query_targets(row, float(tree.root))
+        if targets.size:
+            out["q_out"][i] = tree.query(targets)
+    write_npz_deterministic(os.path.join(GOLDEN, "int_path_sumtree_edges.npz"), out)
+    print("wrote int_path_sumtree_edges.npz", len(rows), "rows")
 
 
 def capture_samplers():
@@ -555,6 +582,7 @@ def capture_iqn(names=None):
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--int", action="store_true")
+    ap.add_argument("--int-edges", action="store_true")
     ap.add_argument("--fp", action="store_true")
     ap.add_argument("--iqn", action="store_true")
     ap.add_argument("--replay", action="store_true")
@@ -565,6 +593,9 @@ if __name__ == "__main__":
         sys.path.insert(0, REFERENCE)
         capture_sumtree()
         capture_samplers()
+    if args.int_edges:
+        sys.path.insert(0, REFERENCE)
+        capture_sumtree_edges()
     if args.replay:
         sys.path.insert(0, REFERENCE)
         capture_replay()
