@@ -818,6 +818,10 @@ int plan_iqn_bwd_order(idqn_handle_s* h, int nb, int forced_e) {
             fprintf(stderr, "[plan] iqn dense0 update (nb %d): fused %.2f vs two splits + adam %.2f units -> %s\n", nb, fused, split,
                     w.bwd_fuse[nb - 1] ? "fused" : "two splits");
     }
+    // IDQN_IQN_ADAM_FUSE=0 (read here, once per plan: INTEGRATION.md): the two-split launch + Adam pass wherever the plan says fused
+    // (tests/test_gpu_iqn_shapes.py holds that pair to the oracle at the shapes the planner would never give it)
+    if (const char* e = getenv("IDQN_IQN_ADAM_FUSE"))
+        if (atoi(e) == 0) w.bwd_fuse[nb - 1] = false;
     return IDQN_OK;
 }
 
