@@ -3,7 +3,7 @@
 // Replaces (reference file:line):
 //   iDQN.learn_on_batch          slimdqn/networks/idqn.py:96-109   (jit o vmap of value_and_grad + optax.adam)
 //   iDQN.update_target_params    slimdqn/networks/idqn.py:74-94    (copy + shift / sync, as device copies)
-//   DQNNet.apply                 slimdqn/networks/architectures/dqn.py:38-70
+//   DQNNet.apply                 slimdqn/networks/architectures/dqn.py:38-70   (cnn, fc; impala: :7-29,54-60, impala_kernels.h)
 // One launch sequence per step on the caller's stream; nothing here synchronises with the host.
 // Scratch buffers are addressed compactly with the ACTIVE number of 32-sample batch blocks of a call
 // (slot = (net * nb + bb) * block); zero borders sit at fixed offsets inside every block-sized slot
@@ -31,6 +31,7 @@
 #include "fc_steps_kernels.h"
 #include "iqn_kernels.h"
 #include "gcnn_kernels.h"
+#include "impala_kernels.h"
 #include "fc_act_many_kernels.h"
 #include "fc_group_kernels.h"
 #include "dp_internal.h"
@@ -212,8 +213,39 @@ int build_layout(const idqn_config_t& c, Layout& L) {
             add_leaf(L, nm, 1, bs, &off);
             fan = f;
         }
+    } else if (c.arch == IDQN_ARCH_IMPALA) {
+        // three Stacks of five 3x3 convs (flax numbers them Conv_0..4), Dense + ReLU for every features[3:], Dense(n_actions)
+        // (architectures/dqn.py:7-29,54-60)
+        IDQN_REQUIRE(c.n_quantiles == 0, "impala: the i-IQN heads are built for the cnn arch");
+        IDQN_REQUIRE(c.n_features >= 3, "impala: at least 3 features (the three Stacks), got %d", c.n_features);
+        IDQN_REQUIRE(c.obs_h >= 1 && c.obs_w >= 1 && c.obs_c >= 1, "impala: empty observation");
+        int h = c.obs_h, w = c.obs_w, ch = c.obs_c;
+        for (int s = 0; s < 3; ++s) {
+            IDQN_REQUIRE(c.features[s] >= 1, "impala: Stack width %d", c.features[s]);
+            for (int i = 0; i < 5; ++i) {
+                long ks[4] = {3, 3, i == 0 ? ch : c.features[s], c.features[s]};
+                snprintf(nm, sizeof nm, "Stack_%d/Conv_%d/kernel", s, i);
+                add_leaf(L, nm, 4, ks, &off);
+                long bs[1] = {c.features[s]};
+                snprintf(nm, sizeof nm, "Stack_%d/Conv_%d/bias", s, i);
+                add_leaf(L, nm, 1, bs, &off);
+            }
+            h = (h + 1) / 2; w = (w + 1) / 2; ch = c.features[s];
+        }
+        long fan = (long)h * w * ch;
+        for (int i = 3; i <= c.n_features; ++i) {
+            long f = i < c.n_features ? c.features[i] : c.n_actions;
+            IDQN_REQUIRE(f >= 1, "impala: dense width %ld", f);
+            long ws[2] = {fan, f};
+            snprintf(nm, sizeof nm, "Dense_%d/kernel", i - 3);
+            add_leaf(L, nm, 2, ws, &off);
+            long bs[1] = {f};
+            snprintf(nm, sizeof nm, "Dense_%d/bias", i - 3);
+            add_leaf(L, nm, 1, bs, &off);
+            fan = f;
+        }
     } else {
-        IDQN_REQUIRE(false, "unknown arch %d (impala is out of scope of the HIP path)", c.arch);
+        IDQN_REQUIRE(false, "unknown arch %d (0 = cnn, 1 = fc, 2 = impala)", c.arch);
     }
     L.head_stride = off;
     return IDQN_OK;
@@ -275,6 +307,29 @@ struct GcnnWs {
     float* inf_ws = nullptr;
 };
 
+// workspace of the impala path (impala_kernels.h).  Per Stack s and image: c0 = Conv_0's output [H][W][CO], x[0] = the pool's
+// output, y[blk] = relu(Conv_{1+2blk}(relu(x[blk]))), x[blk + 1] = Conv_{2+2blk}(y[blk]) + x[blk], all [PH][PW][CO];
+// x[2] is the Stack's output (Stack 2: after the final ReLU, i.e. the dense head's input).
+struct ImpActs { float *c0[3], *x[3][3], *y[3][2]; };
+struct ImpStackL { int H, W, CI, CO, PH, PW, lo_h, lo_w; long w_off[5], b_off[5]; };
+struct ImpalaWs {
+    bool on = false;
+    int Bmax = 0;
+    ImpStackL st[3];
+    ImpActs train, infer;  // the 2K training nets x Bmax samples; one net x 32 states (acting)
+    float *d[3] = {nullptr, nullptr, nullptr};    // [K][Bmax][PH][PW][CO]: gradient of the Stack's running x
+    float *t[3] = {nullptr, nullptr, nullptr};    // same shape: gradient of y (the inner conv's output)
+    float *dc0[3] = {nullptr, nullptr, nullptr};  // [K][Bmax][H][W][CO]: gradient of Conv_0's output
+    float* wpart = nullptr;  // weight-gradient partials of one conv [K][chunks][9 CI CO + CO] (sized for the largest)
+    float* inf_ws = nullptr;
+    // a head with a hidden layer: Dense_0 runs on the k_imp_d0_* kernels, k_fc_step on the layers behind it (`tail`)
+    bool d0_split = false;
+    FcNet tail;
+    float* hid = nullptr;   // [2K][Bmax][D]  relu(Dense_0)
+    float* dhid = nullptr;  // [K][Bmax][D]   dL/d(pre-activation of Dense_0)
+    float* inf_hid = nullptr;  // [32][D]     relu(Dense_0) of the acting net
+};
+
 }  // namespace
 
 // Buffers, mailbox and counters of the many-state acting entries: idqn_act_host_many (act_many_kernels.h), idqn_act_host_many_fc
@@ -315,6 +370,7 @@ struct idqn_handle_s {
     NetSet train, infer;
     IqnWs iqn;
     GcnnWs gc;
+    ImpalaWs imp;
     float* dpart = nullptr;  // partial Dense_0 data gradients of the fused weight-gradient kernel [n_jt][K * nb][F][32]
     float *da3 = nullptr, *da2 = nullptr, *da1 = nullptr, *qdbg = nullptr, *slab = nullptr;
     float *hbuf = nullptr, *qpart = nullptr, *bcinv = nullptr;
@@ -974,6 +1030,251 @@ int gcnn_learn(idqn_handle_s* h, const uint8_t* st, const uint8_t* st2, const in
         const long nw = (long)b.f.KS * b.f.KS * b.f.CI * b.f.CO + b.f.CO;
         hipLaunchKernelGGL(k_gconv_wgrad, dim3(ggrid(nw), K), dim3(256), 0, q, b);
         if (i > 0) hipLaunchKernelGGL(k_gconv_dgrad, dim3(ggrid((long)K * B * b.f.IH * b.f.IW * b.f.CI)), dim3(256), 0, q, b);
+    }
+    IDQN_HIP_CHECK(hipGetLastError());
+    return IDQN_OK;
+}
+
+// ---- impala path (impala_kernels.h) ----------------------------------------------------------------------------------
+int imp_wgrad_chunks(const ImpStackL& s, int conv, long B) {
+    const int H = conv == 0 ? s.H : s.PH, W = conv == 0 ? s.W : s.PW;
+    return (int)cdiv(B * cdiv(H, IMP_TH) * cdiv(W, IMP_TW), IMP_WG_TILES);
+}
+
+int imp_alloc_acts(idqn_handle_s* h, ImpActs& A, long n_img, const char* tag, bool named) {
+    const ImpalaWs& w = h->imp;
+    int rc;
+    char nm[24];
+    for (int s = 0; s < 3; ++s) {
+        const ImpStackL& l = w.st[s];
+        const long full = (long)l.H * l.W * l.CO, pooled = (long)l.PH * l.PW * l.CO;
+        snprintf(nm, sizeof nm, "%s_c0_%d", tag, s);
+        if ((rc = alloc_zero(&A.c0[s], n_img * full, h, nm))) return rc;
+        for (int i = 0; i < 3; ++i) {
+            // the names the tests read: imp_pool<s> = the pool's output, imp_stack<s> = the Stack's output
+            if (named && i == 0) snprintf(nm, sizeof nm, "imp_pool%d", s);
+            else if (named && i == 2) snprintf(nm, sizeof nm, "imp_stack%d", s);
+            else snprintf(nm, sizeof nm, "%s_x%d_%d", tag, i, s);
+            if ((rc = alloc_zero(&A.x[s][i], n_img * pooled, h, nm))) return rc;
+        }
+        for (int i = 0; i < 2; ++i) {
+            snprintf(nm, sizeof nm, "%s_y%d_%d", tag, i, s);
+            if ((rc = alloc_zero(&A.y[s][i], n_img * pooled, h, nm))) return rc;
+        }
+    }
+    return IDQN_OK;
+}
+
+int impala_setup(idqn_handle_s* h) {
+    const idqn_config_t& c = h->cfg;
+    ImpalaWs& w = h->imp;
+    w.on = true;
+    w.Bmax = c.max_batch;
+    const int K = c.n_heads;
+    const long B = w.Bmax;
+    int ih = c.obs_h, iw = c.obs_w, ci = c.obs_c, hi;
+    long part_max = 0;
+    for (int s = 0; s < 3; ++s) {
+        ImpStackL& l = w.st[s];
+        l.H = ih; l.W = iw; l.CI = ci; l.CO = c.features[s];
+        same_pad(ih, 3, 2, &l.PH, &l.lo_h, &hi);
+        same_pad(iw, 3, 2, &l.PW, &l.lo_w, &hi);
+        for (int i = 0; i < 5; ++i) {
+            l.w_off[i] = h->L.leaves[10 * s + 2 * i].offset;
+            l.b_off[i] = h->L.leaves[10 * s + 2 * i + 1].offset;
+            part_max = std::max(part_max, (long)imp_wgrad_chunks(l, i, B) * (9L * (i == 0 ? l.CI : l.CO) * l.CO + l.CO));
+        }
+        ih = l.PH; iw = l.PW; ci = l.CO;
+    }
+    h->F = ih * iw * ci;
+    FcNet& n = h->fc;  // the dense head over the flattened features
+    n.L = c.n_features - 3 + 1;
+    IDQN_REQUIRE(n.L <= FC_MAX_LAYERS, "impala: too many dense layers (%d)", n.L);
+    n.d[0] = h->F;
+    n.dmax = n.d[0];
+    for (int l = 0; l < n.L; ++l) {
+        n.d[l + 1] = 3 + l < c.n_features ? c.features[3 + l] : c.n_actions;
+        n.dmax = std::max(n.dmax, n.d[l + 1]);
+        n.w_off[l] = h->L.leaves[30 + 2 * l].offset;
+        n.b_off[l] = h->L.leaves[31 + 2 * l].offset;
+    }
+    int rc;
+    if ((rc = imp_alloc_acts(h, w.train, 2L * K * B, "imp", true))) return rc;
+    if ((rc = imp_alloc_acts(h, w.infer, 32, "imp_i", false))) return rc;
+    for (int s = 0; s < 3; ++s) {
+        const ImpStackL& l = w.st[s];
+        char nm[16];
+        snprintf(nm, sizeof nm, "imp_d%d", s);
+        if ((rc = alloc_zero(&w.d[s], (long)K * B * l.PH * l.PW * l.CO, h, nm))) return rc;
+        snprintf(nm, sizeof nm, "imp_t%d", s);
+        if ((rc = alloc_zero(&w.t[s], (long)K * B * l.PH * l.PW * l.CO, h, nm))) return rc;
+        snprintf(nm, sizeof nm, "imp_dc0_%d", s);
+        if ((rc = alloc_zero(&w.dc0[s], (long)K * B * l.H * l.W * l.CO, h, nm))) return rc;
+    }
+    if ((rc = alloc_zero(&w.wpart, (long)K * part_max, h, "imp_wpart"))) return rc;
+    if ((rc = alloc_zero(&h->fc_ws, K * ((long)(n.L + 3) * B * n.dmax + 2 * B), h, "fc_ws"))) return rc;
+    if ((rc = alloc_zero(&w.inf_ws, 2L * 32 * n.dmax, h, "imp_infws"))) return rc;
+    w.d0_split = n.L >= 2;
+    if (w.d0_split) {
+        FcNet& t = w.tail;
+        t.L = n.L - 1;
+        t.dmax = 0;
+        for (int l = 0; l <= t.L; ++l) {
+            t.d[l] = n.d[l + 1];
+            t.dmax = std::max(t.dmax, t.d[l]);
+        }
+        for (int l = 0; l < t.L; ++l) {
+            t.w_off[l] = n.w_off[l + 1];
+            t.b_off[l] = n.b_off[l + 1];
+        }
+        if ((rc = alloc_zero(&w.hid, 2L * K * B * n.d[1], h, "imp_hid"))) return rc;
+        if ((rc = alloc_zero(&w.dhid, (long)K * B * n.d[1], h, "imp_dhid"))) return rc;
+        if ((rc = alloc_zero(&w.inf_hid, 32L * n.d[1], h, "imp_ihid"))) return rc;
+    }
+    if ((rc = alloc_zero(&h->qdbg, 2L * K * B * c.n_actions, h, "q"))) return rc;
+    IDQN_HIP_CHECK(hipMalloc((void**)&h->train.wbase, sizeof(float*) * 2 * K));
+    h->owned.push_back((void*)h->train.wbase);
+    std::vector<const float*> wb(2 * K);
+    for (int k = 0; k < K; ++k) {
+        wb[k] = h->online + (long)k * h->L.head_stride;
+        wb[K + k] = h->target + (long)k * h->L.head_stride;
+    }
+    IDQN_HIP_CHECK(hipMemcpy(h->train.wbase, wb.data(), sizeof(float*) * 2 * K, hipMemcpyHostToDevice));
+    h->dominant = "k_fc_step";
+    return IDQN_OK;
+}
+
+// one conv launch of Stack s: `conv` 0..4 forward, or its data gradient (dgrad: in = the output gradient)
+enum ImpKind { IMP_FWD_U8, IMP_FWD_PLAIN, IMP_FWD_INNER, IMP_FWD_RES, IMP_FWD_RES_RELU, IMP_DG_PLAIN, IMP_DG_MASK, IMP_DG_MASK_SKIP };
+void imp_conv(idqn_handle_s* h, ImpKind kind, int s, int conv, const float* const* wbase, int n_nets, int n_split, int B,
+              const uint8_t* s0, const uint8_t* s1, const float* in, float* out, const float* aux, const float* mask, hipStream_t q,
+              const char* name) {
+    const ImpStackL& l = h->imp.st[s];
+    const bool dg = kind >= IMP_DG_PLAIN;
+    ImpConvArgs a;
+    a.in_u8[0] = s0; a.in_u8[1] = s1; a.in = in; a.out = out; a.aux = aux; a.mask = mask; a.wbase = wbase;
+    a.w_off = l.w_off[conv]; a.b_off = l.b_off[conv]; a.n_nets = n_nets; a.n_split = n_split; a.B = B;
+    a.H = conv == 0 ? l.H : l.PH; a.W = conv == 0 ? l.W : l.PW;
+    const int leaf_ci = conv == 0 ? l.CI : l.CO;
+    a.CI = dg ? l.CO : leaf_ci; a.CO = dg ? leaf_ci : l.CO;
+    const dim3 grid((unsigned)(cdiv(a.H, IMP_TH) * cdiv(a.W, IMP_TW)), (unsigned)cdiv(a.CO, IMP_COB), (unsigned)(n_nets * B));
+    const dim3 blk(256);
+    switch (kind) {
+    case IMP_FWD_U8: hipLaunchKernelGGL((k_imp_conv<IMP_SRC_U8, false, false, false, false, false, 4>), grid, blk, 0, q, a); break;
+    case IMP_FWD_PLAIN: hipLaunchKernelGGL((k_imp_conv<IMP_SRC_F32, false, false, false, false, false, IMP_CIC>), grid, blk, 0, q, a); break;
+    case IMP_FWD_INNER: hipLaunchKernelGGL((k_imp_conv<IMP_SRC_F32, true, true, false, false, false, IMP_CIC>), grid, blk, 0, q, a); break;
+    case IMP_FWD_RES: hipLaunchKernelGGL((k_imp_conv<IMP_SRC_F32, false, false, true, false, false, IMP_CIC>), grid, blk, 0, q, a); break;
+    case IMP_FWD_RES_RELU: hipLaunchKernelGGL((k_imp_conv<IMP_SRC_F32, false, true, true, false, false, IMP_CIC>), grid, blk, 0, q, a); break;
+    case IMP_DG_PLAIN: hipLaunchKernelGGL((k_imp_conv<IMP_SRC_F32, false, false, false, true, false, IMP_CIC>), grid, blk, 0, q, a); break;
+    case IMP_DG_MASK: hipLaunchKernelGGL((k_imp_conv<IMP_SRC_F32, false, false, false, true, true, IMP_CIC>), grid, blk, 0, q, a); break;
+    case IMP_DG_MASK_SKIP: hipLaunchKernelGGL((k_imp_conv<IMP_SRC_F32, false, false, true, true, true, IMP_CIC>), grid, blk, 0, q, a); break;
+    }
+    tl_mark(h, q, name);
+}
+
+ImpPoolArgs imp_pool_args(const ImpStackL& l, long n_img) {
+    ImpPoolArgs p;
+    p.c0 = nullptr; p.out = nullptr; p.dy = nullptr; p.dx = nullptr; p.N = n_img;
+    p.H = l.H; p.W = l.W; p.C = l.CO; p.PH = l.PH; p.PW = l.PW; p.lo_h = l.lo_h; p.lo_w = l.lo_w;
+    return p;
+}
+
+// the three Stacks of `n_nets` nets (the first n_split read s0, the rest s1) on B samples each, into A
+int impala_trunk(idqn_handle_s* h, const float* const* wbase, int n_nets, int n_split, int B, const uint8_t* s0, const uint8_t* s1,
+                 const ImpActs& A, hipStream_t q) {
+    for (int s = 0; s < 3; ++s) {
+        const ImpStackL& l = h->imp.st[s];
+        if (s == 0) imp_conv(h, IMP_FWD_U8, s, 0, wbase, n_nets, n_split, B, s0, s1, nullptr, A.c0[s], nullptr, nullptr, q, "k_imp_conv<u8>");
+        else imp_conv(h, IMP_FWD_PLAIN, s, 0, wbase, n_nets, n_split, B, nullptr, nullptr, A.x[s - 1][2], A.c0[s], nullptr, nullptr, q, "k_imp_conv<conv0>");
+        ImpPoolArgs p = imp_pool_args(l, (long)n_nets * B);
+        p.c0 = A.c0[s]; p.out = A.x[s][0];
+        hipLaunchKernelGGL(k_imp_pool_fwd, dim3(ggrid(p.N * l.PH * l.PW * l.CO)), dim3(256), 0, q, p);
+        tl_mark(h, q, "k_imp_pool_fwd");
+        for (int blk = 0; blk < 2; ++blk) {
+            imp_conv(h, IMP_FWD_INNER, s, 1 + 2 * blk, wbase, n_nets, n_split, B, nullptr, nullptr, A.x[s][blk], A.y[s][blk], nullptr, nullptr, q,
+                     "k_imp_conv<inner>");
+            imp_conv(h, s == 2 && blk == 1 ? IMP_FWD_RES_RELU : IMP_FWD_RES, s, 2 + 2 * blk, wbase, n_nets, n_split, B, nullptr, nullptr,
+                     A.y[s][blk], A.x[s][blk + 1], A.x[s][blk], nullptr, q, "k_imp_conv<res>");
+        }
+    }
+    IDQN_HIP_CHECK(hipGetLastError());
+    return IDQN_OK;
+}
+
+// weight + bias gradient of conv `conv` of Stack s for the K online nets: per-chunk partials, then their ordered sum
+void imp_wgrad(idqn_handle_s* h, int s, int conv, int B, const uint8_t* st, const float* in, bool relu_in, const float* dy, hipStream_t q) {
+    const ImpStackL& l = h->imp.st[s];
+    const int K = h->cfg.n_heads;
+    ImpWgradArgs a;
+    a.in_u8 = st; a.in = in; a.dy = dy; a.part = h->imp.wpart; a.B = B;
+    a.H = conv == 0 ? l.H : l.PH; a.W = conv == 0 ? l.W : l.PW; a.CI = conv == 0 ? l.CI : l.CO; a.CO = l.CO;
+    a.n_tiles = B * cdiv(a.H, IMP_TH) * cdiv(a.W, IMP_TW);
+    a.n_chunks = cdiv(a.n_tiles, IMP_WG_TILES);
+    const dim3 grid((unsigned)a.n_chunks, (unsigned)(cdiv(a.CI, IMP_CIC) * cdiv(a.CO, IMP_COB)), (unsigned)K);
+    if (st) hipLaunchKernelGGL((k_imp_wgrad<IMP_SRC_U8, false>), grid, dim3(256), 0, q, a);
+    else if (relu_in) hipLaunchKernelGGL((k_imp_wgrad<IMP_SRC_F32, true>), grid, dim3(256), 0, q, a);
+    else hipLaunchKernelGGL((k_imp_wgrad<IMP_SRC_F32, false>), grid, dim3(256), 0, q, a);
+    tl_mark(h, q, "k_imp_wgrad");
+    ImpWreduceArgs r;
+    r.part = h->imp.wpart; r.grad = h->grad; r.gm = GradMap{h->gP, h->g_w0_begin, h->g_w0_end, h->g_w0_base};
+    r.w_off = l.w_off[conv]; r.b_off = l.b_off[conv]; r.nw = 9L * a.CI * a.CO; r.CO = a.CO; r.n_chunks = a.n_chunks;
+    hipLaunchKernelGGL(k_imp_wreduce, dim3(ggrid(r.nw + r.CO), K), dim3(256), 0, q, r);
+    tl_mark(h, q, "k_imp_wreduce");
+}
+
+int impala_learn(idqn_handle_s* h, const uint8_t* st, const uint8_t* st2, const int32_t* action, const float* reward,
+                 const uint8_t* terminal, int B, int Bdiv, bool grads_only, bool profile, hipStream_t q) {
+    ImpalaWs& w = h->imp;
+    const ImpActs& A = w.train;
+    const int K = h->cfg.n_heads;
+    IDQN_REQUIRE(B <= w.Bmax, "batch %d exceeds the workspace (%d)", B, w.Bmax);
+    int rc = impala_trunk(h, h->train.wbase, 2 * K, K, B, st, st2, A, q);
+    if (rc) return rc;
+    FcArgs a = fc_args(h, B, Bdiv, grads_only);
+    a.s = A.x[2][2]; a.s2 = A.x[2][2] + (long)K * B * h->F; a.s_stride = (long)B * h->F; a.din = w.d[2];
+    ImpD0Args d0;
+    const int D = h->fc.d[1], sblocks = cdiv(B, IMP_D0_SB);
+    if (w.d0_split) {
+        d0.x = A.x[2][2]; d0.hid = w.hid; d0.dh = w.dhid; d0.din = w.d[2]; d0.wbase = h->train.wbase; d0.grad = h->grad;
+        d0.gm = GradMap{h->gP, h->g_w0_begin, h->g_w0_end, h->g_w0_base};
+        d0.w_off = h->fc.w_off[0]; d0.b_off = h->fc.b_off[0]; d0.B = B; d0.F = h->F; d0.D = D;
+        hipLaunchKernelGGL(k_imp_d0_fwd, dim3((unsigned)cdiv(D, IMP_D0_OC), (unsigned)sblocks, (unsigned)(2 * K)), dim3(256), 0, q, d0);
+        tl_mark(h, q, "k_imp_d0_fwd");
+        a.net = w.tail; a.s = w.hid; a.s2 = w.hid + (long)K * B * D; a.s_stride = (long)B * D; a.din = w.dhid;
+    }
+    a.action = action; a.reward = reward; a.terminal = terminal;
+    a.is_weight = h->is_weight; a.td_abs = h->td_abs;
+    if (profile && h->ev_used + 2 <= (int)h->ev.size()) IDQN_HIP_CHECK(hipEventRecord(h->ev[h->ev_used], q));
+    hipLaunchKernelGGL(k_fc_step, dim3(K), dim3(256), 0, q, a);
+    tl_mark(h, q, "k_fc_step");
+    if (profile && h->ev_used + 2 <= (int)h->ev.size()) {
+        IDQN_HIP_CHECK(hipEventRecord(h->ev[h->ev_used + 1], q));
+        h->ev_used += 2;
+    }
+    if (w.d0_split) {
+        hipLaunchKernelGGL(k_imp_d0_wgrad, dim3((unsigned)cdiv(h->F, IMP_D0_R), (unsigned)cdiv(D, IMP_D0_OC), (unsigned)K), dim3(256), 0, q, d0);
+        tl_mark(h, q, "k_imp_d0_wgrad");
+        hipLaunchKernelGGL(k_imp_d0_dgrad, dim3((unsigned)cdiv(h->F, IMP_D0_R), (unsigned)sblocks, (unsigned)K), dim3(256), 0, q, d0);
+        tl_mark(h, q, "k_imp_d0_dgrad");
+    }
+    // Stacks top down.  w.d[s] holds dL/dx of the Stack's running x (entering Stack 2: the head's input gradient, already
+    // masked by the final ReLU); each block adds its branch to it in place.
+    const float* const* wb = h->train.wbase;
+    for (int s = 2; s >= 0; --s) {
+        const ImpStackL& l = w.st[s];
+        for (int blk = 1; blk >= 0; --blk) {
+            imp_wgrad(h, s, 2 + 2 * blk, B, nullptr, A.y[s][blk], false, w.d[s], q);
+            imp_conv(h, IMP_DG_MASK, s, 2 + 2 * blk, wb, K, K, B, nullptr, nullptr, w.d[s], w.t[s], nullptr, A.y[s][blk], q, "k_imp_conv<dgrad mask>");
+            imp_wgrad(h, s, 1 + 2 * blk, B, nullptr, A.x[s][blk], true, w.t[s], q);
+            imp_conv(h, IMP_DG_MASK_SKIP, s, 1 + 2 * blk, wb, K, K, B, nullptr, nullptr, w.t[s], w.d[s], w.d[s], A.x[s][blk], q,
+                     "k_imp_conv<dgrad mask skip>");
+        }
+        ImpPoolArgs p = imp_pool_args(l, (long)K * B);
+        p.c0 = A.c0[s]; p.dy = w.d[s]; p.dx = w.dc0[s];
+        hipLaunchKernelGGL(k_imp_pool_bwd, dim3(ggrid(p.N * l.H * l.W * l.CO)), dim3(256), 0, q, p);
+        tl_mark(h, q, "k_imp_pool_bwd");
+        imp_wgrad(h, s, 0, B, s == 0 ? st : nullptr, s == 0 ? nullptr : A.x[s - 1][2], false, w.dc0[s], q);
+        if (s > 0) imp_conv(h, IMP_DG_PLAIN, s, 0, wb, K, K, B, nullptr, nullptr, w.dc0[s], w.d[s - 1], nullptr, nullptr, q, "k_imp_conv<dgrad>");
     }
     IDQN_HIP_CHECK(hipGetLastError());
     return IDQN_OK;
@@ -2050,6 +2351,13 @@ int step_epilogue(idqn_handle_s* h, bool bump, hipStream_t q) {
 // =================================================================================================
 // C ABI
 // =================================================================================================
+// impala handles (impala_kernels.h) are served by idqn_learn_on_batch, idqn_learn_on_replay_fc(_dev), idqn_q_values /
+// idqn_best_action, idqn_act_host(_begin / _end), the target operations, idqn_apply_adam, idqn_set_per_buffers and the debug /
+// profile reads.  Every other entry refuses them here, before anything is enqueued; the Python callers take their fallbacks.
+#define IDQN_REFUSE_IMPALA(h, fn)                                                                                      \
+    IDQN_REQUIRE(!((h) && (h)->cfg.arch == IDQN_ARCH_IMPALA),                                                           \
+                 "%s: the impala architecture is not served by this entry (single calls of idqn_learn_on_batch / idqn_act_host are)", fn)
+
 extern "C" int idqn_layout(const idqn_config_t* cfg, int32_t* n_leaves, idqn_leaf_t* leaves, int64_t* head_stride) {
     IDQN_REQUIRE(cfg && n_leaves && leaves && head_stride, "idqn_layout: null pointer");
     Layout L;
@@ -2098,7 +2406,7 @@ extern "C" int idqn_create(const idqn_config_t* cfg, float* online_dev, float* t
     rc = alloc_zero(&h->bcinv, 2L * cfg->n_heads + 64, h, "bcinv");
     const bool general = cfg->arch == IDQN_ARCH_CNN && !cnn_fast_shape(*cfg);
     if (general) h->planes = false;
-    if (!rc) rc = general ? gcnn_setup(h) : (cfg->arch == IDQN_ARCH_CNN ? cnn_setup(h) : fc_setup(h));
+    if (!rc) rc = general ? gcnn_setup(h) : (cfg->arch == IDQN_ARCH_CNN ? cnn_setup(h) : cfg->arch == IDQN_ARCH_IMPALA ? impala_setup(h) : fc_setup(h));
     if (rc) { idqn_destroy(h); return rc; }
     h->ev.resize(2 * 2048);
     for (auto& e : h->ev)
@@ -2171,6 +2479,13 @@ extern "C" int idqn_learn_on_batch(idqn_handle_t h, const void* state_dev, const
     h->pend_B = 0; h->pend_stage = 0;
     if (const int rc = tl_begin(h, flags, q)) return rc;
     int rc;
+    if (h->imp.on) {
+        if ((rc = impala_learn(h, (const uint8_t*)state_dev, (const uint8_t*)next_state_dev, action_dev, reward_dev, terminal_dev, batch,
+                               batch_mean_divisor, grads_only, profile, q)))
+            return rc;
+        if (!grads_only && (rc = launch_adam(h, 0, h->L.head_stride, 0, 0, false, q))) return rc;
+        return IDQN_OK;
+    }
     if (h->gc.on) {
         IDQN_REQUIRE(!(stop0 || stopb), "the IDQN_F_STOP_* flags belong to the MFMA cnn path");
         if ((rc = gcnn_learn(h, (const uint8_t*)state_dev, (const uint8_t*)next_state_dev, action_dev, reward_dev, terminal_dev, batch,
@@ -2334,6 +2649,7 @@ static int replay_check(idqn_handle_t h, const char* fn, const uint8_t* frame_ri
                         const int32_t* rows_dev, const int32_t* slots_host, const int32_t* slots_dev, int32_t batch, int32_t stack,
                         const float* tau_dev, uint32_t flags) {
     IDQN_REQUIRE(h && frame_ring_dev && rows_dev && (slots_host || slots_dev), "%s: null pointer", fn);
+    IDQN_REFUSE_IMPALA(h, fn);
     if (tau_dev) {  // the quantile step (idqn_iqn_learn_on_replay*): the limits of idqn_iqn_learn_on_batch, under the caller's name
         IDQN_REQUIRE(h->iqn.N > 0, "%s: the handle was created without quantile heads (cfg.n_quantiles)", fn);
         IDQN_REQUIRE(!(flags & ~(IDQN_F_PROFILE | IDQN_F_PROFILE_ALL)), "%s: only the profile flags are supported", fn);
@@ -2406,9 +2722,9 @@ static int replay_fc_check(idqn_handle_t h, const char* fn, const uint8_t* frame
                            const int32_t* rows_dev, const int32_t* slots_host, const int32_t* slots_dev, int32_t batch, int32_t stack,
                            int32_t batch_mean_divisor, uint32_t flags, long* obs_elems_out) {
     IDQN_REQUIRE(h && frame_ring_dev && rows_dev && (slots_host || slots_dev), "%s: null pointer", fn);
-    const bool fc = h->cfg.arch == IDQN_ARCH_FC, gc = h->cfg.arch == IDQN_ARCH_CNN && h->gc.on;
+    const bool fc = h->cfg.arch == IDQN_ARCH_FC, gc = (h->cfg.arch == IDQN_ARCH_CNN && h->gc.on) || h->imp.on;
     IDQN_REQUIRE((fc || gc) && h->cfg.n_quantiles == 0 && h->iqn.N == 0,
-                 "%s: serves MLP handles and general-shape cnn handles (plane-path cnn handles: idqn_learn_on_replay; the f32 MFMA "
+                 "%s: serves MLP handles, general-shape cnn handles and impala handles (plane-path cnn handles: idqn_learn_on_replay; the f32 MFMA "
                  "conv mode and quantile heads: gather, then learn on the batch)", fn);
     IDQN_REQUIRE(batch >= 1 && batch <= h->cfg.max_batch, "%s: batch %d not in [1, %d]", fn, batch, h->cfg.max_batch);
     IDQN_REQUIRE(batch_mean_divisor >= batch, "%s: mean divisor %d < batch %d", fn, batch_mean_divisor, batch);
@@ -2423,7 +2739,7 @@ static int replay_fc_check(idqn_handle_t h, const char* fn, const uint8_t* frame
     } else {
         obs_elems = (long)h->cfg.obs_h * h->cfg.obs_w * h->cfg.obs_c;
         IDQN_REQUIRE(stack == h->cfg.obs_c && frame_bytes == (int64_t)h->cfg.obs_h * h->cfg.obs_w,
-                     "%s: a general-shape cnn handle takes uint8 frames of obs_h x obs_w bytes, stack == obs_c (got stack %d, frame_bytes %ld, "
+                     "%s: a general-shape cnn / impala handle takes uint8 frames of obs_h x obs_w bytes, stack == obs_c (got stack %d, frame_bytes %ld, "
                      "obs %d x %d x %d)", fn, stack, (long)frame_bytes, h->cfg.obs_h, h->cfg.obs_w, h->cfg.obs_c);
     }
     *obs_elems_out = obs_elems;
@@ -2559,6 +2875,7 @@ static int learn_steps_on_replay_fc(idqn_handle_t h, const char* fn, const uint8
                                     int32_t batch, int32_t stack, int32_t batch_mean_divisor, uint32_t flags, void* stream) {
     IDQN_REQUIRE(h && frame_ring_dev && rows_dev && (slots_host || slots_dev), "%s: null pointer", fn);
     IDQN_REQUIRE(n_steps >= 1 && n_steps <= IDQN_MAX_STEPS_PER_CALL, "%s: n_steps %d not in [1, %d]", fn, n_steps, IDQN_MAX_STEPS_PER_CALL);
+    IDQN_REFUSE_IMPALA(h, fn);
     IDQN_REQUIRE(flags == 0, "%s: takes no flags (got 0x%x): profile or split a single step through idqn_learn_on_replay_fc", fn, flags);
     IDQN_REQUIRE(!h->is_weight && !h->td_abs,
                  "%s: the handle has prioritized-replay buffers set (idqn_set_per_buffers): weights and |TD| belong to one step", fn);
@@ -2644,6 +2961,7 @@ template <class P>
 static int per_learn_on_replay(idqn_handle_t h, const char* fn, const P& per, const float* tau_dev, const uint8_t* frame_ring_dev, int64_t n_frames,
                                int64_t frame_bytes, const int32_t* rows_dev, int32_t n_steps, int32_t batch, int32_t stack,
                                int32_t batch_mean_divisor, uint32_t flags, void* stream, bool marks) {
+    IDQN_REFUSE_IMPALA(h, fn);
     IDQN_REQUIRE(!(flags & ~(IDQN_F_PROFILE | IDQN_F_PROFILE_ALL)), "%s: only the profile flags are supported (got 0x%x)", fn, flags);
     IDQN_REQUIRE(!h->is_weight && !h->td_abs,
                  "%s: the handle has prioritized-replay buffers set (idqn_set_per_buffers): the call sets its own for its duration", fn);
@@ -2736,6 +3054,7 @@ extern "C" int idqn_iqn_learn_on_batch(idqn_handle_t h, const void* state_dev, c
                                        const float* tau_dev, int32_t batch, uint32_t flags, void* stream) {
     IDQN_REQUIRE(h && state_dev && next_state_dev && action_dev && reward_dev && terminal_dev && tau_dev,
                  "idqn_iqn_learn_on_batch: null pointer");
+    IDQN_REFUSE_IMPALA(h, "idqn_iqn_learn_on_batch");
     IDQN_REQUIRE(h->iqn.N > 0, "idqn_iqn_learn_on_batch: the handle was created without quantile heads (cfg.n_quantiles)");
     IDQN_REQUIRE(batch >= 1 && batch <= 256 && batch <= h->cfg.max_batch, "idqn_iqn_learn_on_batch: batch %d not in [1, min(256, %d)]",
                  batch, h->cfg.max_batch);
@@ -2884,6 +3203,7 @@ extern "C" int idqn_iqn_learn_on_batch(idqn_handle_t h, const void* state_dev, c
 extern "C" int idqn_iqn_q_values(idqn_handle_t h, int32_t which, int32_t head, const void* states_dev, int32_t n,
                                  const float* tau_dev, float* q_out_dev, int32_t* action_out_dev, void* stream) {
     IDQN_REQUIRE(h && states_dev && tau_dev && q_out_dev, "idqn_iqn_q_values: null pointer");
+    IDQN_REFUSE_IMPALA(h, "idqn_iqn_q_values");
     IDQN_REQUIRE(h->iqn.N > 0, "idqn_iqn_q_values: the handle was created without quantile heads (cfg.n_quantiles)");
     IDQN_REQUIRE(head >= 0 && head < h->cfg.n_heads && (which == 0 || which == 1), "idqn_iqn_q_values: bad head / which");
     IDQN_REQUIRE(n >= 1 && n <= h->cfg.max_batch, "idqn_iqn_q_values: n = %d, must be in [1, max_batch = %d]", n, h->cfg.max_batch);
@@ -2904,6 +3224,7 @@ extern "C" int idqn_iqn_q_values(idqn_handle_t h, int32_t which, int32_t head, c
 }
 
 extern "C" int idqn_backward_rest(idqn_handle_t h, void* stream) {
+    IDQN_REFUSE_IMPALA(h, "idqn_backward_rest");
     IDQN_REQUIRE(h && h->pend_B > 0, "idqn_backward_rest: no backward pass is waiting (IDQN_F_STOP_* first)");
     const int B = h->pend_B;
     if (h->pend_stage == 2) h->pend_B = 0;  // stage 1 keeps B for idqn_export / idqn_finish_step_factored
@@ -2912,6 +3233,7 @@ extern "C" int idqn_backward_rest(idqn_handle_t h, void* stream) {
 
 extern "C" int idqn_export_dense0_factors(idqn_handle_t h, float* a3_out_dev, float* dh_out_dev, void* stream) {
     IDQN_REQUIRE(h && a3_out_dev && dh_out_dev, "idqn_export_dense0_factors: null pointer");
+    IDQN_REFUSE_IMPALA(h, "idqn_export_dense0_factors");
     IDQN_REQUIRE(h->pend_stage == 1 && h->pend_B > 0, "idqn_export_dense0_factors: needs IDQN_F_STOP_BEFORE_DENSE0_WGRAD first");
     const long nb = cdiv(h->pend_B, 32), K = h->cfg.n_heads;
     // the online nets are the first K * nb slots of the activation buffer
@@ -2922,6 +3244,7 @@ extern "C" int idqn_export_dense0_factors(idqn_handle_t h, float* a3_out_dev, fl
 
 extern "C" int idqn_dense0_factors(idqn_handle_t h, float** factors_dev, int64_t* n_dh, int64_t* n_a3) {
     IDQN_REQUIRE(h && factors_dev && n_dh && n_a3, "idqn_dense0_factors: null pointer");
+    IDQN_REFUSE_IMPALA(h, "idqn_dense0_factors");
     IDQN_REQUIRE(h->pend_stage == 1 && h->pend_B > 0, "idqn_dense0_factors: needs IDQN_F_STOP_BEFORE_DENSE0_WGRAD first");
     const int nb = cdiv(h->pend_B, 32);
     *factors_dev = dh_of(h, nb);
@@ -2935,6 +3258,7 @@ extern "C" int idqn_finish_step_factored(idqn_handle_t h, const float* a3_all_de
                                          int64_t a3_inner, int64_t dh_outer, int64_t dh_head, int64_t dh_inner,
                                          uint32_t phases, void* stream) {
     IDQN_REQUIRE(h && (phases & 3u) && !(phases & ~3u), "idqn_finish_step_factored: phases must be 1, 2 or 3");
+    IDQN_REFUSE_IMPALA(h, "idqn_finish_step_factored");
     hipStream_t q = (hipStream_t)stream;
     int rc;
     if (phases & IDQN_FACTORED_DENSE0) {
@@ -2957,6 +3281,7 @@ extern "C" int idqn_finish_step_factored(idqn_handle_t h, const float* a3_all_de
 
 int idqn_internal_dp_view(idqn_handle_t h, IdqnDpView* v) {  // (csrc/dp.hip)
     IDQN_REQUIRE(h && v, "null handle");
+    IDQN_REFUSE_IMPALA(h, "the data-parallel step (idqn_dp_*)");
     IDQN_REQUIRE(h->cfg.arch == IDQN_ARCH_CNN && !h->gc.on && h->cfg.n_quantiles == 0,
                  "the data-parallel step is built for the MFMA cnn path of the i-DQN heads");
     v->grad = h->grad; v->losses = h->losses; v->td_abs = h->td_abs; v->n_small = (long)h->cfg.n_heads * h->gP + 64;
@@ -3056,6 +3381,27 @@ static int q_values_impl(idqn_handle_t h, int32_t which, int32_t head, const voi
     IDQN_REQUIRE(n >= 1 && n <= 32, "idqn_q_values: n = %d, must be in [1, 32]", n);
     hipStream_t q = (hipStream_t)stream;
     const float* params = (which ? h->target : h->online) + (long)head * h->L.head_stride;
+    if (h->imp.on) {  // impala: the three Stacks of the one net on the n states, then the generic dense forward
+        const float* const* wb = h->train.wbase + (which * h->cfg.n_heads + head);
+        int rc = impala_trunk(h, wb, 1, 1, n, (const uint8_t*)states_dev, (const uint8_t*)states_dev, h->imp.infer, q);
+        if (rc) return rc;
+        FcQArgs a;
+        a.net = h->fc; a.params = params; a.s = h->imp.infer.x[2][2]; a.n = n; a.q_out = q_out_dev; a.ws = h->imp.inf_ws;
+        if (h->imp.d0_split) {  // Dense_0 over the chip, the layers behind it in k_fc_q
+            ImpD0Args d0;
+            memset(&d0, 0, sizeof(d0));
+            d0.x = h->imp.infer.x[2][2]; d0.hid = h->imp.inf_hid; d0.wbase = wb;
+            d0.w_off = h->fc.w_off[0]; d0.b_off = h->fc.b_off[0]; d0.B = n; d0.F = h->F; d0.D = h->fc.d[1];
+            hipLaunchKernelGGL(k_imp_d0_fwd, dim3((unsigned)cdiv(d0.D, IMP_D0_OC), 1, 1), dim3(256), 0, q, d0);
+            a.net = h->imp.tail; a.s = h->imp.inf_hid;
+        }
+        hipLaunchKernelGGL(k_fc_q, dim3(1), dim3(256), 0, q, a);
+        if (action_out_dev)
+            hipLaunchKernelGGL(k_argmax_rows, dim3(1), dim3(64), 0, q, q_out_dev, n, h->cfg.n_actions, action_out_dev,
+                               (volatile int32_t*)(h->act_use_mail ? h->act_mail_dev : nullptr), h->act_seq);
+        IDQN_HIP_CHECK(hipGetLastError());
+        return IDQN_OK;
+    }
     if (h->gc.on) {  // general-shape cnn: trunk of the one net on the n states, then the generic dense forward
         const float* const* wb = h->train.wbase + (which * h->cfg.n_heads + head);
         int rc = gcnn_trunk(h, wb, 1, 1, n, (const uint8_t*)states_dev, (const uint8_t*)states_dev, h->gc.inf_act, q);
@@ -3169,8 +3515,8 @@ static int act_host_impl(idqn_handle_t h, int32_t which, int32_t head, const voi
     IDQN_REQUIRE(head >= 0 && head < h->cfg.n_heads && (which == 0 || which == 1), "idqn_act_host: bad head / which");
     const bool iqn = tau_host_pinned != nullptr;
     hipStream_t q = (hipStream_t)stream;
-    const bool cnn = h->cfg.arch == IDQN_ARCH_CNN;
-    // bytes of one state: uint8 pixels (cnn) or float32 features (fc)
+    const bool cnn = h->cfg.arch == IDQN_ARCH_CNN || h->imp.on;  // (pixel input)
+    // bytes of one state: uint8 pixels (cnn, impala) or float32 features (fc)
     const size_t E = cnn ? (size_t)h->cfg.obs_h * h->cfg.obs_w * h->cfg.obs_c : (size_t)h->fc.d[0] * 4;
     if (!h->act_state) {  // (fc handles: a few floats)
         IDQN_HIP_CHECK(hipMalloc((void**)&h->act_state, E + 64));
@@ -3182,7 +3528,7 @@ static int act_host_impl(idqn_handle_t h, int32_t which, int32_t head, const voi
     // sequence number the host polls (IDQN_ACT_POLL=0: a device-to-host copy and a stream synchronisation instead).
     // (the i-IQN chain always ends in k_iqn_act_head, which writes the mailbox: it never takes the generic route, so
     // IDQN_ACT_GENERIC has no say in it)
-    const bool poll = !act_no_poll() && (iqn || ((cnn && !h->gc.on) ? (!act_generic() && h->J <= 512 && h->cfg.n_actions <= 32) : true));
+    const bool poll = !act_no_poll() && (iqn || ((cnn && !h->gc.on && !h->imp.on) ? (!act_generic() && h->J <= 512 && h->cfg.n_actions <= 32) : true));
     if (iqn && !h->iact_tau) {
         const long NP = h->iqn.N > 32 ? 64 : 32;
         float* p = nullptr;
@@ -3295,6 +3641,7 @@ extern "C" int idqn_act_host_begin(idqn_handle_t h, int32_t which, int32_t head,
 static int iqn_act_check(idqn_handle_t h, const char* fn, int32_t which, int32_t head, const void* state_host_pinned,
                          const float* tau_host_pinned, float* q_out_dev, int32_t* action_host_pinned) {
     IDQN_REQUIRE(h && state_host_pinned && tau_host_pinned && q_out_dev && action_host_pinned, "%s: null pointer", fn);
+    IDQN_REFUSE_IMPALA(h, fn);
     IDQN_REQUIRE(h->iqn.N > 0, "%s: the handle was created without quantile heads (cfg.n_quantiles)", fn);
     IDQN_REQUIRE(head >= 0 && head < h->cfg.n_heads && (which == 0 || which == 1), "%s: bad head / which", fn);
     IDQN_REQUIRE(h->act_pending == 0, "%s: an acting launch is already pending (idqn_act_host_end collects it)", fn);
@@ -3515,6 +3862,7 @@ static int act_many_chain(idqn_handle_t h, int n, float* q_out_dev, int32_t* mai
 extern "C" int idqn_act_host_many(idqn_handle_t h, int32_t which, const int32_t* heads_host, const void* states_host_pinned, int32_t n,
                                   float* q_out_dev, int32_t* actions_host_pinned, void* stream) {
     IDQN_REQUIRE(h && heads_host && states_host_pinned && q_out_dev && actions_host_pinned, "idqn_act_host_many: null pointer");
+    IDQN_REFUSE_IMPALA(h, "idqn_act_host_many");
     IDQN_REQUIRE(n >= 1 && n <= ACT_MANY_MAX, "idqn_act_host_many: n = %d, must be in [1, %d]", n, ACT_MANY_MAX);
     IDQN_REQUIRE(which == 0 || which == 1, "idqn_act_host_many: which = %d", which);
     const int K = h->cfg.n_heads;
@@ -3571,6 +3919,7 @@ static int fc_act_many_chain(idqn_handle_t h, int n, float* q_out_dev, int32_t* 
 extern "C" int idqn_act_host_many_fc(idqn_handle_t h, int32_t which, const int32_t* heads_host, const void* states_host_pinned, int32_t n,
                                      float* q_out_dev, int32_t* actions_host_pinned, void* stream) {
     IDQN_REQUIRE(h && heads_host && states_host_pinned && q_out_dev && actions_host_pinned, "idqn_act_host_many_fc: null pointer");
+    IDQN_REFUSE_IMPALA(h, "idqn_act_host_many_fc");
     IDQN_REQUIRE(n >= 1 && n <= ACT_MANY_MAX, "idqn_act_host_many_fc: n = %d, must be in [1, %d]", n, ACT_MANY_MAX);
     IDQN_REQUIRE(which == 0 || which == 1, "idqn_act_host_many_fc: which = %d", which);
     const int K = h->cfg.n_heads;
@@ -3629,6 +3978,7 @@ extern "C" int idqn_iqn_act_host_many(idqn_handle_t h, int32_t which, const int3
                                       void* stream) {
     IDQN_REQUIRE(h && heads_host && states_host_pinned && taus_host_pinned && q_out_dev && actions_host_pinned,
                  "idqn_iqn_act_host_many: null pointer");
+    IDQN_REFUSE_IMPALA(h, "idqn_iqn_act_host_many");
     IDQN_REQUIRE(n >= 1 && n <= ACT_MANY_MAX, "idqn_iqn_act_host_many: n = %d, must be in [1, %d]", n, ACT_MANY_MAX);
     IDQN_REQUIRE(which == 0 || which == 1, "idqn_iqn_act_host_many: which = %d", which);
     IDQN_REQUIRE(h->iqn.N > 0, "idqn_iqn_act_host_many: the handle was created without quantile heads (cfg.n_quantiles)");
@@ -3764,6 +4114,7 @@ extern "C" int idqn_group_create(const idqn_handle_t* members, int32_t n_members
     for (int g = 0; g < n_members; ++g) {
         const idqn_handle_t h = members[g];
         IDQN_REQUIRE(h, "idqn_group_create: member %d is null", g);
+        IDQN_REFUSE_IMPALA(h, "idqn_group_create");
         IDQN_REQUIRE(h->cfg.arch == IDQN_ARCH_FC && h->cfg.n_quantiles == 0 && h->iqn.N == 0,
                      "idqn_group_create: member %d is not an MLP (fc) handle: groups serve fc handles only", g);
         IDQN_REQUIRE(h->fcp_plan_.floats != 0,
@@ -4105,6 +4456,7 @@ extern "C" int idqn_act_group_create(const idqn_handle_t* members, int32_t n_mem
     for (int g = 0; g < n_members; ++g) {
         const idqn_handle_t h = members[g];
         IDQN_REQUIRE(h, "%s: member %d is null", fn, g);
+        IDQN_REFUSE_IMPALA(h, fn);
         IDQN_REQUIRE(h->cfg.n_quantiles == 0 && h->iqn.N == 0, "%s: member %d was created with quantile heads", fn, g);
         IDQN_REQUIRE(h->cfg.arch == IDQN_ARCH_CNN, "%s: member %d is an MLP (fc) handle: idqn_group_create serves those", fn, g);
         // (idqn_create sends J > 512 and A > 32 down the general-shape path: named first, under their own texts)

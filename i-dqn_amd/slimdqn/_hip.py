@@ -10,8 +10,8 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("IDQN_HIP_LIB") or os.path.join(os.path.dirname(_HERE), "libidqn_hip.so")  # override: kernel experiments
 
-IDQN_ARCH_CNN, IDQN_ARCH_FC = 0, 1
-IDQN_MAX_FEATURES, IDQN_MAX_LEAVES = 8, 24
+IDQN_ARCH_CNN, IDQN_ARCH_FC, IDQN_ARCH_IMPALA = 0, 1, 2
+IDQN_MAX_FEATURES, IDQN_MAX_LEAVES = 8, 48
 F_GRADS_ONLY, F_PROFILE, F_STOP_AFTER_DENSE0, F_STOP_BEFORE_DENSE0_WGRAD, F_PROFILE_ALL = 1, 2, 4, 8, 16
 FACTORED_DENSE0, FACTORED_REST = 1, 2
 DP_SIDE_STREAM, DP_UNIQUE_ID_BYTES = 1, 128
@@ -247,7 +247,7 @@ def current_stream():
 
 def make_config(arch, n_heads, n_actions, obs, features, max_batch, lr, eps, gamma_n, b1=0.9, b2=0.999, n_quantiles=0):
     cfg = Config()
-    cfg.arch = {"cnn": IDQN_ARCH_CNN, "fc": IDQN_ARCH_FC}[arch]
+    cfg.arch = {"cnn": IDQN_ARCH_CNN, "fc": IDQN_ARCH_FC, "impala": IDQN_ARCH_IMPALA}[arch]
     cfg.n_heads, cfg.n_actions = int(n_heads), int(n_actions)
     cfg.obs_h, cfg.obs_w, cfg.obs_c = (int(x) for x in obs)
     cfg.n_features = len(features)

@@ -14,14 +14,17 @@ import torch
 
 from slimdqn import _hip, prng
 from slimdqn.networks.architectures.dqn import DQNNet
+from slimdqn.networks.architectures.impala import ImpalaNet
+
+PIXEL_ARCHS = ("cnn", "impala")  # uint8 (H, W, C) states; everything else is a flat float32 vector
 
 
 def _obs_triplet(observation_dim, arch):
     if isinstance(observation_dim, (int, np.integer)):
         return (int(observation_dim), 1, 1)
     dims = tuple(int(d) for d in observation_dim)
-    if arch == "cnn":
-        assert len(dims) == 3, "cnn expects observation_dim = (H, W, C)"
+    if arch in PIXEL_ARCHS:
+        assert len(dims) == 3, f"{arch} expects observation_dim = (H, W, C)"
         return dims
     return (int(np.prod(dims)), 1, 1)
 
@@ -86,10 +89,12 @@ class DeviceAgent:
 
     def __init__(self, key, observation_dim, n_actions, n_heads, features, architecture_type, learning_rate, gamma,
                  update_horizon, adam_eps, stacked, init_heads=None):
-        self.network = DQNNet(features, architecture_type, n_actions)
+        self.network = (ImpalaNet(features, n_actions) if architecture_type == "impala"
+                        else DQNNet(features, architecture_type, n_actions))
         self._K = int(n_heads)
         self._stacked = stacked  # iDQN leaves carry a leading K axis, DQN leaves do not
         self._arch = architecture_type
+        self._pixels = architecture_type in PIXEL_ARCHS
         self._obs = _obs_triplet(observation_dim, architecture_type)
         self._lr, self._eps = float(learning_rate), float(adam_eps)
         self.gamma, self.update_horizon = gamma, update_horizon
@@ -108,7 +113,7 @@ class DeviceAgent:
         # that one collective covers them) | [K][w0n] Dense_0/kernel gradients of the cnn
         names = [n for n, _, _ in self._leaves]
         self._w0 = (0, 0)
-        if architecture_type == "cnn":
+        if architecture_type == "cnn":  # (impala: one region, like fc)
             i = names.index("Dense_0/kernel")
             self._w0 = (self._leaves[i][1], self._leaves[i + 1][1])
         self._gP = P - (self._w0[1] - self._w0[0])
@@ -145,9 +150,12 @@ class DeviceAgent:
     def _tree(self, arena):
         tree = {}
         for name, off, shape in self._leaves:
-            mod, leaf = name.split("/")
+            *mods, leaf = name.split("/")  # "Conv_0/kernel", or "Stack_0/Conv_0/kernel": nested as flax nests submodules
             view = arena[:, off : off + int(np.prod(shape))].view((self._K,) + tuple(shape))
-            tree.setdefault(mod, {})[leaf] = view if self._stacked else view[0]
+            node = tree
+            for mod in mods:
+                node = node.setdefault(mod, {})
+            node[leaf] = view if self._stacked else view[0]
         return {"params": tree}
 
     def _ensure_handle(self, batch):
@@ -199,7 +207,7 @@ class DeviceAgent:
         hit = cache.get(id(batch))
         if hit is not None and hit[0] is batch and self._handle is not None and hit[1] <= self._handle_batch:
             return hit[1], hit[2]
-        if self._arch == "cnn":
+        if self._pixels:
             s, s2 = self._dev(batch.state, torch.uint8), self._dev(batch.next_state, torch.uint8)
             assert tuple(s.shape[1:]) == self._obs, f"state shape {tuple(s.shape)} vs observation_dim {self._obs}"
         else:
@@ -253,7 +261,7 @@ class DeviceAgent:
         """Buffer-side conditions of ``idqn_learn_on_replay_fc``, read on every call (the switches included)."""
         return (self.fuse_replay_sampling and hasattr(rb, "sample_slots") and hasattr(rb, "ring_view")
                 and getattr(self, "_replay_fc_ok", True) and os.environ.get("IDQN_LEARN_ON_REPLAY", "1") != "0"
-                and (self._arch == "fc" or (self._arch == "cnn" and self.__dict__.get("_replay_fused_ok") is False)))
+                and (self._arch in ("fc", "impala") or (self._arch == "cnn" and self.__dict__.get("_replay_fused_ok") is False)))
 
     def _ring_fc_fusable(self, ring_view):
         _, _, frame_bytes, _, stack, fshape, fdt = ring_view
@@ -399,7 +407,7 @@ class DeviceAgent:
 
     def _q_values(self, which, head, state):
         """Q-values [n, A] (device) of one head for <= 32 states."""
-        dt = torch.uint8 if self._arch == "cnn" else torch.float32
+        dt = torch.uint8 if self._pixels else torch.float32
         s = self._dev(state, dt)
         n = 1 if s.numel() == int(np.prod(self._obs)) else int(s.shape[0])
         self._ensure_handle(32)
@@ -411,7 +419,7 @@ class DeviceAgent:
     def _best_action(self, which, head, state):
         """Greedy action (device int32 scalar, first maximum on ties) of one head for one state: one C call.
         A host state goes through a pinned staging buffer (a pageable 28 KB upload costs ~100 us, this ~10)."""
-        dt = torch.uint8 if self._arch == "cnn" else torch.float32
+        dt = torch.uint8 if self._pixels else torch.float32
         st = getattr(state, "tensor", state)
         if isinstance(st, torch.Tensor) and st.is_cuda:
             s = self._dev(st, dt)
@@ -477,7 +485,7 @@ class DeviceAgent:
                 continue
             if not staged:
                 if not hasattr(self, "_acts_pin"):
-                    dt = torch.uint8 if self._arch == "cnn" else torch.float32  # the arch's dtype: pixels or features
+                    dt = torch.uint8 if self._pixels else torch.float32  # the arch's dtype: pixels or features
                     self._acts_pin = torch.empty((32, size), dtype=dt).pin_memory()
                     self._acts_pin_np = self._acts_pin.numpy()
                     self._acts_out = torch.zeros(32, dtype=torch.int32).pin_memory()
@@ -511,9 +519,12 @@ class DeviceAgent:
         host = arena.cpu().numpy()
         tree = {}
         for name, off, shape in self._leaves:
-            mod, leaf = name.split("/")
+            *mods, leaf = name.split("/")
             v = host[:, off : off + int(np.prod(shape))].reshape((self._K,) + tuple(shape)).copy()
-            tree.setdefault(mod, {})[leaf] = v if self._stacked else v[0]
+            node = tree
+            for mod in mods:
+                node = node.setdefault(mod, {})
+            node[leaf] = v if self._stacked else v[0]
         return {"params": tree}
 
     def _load_flat(self, arena, flat):

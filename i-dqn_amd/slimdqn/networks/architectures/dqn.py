@@ -4,8 +4,8 @@ The reference's flax module both defines the architecture and executes it; here 
 HIP path (``csrc/cnn_kernels.h`` / ``csrc/fc_kernels.h``), so ``DQNNet`` only carries the
 architecture, produces the parameter pytree layout and initialises parameters with the reference's
 initialiser families: ``xavier_uniform`` for the cnn's convs and dense layers (``:40``),
-``lecun_normal`` for ``fc`` (``:62``), zero biases.  ``impala`` (``:54-60``) is outside the HIP
-path's scope and raises.
+``lecun_normal`` for ``fc`` (``:62``), zero biases.  ``impala`` (``:54-60``) has a descriptor of its
+own, ``architectures/impala.py::ImpalaNet`` (the agents pick it), and raises here.
 """
 from typing import Sequence
 
@@ -16,7 +16,8 @@ class DQNNet:
     def __init__(self, features: Sequence[int], architecture_type: str, n_actions: int):
         if architecture_type not in ("cnn", "fc"):
             raise NotImplementedError(
-                f"architecture_type={architecture_type!r}: only 'cnn' and 'fc' have HIP kernels (impala is out of scope)")
+                f"architecture_type={architecture_type!r}: DQNNet describes 'cnn' and 'fc'; 'impala' is "
+                "slimdqn.networks.architectures.impala.ImpalaNet(features, n_actions), which the agents pick themselves")
         self.features = [int(f) for f in features]
         self.architecture_type = architecture_type
         self.n_actions = int(n_actions)

@@ -166,6 +166,8 @@ class PrioritizedLearner:
             return (view, "iqn") if view is not None and defaults.get("iqn") else None
         if type(agent)._learn is not DeviceAgent._learn:
             return None
+        if agent._arch == "impala":
+            return None  # the one-call forms refuse impala handles: the chain, through the agent's replay-sourced entry
         family = "fc" if agent._arch == "fc" else ("gcnn" if self._general_shape(agent) else "plane")
         if not defaults.get(family):
             return None

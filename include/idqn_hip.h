@@ -27,8 +27,17 @@ extern "C" {
 
 #define IDQN_ARCH_CNN 0         /* slimdqn/networks/architectures/dqn.py:39-53 */
 #define IDQN_ARCH_FC 1          /* slimdqn/networks/architectures/dqn.py:61-63 */
+#define IDQN_ARCH_IMPALA 2      /* slimdqn/networks/architectures/dqn.py:7-29,54-60: three residual Stacks + dense head.
+                                   Served by idqn_learn_on_batch, idqn_learn_on_replay_fc(_dev), idqn_q_values / idqn_best_action,
+                                   idqn_act_host(_begin / _end), the target operations, idqn_apply_adam, idqn_set_per_buffers and the
+                                   debug / profile reads; every other entry answers IDQN_E_INVALID, nothing enqueued.  Its
+                                   gradient arena has no second region (gP = head_stride).  Debug buffers: imp_pool<s>,
+                                   imp_stack<s> (s = 0..2; imp_stack2 is the head's input, after the final ReLU).           */
 #define IDQN_MAX_FEATURES 8
-#define IDQN_MAX_LEAVES 24
+/* impala: 3 Stacks x 5 convs x 2 + the dense leaves.  This was 24 before the impala architecture and idqn_abi_version did
+ * not change: a caller of idqn_layout must size its leaves array by THIS constant (recompile against this header); an array
+ * of 24 overflows on an impala configuration.                                                                          */
+#define IDQN_MAX_LEAVES 48
 
 const char* idqn_last_error(void);
 int idqn_abi_version(void);
@@ -43,7 +52,7 @@ typedef struct idqn_config {
     int32_t n_actions;                    /* A <= 32                                            */
     int32_t obs_h, obs_w, obs_c;          /* cnn: (84, 84, 4); fc: (dim, 1, 1)                    */
     int32_t n_features;
-    int32_t features[IDQN_MAX_FEATURES];  /* cnn: [F0, F1, F2, F3]; fc: hidden widths            */
+    int32_t features[IDQN_MAX_FEATURES];  /* cnn: [F0, F1, F2, F3]; fc: hidden widths; impala: Stack widths, then dense */
     int32_t max_batch;                    /* largest minibatch a call may pass                   */
     /* doubles: folded to f32 inside exactly like the reference's Python floats are by jit        */
     double learning_rate;                 /* optax.adam(lr, eps=adam_eps), idqn.py:52            */
@@ -67,7 +76,7 @@ typedef struct idqn_leaf {
  * The GRADIENT arena has K*head_stride + 64 floats arranged as two contiguous regions (two collectives in the
  * data-parallel step): [K][gP] all leaves except the cnn's Dense_0/kernel (same order; gP = head_stride - its padded
  * size), 64 floats reserved for the caller (the Python mirror keeps the K losses there), then [K][Dense_0/kernel].
- * For the fc architecture the second region is empty and gP = head_stride.                                       */
+ * For the fc and impala architectures the second region is empty and gP = head_stride.                           */
 int idqn_layout(const idqn_config_t* cfg, int32_t* n_leaves, idqn_leaf_t* leaves /*[IDQN_MAX_LEAVES]*/,
                 int64_t* head_stride);
 
