@@ -56,7 +56,8 @@ struct ImpConvArgs {
 };
 
 // forward: out = [relu]( conv(in [relu'd on load]) + bias [+ aux] );  DGRAD: out = dgrad(in) [* (mask > 0)] [+ aux]
-template <int SRC, bool RELU_IN, bool RELU_OUT, bool ADD, bool DGRAD, bool MASK, int CIC>
+// PER_NET_U8 (SRC_U8 with B = 1, imp_act_many_kernels.h): net e reads image e of in_u8[0], not the minibatch all nets share
+template <int SRC, bool RELU_IN, bool RELU_OUT, bool ADD, bool DGRAD, bool MASK, int CIC, bool PER_NET_U8 = false>
 __global__ __launch_bounds__(256) void k_imp_conv(ImpConvArgs a) {
     __shared__ float s_in[CIC * IMP_CHP];
     __shared__ __attribute__((aligned(16))) float s_w[CIC * 9 * IMP_COB];
@@ -67,7 +68,8 @@ __global__ __launch_bounds__(256) void k_imp_conv(ImpConvArgs a) {
     const float* P = a.wbase[net];
     const float* Wg = P + a.w_off;
     const long img_elems = (long)a.H * a.W * a.CI;
-    const void* img = SRC == IMP_SRC_U8 ? (const void*)(a.in_u8[net < a.n_split ? 0 : 1] + (long)b * img_elems)
+    const void* img = SRC == IMP_SRC_U8 ? (PER_NET_U8 ? (const void*)(a.in_u8[0] + (long)net * img_elems)
+                                                      : (const void*)(a.in_u8[net < a.n_split ? 0 : 1] + (long)b * img_elems))
                                         : (const void*)(a.in + ((long)net * a.B + b) * img_elems);
     float acc[2][IMP_CB];
 #pragma unroll

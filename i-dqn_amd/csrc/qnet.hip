@@ -33,6 +33,7 @@
 #include "gcnn_kernels.h"
 #include "impala_kernels.h"
 #include "fc_act_many_kernels.h"
+#include "imp_act_many_kernels.h"
 #include "fc_group_kernels.h"
 #include "dp_internal.h"
 #include "per_step_args.h"
@@ -1145,7 +1146,7 @@ int impala_setup(idqn_handle_s* h) {
 }
 
 // one conv launch of Stack s: `conv` 0..4 forward, or its data gradient (dgrad: in = the output gradient)
-enum ImpKind { IMP_FWD_U8, IMP_FWD_PLAIN, IMP_FWD_INNER, IMP_FWD_RES, IMP_FWD_RES_RELU, IMP_DG_PLAIN, IMP_DG_MASK, IMP_DG_MASK_SKIP };
+enum ImpKind { IMP_FWD_U8, IMP_FWD_U8_PER_NET, IMP_FWD_PLAIN, IMP_FWD_INNER, IMP_FWD_RES, IMP_FWD_RES_RELU, IMP_DG_PLAIN, IMP_DG_MASK, IMP_DG_MASK_SKIP };
 void imp_conv(idqn_handle_s* h, ImpKind kind, int s, int conv, const float* const* wbase, int n_nets, int n_split, int B,
               const uint8_t* s0, const uint8_t* s1, const float* in, float* out, const float* aux, const float* mask, hipStream_t q,
               const char* name) {
@@ -1161,6 +1162,7 @@ void imp_conv(idqn_handle_s* h, ImpKind kind, int s, int conv, const float* cons
     const dim3 blk(256);
     switch (kind) {
     case IMP_FWD_U8: hipLaunchKernelGGL((k_imp_conv<IMP_SRC_U8, false, false, false, false, false, 4>), grid, blk, 0, q, a); break;
+    case IMP_FWD_U8_PER_NET: hipLaunchKernelGGL((k_imp_conv<IMP_SRC_U8, false, false, false, false, false, 4, true>), grid, blk, 0, q, a); break;
     case IMP_FWD_PLAIN: hipLaunchKernelGGL((k_imp_conv<IMP_SRC_F32, false, false, false, false, false, IMP_CIC>), grid, blk, 0, q, a); break;
     case IMP_FWD_INNER: hipLaunchKernelGGL((k_imp_conv<IMP_SRC_F32, true, true, false, false, false, IMP_CIC>), grid, blk, 0, q, a); break;
     case IMP_FWD_RES: hipLaunchKernelGGL((k_imp_conv<IMP_SRC_F32, false, false, true, false, false, IMP_CIC>), grid, blk, 0, q, a); break;
@@ -1180,11 +1182,12 @@ ImpPoolArgs imp_pool_args(const ImpStackL& l, long n_img) {
 }
 
 // the three Stacks of `n_nets` nets (the first n_split read s0, the rest s1) on B samples each, into A
+// per_net_u8 (B = 1, idqn_act_host_many_impala): net e reads state e of s0
 int impala_trunk(idqn_handle_s* h, const float* const* wbase, int n_nets, int n_split, int B, const uint8_t* s0, const uint8_t* s1,
-                 const ImpActs& A, hipStream_t q) {
+                 const ImpActs& A, hipStream_t q, bool per_net_u8 = false) {
     for (int s = 0; s < 3; ++s) {
         const ImpStackL& l = h->imp.st[s];
-        if (s == 0) imp_conv(h, IMP_FWD_U8, s, 0, wbase, n_nets, n_split, B, s0, s1, nullptr, A.c0[s], nullptr, nullptr, q, "k_imp_conv<u8>");
+        if (s == 0) imp_conv(h, per_net_u8 ? IMP_FWD_U8_PER_NET : IMP_FWD_U8, s, 0, wbase, n_nets, n_split, B, s0, s1, nullptr, A.c0[s], nullptr, nullptr, q, "k_imp_conv<u8>");
         else imp_conv(h, IMP_FWD_PLAIN, s, 0, wbase, n_nets, n_split, B, nullptr, nullptr, A.x[s - 1][2], A.c0[s], nullptr, nullptr, q, "k_imp_conv<conv0>");
         ImpPoolArgs p = imp_pool_args(l, (long)n_nets * B);
         p.c0 = A.c0[s]; p.out = A.x[s][0];
@@ -4004,6 +4007,58 @@ extern "C" int idqn_iqn_act_host_many(idqn_handle_t h, int32_t which, const int3
     memcpy(h->many.pin + sizeof(IqnActManyBlock), states_host_pinned, (size_t)n * sb);
     return act_many_run(h, "idqn_iqn_act_host_many", n, sb, q_out_dev, actions_host_pinned, (hipStream_t)stream,
                         [&](hipStream_t qs, int32_t* mail_dev) { return iqn_act_many_chain(h, n, q_out_dev, mail_dev, qs); });
+}
+
+// select_action's greedy branch on an impala handle (imp_act_many_kernels.h): behind the copy node, the one-workgroup launch
+// that resolves the n parameter bases from the uploaded table, the trunk's launches on n nets of one image each in the acting
+// workspace, Dense_0 per group of states with one head (a head with a hidden layer), the tail per state.
+static int imp_act_many_chain(idqn_handle_t h, int n, float* q_out_dev, int32_t* mail_dev, hipStream_t q) {
+    const ActManySlot& s = h->many;
+    const ActManyNets nets = act_many_nets(h);
+    const uint8_t* states = s.block + s.head_bytes;
+    ImpActManyBasesArgs ba;
+    ba.nets = nets; ba.wbase = (const float**)s.a[0];
+    hipLaunchKernelGGL(k_imp_act_many_bases, dim3(1), dim3(64), 0, q, ba);
+    int rc = impala_trunk(h, (const float* const*)s.a[0], n, n, 1, states, states, h->imp.infer, q, true);
+    if (rc) return rc;
+    ImpActManyTailArgs t;
+    memset(&t, 0, sizeof(t));
+    t.f.net = h->fc; t.f.nets = nets; t.f.s = h->imp.infer.x[2][2]; t.f.s_ld = h->F; t.f.ws = h->imp.inf_ws; t.f.q_out = q_out_dev;
+    t.f.action = s.action; t.f.mail = mail_dev; t.f.ctr = s.ctr; t.f.n = n;
+    if (h->imp.d0_split) {
+        const imp_act_many_d0_plan_t pl = imp_act_many_d0_plan(h->F, h->fc.d[1]);
+        ImpActManyD0Args d;
+        d.nets = nets; d.x = h->imp.infer.x[2][2]; d.part = s.part; d.w_off = h->fc.w_off[0]; d.F = h->F; d.D = h->fc.d[1]; d.NP = pl.n_pass;
+        hipLaunchKernelGGL(k_imp_act_many_d0, dim3((unsigned)pl.col_blocks, (unsigned)pl.ranges, (unsigned)std::min(n, h->cfg.n_heads)), dim3(256),
+                           0, q, d);
+        t.f.net = h->imp.tail; t.part = s.part; t.b0_off = h->fc.b_off[0]; t.NP = pl.n_pass; t.D = d.D;
+    }
+    hipLaunchKernelGGL(k_imp_act_many_tail, dim3(n), dim3(256), 0, q, t);
+    return IDQN_OK;
+}
+
+extern "C" int idqn_act_host_many_impala(idqn_handle_t h, int32_t which, const int32_t* heads_host, const void* states_host_pinned, int32_t n,
+                                         float* q_out_dev, int32_t* actions_host_pinned, void* stream) {
+    IDQN_REQUIRE(h, "idqn_act_host_many_impala: null pointer");
+    IDQN_REQUIRE(h->imp.on, "idqn_act_host_many_impala: serves impala handles only (idqn_act_host_many, idqn_act_host_many_fc and "
+                            "idqn_iqn_act_host_many serve the other architectures)");
+    const int K = h->cfg.n_heads;
+    int at = -1;
+    const char* bad = imp_act_many_args_error(n, K, which, heads_host, states_host_pinned, q_out_dev, actions_host_pinned, &at);
+    IDQN_REQUIRE(!bad, "idqn_act_host_many_impala: %s (n = %d, which = %d, state %d)", bad, n, which, at);
+    IDQN_REQUIRE(h->act_pending == 0, "idqn_act_host_many_impala: an idqn_act_host_begin is still waiting for its _end");
+    const size_t sb = (size_t)h->cfg.obs_h * h->cfg.obs_w * h->cfg.obs_c;  // bytes of one state
+    if (!h->many.block) {  // the bases' array, nothing, nothing, the Dense_0 pass sums
+        long fl[4] = {2 * ACT_MANY_MAX, 0, 0, h->imp.d0_split ? (long)imp_act_many_d0_plan(h->F, h->fc.d[1]).part_floats : 0};
+        if (const int rc = act_many_alloc(h, sizeof(ActManyTable), sb, fl, 4)) return rc;
+    }
+    ActManyTable* tb = (ActManyTable*)h->many.pin;
+    act_many_fill_table(tb, which, heads_host, n, K, true);
+    bad = imp_act_many_table_error(n, K, heads_host, tb->head, tb->n_groups, tb->order, tb->g_head, tb->g_start, tb->g_count, &at);
+    IDQN_REQUIRE(!bad, "idqn_act_host_many_impala: the head table is inconsistent: %s (at %d)", bad, at);
+    memcpy(h->many.pin + sizeof(ActManyTable), states_host_pinned, (size_t)n * sb);
+    return act_many_run(h, "idqn_act_host_many_impala", n, sb, q_out_dev, actions_host_pinned, (hipStream_t)stream,
+                        [&](hipStream_t qs, int32_t* mail_dev) { return imp_act_many_chain(h, n, q_out_dev, mail_dev, qs); });
 }
 
 extern "C" int idqn_debug_conv_items(const int64_t* p, int32_t n_params, int32_t n_items, void* out_host) {

@@ -68,7 +68,8 @@ def launch(env_name, algo, argvs, env=None, save_root=None):
     # host work under the acting launch (slimdqn/sample_collection/utils.py, collect_single_sample); IDQN_LOOP_OVERLAP=0: off.
     # Only where the launch is long enough to hide something: the conv nets' ~40 us (Atari-shaped loop 6.15 -> 6.5 k env
     # steps/s); the MLP's ~20 us launch is shorter than what the extra calls cost (7.3 -> 7.0 k), so it stays synchronous.
-    # impala acting is a chain of some twenty launches and the overlap has not been measured on it: synchronous until it is.
+    # impala acting is a chain of some twenty launches -- one idqn_act_host takes 1.44 ms at the workload's widths, 0.19 ms at the
+    # reference's test widths (profiles/impala_act_many.json) -- and the overlap has not been measured on it: synchronous until it is.
     if os.environ.get("IDQN_LOOP_OVERLAP", "1") != "0" and hasattr(agent, "lazy_host_actions") and p["architecture_type"] == "cnn":
         agent.lazy_host_actions = True
         p["overlap_replay_add"] = True

@@ -17,6 +17,7 @@ FACTORED_DENSE0, FACTORED_REST = 1, 2
 DP_SIDE_STREAM, DP_UNIQUE_ID_BYTES = 1, 128
 E_INVALID, E_HIP, E_RANGE, E_ASSERT = -1, -2, -3, -4
 ACT_MANY_MAX, IQN_ACT_MANY_SC = 32, 4  # csrc/act_many_kernels.h, csrc/iqn_act_many_kernels.h: states per call / per Dense_0 chunk
+IMP_ACT_SC, IMP_ACT_PASS, IMP_ACT_OC, IMP_ACT_PPW = 8, 64, 64, 4  # csrc/imp_act_many_args.h: the Dense_0 plan of idqn_act_host_many_impala
 MAX_STEPS_PER_CALL, STEPS_STAGING_DEPTH = 32, 4  # include/idqn_hip.h: idqn_learn_steps_on_replay_fc, steps per call / slot staging blocks
 # csrc/replay.hip, replay_add_step: frames in / ring writes / rows per call, and the byte offset of the frames in its block
 REPLAY_STEP_MAX_IN, REPLAY_STEP_MAX_WRITES, REPLAY_STEP_MAX_ROWS = 32, 64, 128
@@ -149,6 +150,7 @@ SYMBOLS = {
     "idqn_act_host_end": (C.c_int, [_P, _P, _P]),
     "idqn_act_host_many": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _P, _P, _P]),
     "idqn_act_host_many_fc": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _P, _P, _P]),
+    "idqn_act_host_many_impala": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _P, _P, _P]),
     "idqn_iqn_act_host": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     "idqn_iqn_act_host_begin": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     "idqn_iqn_act_host_many": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P]),

@@ -86,6 +86,10 @@ class _PendingHostAction:
 
 class DeviceAgent:
     lazy_host_actions = False  # True (the trainer of this build sets it): best_action on a host state returns a pending action
+    # n for which an impala agent's ``_best_actions`` asks idqn_act_host_many_impala: the sizes whose one call measured a median
+    # below the MINIMUM of the loop of n idqn_act_host calls, on both shapes and both head assignments
+    # (tools/bench_impala_act_many.py -> profiles/impala_act_many.json).  Sizes that lost and sizes not measured stay on the loop.
+    act_many_imp_sizes = frozenset({1, 2, 3, 4, 8, 16, 32})
 
     def __init__(self, key, observation_dim, n_actions, n_heads, features, architecture_type, learning_rate, gamma,
                  update_horizon, adam_eps, stacked, init_heads=None):
@@ -465,7 +469,8 @@ class DeviceAgent:
         cnn handles (the Dense_0 stream shared among the states of a head); a handle outside its domain answers
         ``E_INVALID`` once and ``idqn_act_host_many_fc`` (MLP, general-shape cnn) is tried under a flag of its own.  A
         handle both refuse (quantile heads, ...) acts through a loop of ``_best_action`` from then on: same actions, same
-        Q rows."""
+        Q rows.  An impala agent -- both refuse it -- asks ``idqn_act_host_many_impala`` third, under ``_act_many_imp_ok`` and
+        by the same protocol, for the n in ``act_many_imp_sizes``; every other n stays on the loop."""
         heads = np.ascontiguousarray(np.asarray(heads, np.int32).reshape(-1))
         n = int(heads.size)
         if not 1 <= n <= 32 or len(states) != n:
@@ -480,7 +485,10 @@ class DeviceAgent:
         assert all(a.size == size for a in srcs), "best_actions takes single states"
         self._ensure_handle(32)
         staged = False
-        for flag, entry in (("_act_many_ok", "idqn_act_host_many"), ("_act_many_fc_ok", "idqn_act_host_many_fc")):
+        entries = [("_act_many_ok", "idqn_act_host_many"), ("_act_many_fc_ok", "idqn_act_host_many_fc")]
+        if getattr(self, "_arch", None) == "impala" and n in self.act_many_imp_sizes:
+            entries.append(("_act_many_imp_ok", "idqn_act_host_many_impala"))
+        for flag, entry in entries:
             if not getattr(self, flag, True):
                 continue
             if not staged:

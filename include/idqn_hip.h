@@ -356,6 +356,20 @@ int idqn_act_host_many(idqn_handle_t h, int32_t which, const int32_t* heads_host
 int idqn_act_host_many_fc(idqn_handle_t h, int32_t which, const int32_t* heads_host, const void* states_host_pinned, int32_t n,
                           float* q_out_dev, int32_t* actions_host_pinned, void* stream);
 
+/* The same call for impala handles (arch == IDQN_ARCH_IMPALA), which the two entries above refuse.  Signature and contract
+ * of idqn_act_host_many_fc; the n states in PINNED host memory are uint8 pixels [n][H][W][C].  Row e of q_out_dev [n][A]
+ * and actions_host_pinned[e] are, byte for byte, what idqn_act_host gives for (which, heads_host[e], state e): the n
+ * states run as n nets of one image each through the conv and pool kernels of the single-state path, a head's states
+ * share ONE stream of its Dense_0/kernel, spread over the chip with every 64-feature pass sum stored and added to the
+ * bias in pass order, and one workgroup per state runs the layers behind it (csrc/imp_act_many_kernels.h).  Every shape
+ * idqn_create accepts for the architecture is served (heads without a hidden layer, A > 32).  Blocking; one linear
+ * hipGraph per (n, buffers), heads and `which` travel as data and the parameter bases are resolved on the device; the
+ * handle's many-state slot and mailbox; IDQN_ACT_GRAPH=0 and IDQN_ACT_POLL=0 as for idqn_act_host.  IDQN_E_INVALID,
+ * before anything is enqueued or allocated on the device: a handle of another architecture, a null pointer, n outside
+ * [1, 32], which not 0 / 1, a head outside [0, K), an idqn_act_host_begin still pending.                                */
+int idqn_act_host_many_impala(idqn_handle_t h, int32_t which, const int32_t* heads_host, const void* states_host_pinned, int32_t n,
+                              float* q_out_dev, int32_t* actions_host_pinned, void* stream);
+
 /* The same for the i-IQN heads: the acting rule of idqn_iqn_act_host for n <= 32 host states at once, one head and N
  * fractions each.  heads_host [n] (ordinary host memory, read before the call returns), n uint8 states and the fractions
  * taus [n][N] in (0, 1) in PINNED host memory.  BYTE IDENTITY: row e of q_out_dev [n][A] and actions_host_pinned[e] are,
