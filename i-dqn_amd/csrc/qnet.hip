@@ -32,6 +32,7 @@
 #include "iqn_kernels.h"
 #include "gcnn_kernels.h"
 #include "impala_kernels.h"
+#include "impala_mx_kernels.h"
 #include "fc_act_many_kernels.h"
 #include "imp_act_many_kernels.h"
 #include "fc_group_kernels.h"
@@ -315,6 +316,7 @@ struct ImpActs { float *c0[3], *x[3][3], *y[3][2]; };
 struct ImpStackL { int H, W, CI, CO, PH, PW, lo_h, lo_w; long w_off[5], b_off[5]; };
 struct ImpalaWs {
     bool on = false;
+    bool mx = false;  // IDQN_IMP_CONV=bf16x3: eligible convs (imx_eligible) run on k_imp_conv_mx, forward and data gradient
     int Bmax = 0;
     ImpStackL st[3];
     ImpActs train, infer;  // the 2K training nets x Bmax samples; one net x 32 states (acting)
@@ -1158,8 +1160,24 @@ void imp_conv(idqn_handle_s* h, ImpKind kind, int s, int conv, const float* cons
     a.H = conv == 0 ? l.H : l.PH; a.W = conv == 0 ? l.W : l.PW;
     const int leaf_ci = conv == 0 ? l.CI : l.CO;
     a.CI = dg ? l.CO : leaf_ci; a.CO = dg ? leaf_ci : l.CO;
-    const dim3 grid((unsigned)(cdiv(a.H, IMP_TH) * cdiv(a.W, IMP_TW)), (unsigned)cdiv(a.CO, IMP_COB), (unsigned)(n_nets * B));
     const dim3 blk(256);
+    if (h->imp.mx && kind >= IMP_FWD_PLAIN && imx_eligible(leaf_ci, l.CO)) {  // the uint8 conv and every other layer: below
+        const imx_plan_t p = imx_plan(a.H, a.W, a.CO, (long)n_nets * B);
+        const dim3 mgrid(p.tiles, p.n_tiles, p.images);
+        switch (kind) {
+        case IMP_FWD_PLAIN: hipLaunchKernelGGL((k_imp_conv_mx<false, false, false, false, false>), mgrid, blk, 0, q, a); name = "k_imp_conv_mx<conv0>"; break;
+        case IMP_FWD_INNER: hipLaunchKernelGGL((k_imp_conv_mx<true, true, false, false, false>), mgrid, blk, 0, q, a); name = "k_imp_conv_mx<inner>"; break;
+        case IMP_FWD_RES: hipLaunchKernelGGL((k_imp_conv_mx<false, false, true, false, false>), mgrid, blk, 0, q, a); name = "k_imp_conv_mx<res>"; break;
+        case IMP_FWD_RES_RELU: hipLaunchKernelGGL((k_imp_conv_mx<false, true, true, false, false>), mgrid, blk, 0, q, a); name = "k_imp_conv_mx<res>"; break;
+        case IMP_DG_PLAIN: hipLaunchKernelGGL((k_imp_conv_mx<false, false, false, true, false>), mgrid, blk, 0, q, a); name = "k_imp_conv_mx<dgrad>"; break;
+        case IMP_DG_MASK: hipLaunchKernelGGL((k_imp_conv_mx<false, false, false, true, true>), mgrid, blk, 0, q, a); name = "k_imp_conv_mx<dgrad mask>"; break;
+        case IMP_DG_MASK_SKIP: hipLaunchKernelGGL((k_imp_conv_mx<false, false, true, true, true>), mgrid, blk, 0, q, a); name = "k_imp_conv_mx<dgrad mask skip>"; break;
+        default: break;
+        }
+        tl_mark(h, q, name);
+        return;
+    }
+    const dim3 grid((unsigned)(cdiv(a.H, IMP_TH) * cdiv(a.W, IMP_TW)), (unsigned)cdiv(a.CO, IMP_COB), (unsigned)(n_nets * B));
     switch (kind) {
     case IMP_FWD_U8: hipLaunchKernelGGL((k_imp_conv<IMP_SRC_U8, false, false, false, false, false, 4>), grid, blk, 0, q, a); break;
     case IMP_FWD_U8_PER_NET: hipLaunchKernelGGL((k_imp_conv<IMP_SRC_U8, false, false, false, false, false, 4, true>), grid, blk, 0, q, a); break;
@@ -2383,8 +2401,12 @@ extern "C" int idqn_create(const idqn_config_t* cfg, float* online_dev, float* t
     int ndev = 0;
     IDQN_HIP_CHECK(hipGetDeviceCount(&ndev));
     IDQN_REQUIRE(ndev > 0, "idqn_create: no HIP device");
+    // impala conv arithmetic: the vector-ALU kernels (the default), or the matrix-core kernel where a layer is eligible
+    const char* imp_mode = getenv("IDQN_IMP_CONV");
+    IDQN_REQUIRE(cfg->arch != IDQN_ARCH_IMPALA || imx_mode_of(imp_mode) != IMX_MODE_BAD, "IDQN_IMP_CONV must be valu or bf16x3, got '%s'", imp_mode);
     idqn_handle_s* h = new idqn_handle_s();
     h->cfg = *cfg;
+    h->imp.mx = cfg->arch == IDQN_ARCH_IMPALA && imx_mode_of(imp_mode) == IMX_MODE_BF16X3;
     int rc = build_layout(*cfg, h->L);
     if (rc) { delete h; return rc; }
     h->online = online_dev; h->target = target_dev; h->mu = mu_dev; h->nu = nu_dev; h->grad = grad_dev;
