@@ -33,6 +33,7 @@
 #include "gcnn_kernels.h"
 #include "impala_kernels.h"
 #include "impala_mx_kernels.h"
+#include "impala_mx_wgrad_kernels.h"
 #include "fc_act_many_kernels.h"
 #include "imp_act_many_kernels.h"
 #include "fc_group_kernels.h"
@@ -323,6 +324,7 @@ struct ImpalaWs {
     float *d[3] = {nullptr, nullptr, nullptr};    // [K][Bmax][PH][PW][CO]: gradient of the Stack's running x
     float *t[3] = {nullptr, nullptr, nullptr};    // same shape: gradient of y (the inner conv's output)
     float *dc0[3] = {nullptr, nullptr, nullptr};  // [K][Bmax][H][W][CO]: gradient of Conv_0's output
+    bool wmx = false;  // IDQN_IMP_WGRAD=bf16x3: the same layers' weight gradients run on k_imp_wgrad_mx
     float* wpart = nullptr;  // weight-gradient partials of one conv [K][chunks][9 CI CO + CO] (sized for the largest)
     float* inf_ws = nullptr;
     // a head with a hidden layer: Dense_0 runs on the k_imp_d0_* kernels, k_fc_step on the layers behind it (`tail`)
@@ -1086,6 +1088,10 @@ int impala_setup(idqn_handle_s* h) {
             l.w_off[i] = h->L.leaves[10 * s + 2 * i].offset;
             l.b_off[i] = h->L.leaves[10 * s + 2 * i + 1].offset;
             part_max = std::max(part_max, (long)imp_wgrad_chunks(l, i, B) * (9L * (i == 0 ? l.CI : l.CO) * l.CO + l.CO));
+            if (w.wmx && !(s == 0 && i == 0) && imx_eligible(i == 0 ? l.CI : l.CO, l.CO)) {  // the larger of the two plans
+                const imxw_plan_t p = imxw_plan((int)B, i == 0 ? l.H : l.PH, i == 0 ? l.W : l.PW, i == 0 ? l.CI : l.CO, l.CO);
+                part_max = std::max(part_max, (long)p.n_chunks * p.part_len);
+            }
         }
         ih = l.PH; iw = l.PW; ci = l.CO;
     }
@@ -1229,13 +1235,23 @@ void imp_wgrad(idqn_handle_s* h, int s, int conv, int B, const uint8_t* st, cons
     ImpWgradArgs a;
     a.in_u8 = st; a.in = in; a.dy = dy; a.part = h->imp.wpart; a.B = B;
     a.H = conv == 0 ? l.H : l.PH; a.W = conv == 0 ? l.W : l.PW; a.CI = conv == 0 ? l.CI : l.CO; a.CO = l.CO;
-    a.n_tiles = B * cdiv(a.H, IMP_TH) * cdiv(a.W, IMP_TW);
-    a.n_chunks = cdiv(a.n_tiles, IMP_WG_TILES);
-    const dim3 grid((unsigned)a.n_chunks, (unsigned)(cdiv(a.CI, IMP_CIC) * cdiv(a.CO, IMP_COB)), (unsigned)K);
-    if (st) hipLaunchKernelGGL((k_imp_wgrad<IMP_SRC_U8, false>), grid, dim3(256), 0, q, a);
-    else if (relu_in) hipLaunchKernelGGL((k_imp_wgrad<IMP_SRC_F32, true>), grid, dim3(256), 0, q, a);
-    else hipLaunchKernelGGL((k_imp_wgrad<IMP_SRC_F32, false>), grid, dim3(256), 0, q, a);
-    tl_mark(h, q, "k_imp_wgrad");
+    if (h->imp.wmx && !st && imx_eligible(a.CI, a.CO)) {  // the uint8 conv and every other layer: below
+        const imxw_plan_t p = imxw_plan(B, a.H, a.W, a.CI, a.CO);
+        a.n_tiles = (int)p.n_tiles;
+        a.n_chunks = (int)p.n_chunks;
+        const dim3 mgrid(p.n_chunks, p.m_blocks * p.n_blocks, (unsigned)K);
+        if (relu_in) hipLaunchKernelGGL((k_imp_wgrad_mx<true>), mgrid, dim3(256), 0, q, a);
+        else hipLaunchKernelGGL((k_imp_wgrad_mx<false>), mgrid, dim3(256), 0, q, a);
+        tl_mark(h, q, "k_imp_wgrad_mx");
+    } else {
+        a.n_tiles = B * cdiv(a.H, IMP_TH) * cdiv(a.W, IMP_TW);
+        a.n_chunks = cdiv(a.n_tiles, IMP_WG_TILES);
+        const dim3 grid((unsigned)a.n_chunks, (unsigned)(cdiv(a.CI, IMP_CIC) * cdiv(a.CO, IMP_COB)), (unsigned)K);
+        if (st) hipLaunchKernelGGL((k_imp_wgrad<IMP_SRC_U8, false>), grid, dim3(256), 0, q, a);
+        else if (relu_in) hipLaunchKernelGGL((k_imp_wgrad<IMP_SRC_F32, true>), grid, dim3(256), 0, q, a);
+        else hipLaunchKernelGGL((k_imp_wgrad<IMP_SRC_F32, false>), grid, dim3(256), 0, q, a);
+        tl_mark(h, q, "k_imp_wgrad");
+    }
     ImpWreduceArgs r;
     r.part = h->imp.wpart; r.grad = h->grad; r.gm = GradMap{h->gP, h->g_w0_begin, h->g_w0_end, h->g_w0_base};
     r.w_off = l.w_off[conv]; r.b_off = l.b_off[conv]; r.nw = 9L * a.CI * a.CO; r.CO = a.CO; r.n_chunks = a.n_chunks;
@@ -2404,9 +2420,12 @@ extern "C" int idqn_create(const idqn_config_t* cfg, float* online_dev, float* t
     // impala conv arithmetic: the vector-ALU kernels (the default), or the matrix-core kernel where a layer is eligible
     const char* imp_mode = getenv("IDQN_IMP_CONV");
     IDQN_REQUIRE(cfg->arch != IDQN_ARCH_IMPALA || imx_mode_of(imp_mode) != IMX_MODE_BAD, "IDQN_IMP_CONV must be valu or bf16x3, got '%s'", imp_mode);
+    const char* imp_wmode = getenv("IDQN_IMP_WGRAD");  // the same for their weight gradients, independently
+    IDQN_REQUIRE(cfg->arch != IDQN_ARCH_IMPALA || imx_mode_of(imp_wmode) != IMX_MODE_BAD, "IDQN_IMP_WGRAD must be valu or bf16x3, got '%s'", imp_wmode);
     idqn_handle_s* h = new idqn_handle_s();
     h->cfg = *cfg;
     h->imp.mx = cfg->arch == IDQN_ARCH_IMPALA && imx_mode_of(imp_mode) == IMX_MODE_BF16X3;
+    h->imp.wmx = cfg->arch == IDQN_ARCH_IMPALA && imx_mode_of(imp_wmode) == IMX_MODE_BF16X3;
     int rc = build_layout(*cfg, h->L);
     if (rc) { delete h; return rc; }
     h->online = online_dev; h->target = target_dev; h->mu = mu_dev; h->nu = nu_dev; h->grad = grad_dev;
