@@ -43,6 +43,7 @@
 #include "per_group_steps_args.h"
 #include "convp_fwd_phases.h"
 #include "convp_items.h"
+#include "staging_ring.h"
 
 namespace {
 
@@ -60,6 +61,10 @@ bool act_generic() { static const bool on = getenv("IDQN_ACT_GENERIC") != nullpt
 // stream synchronisation instead of the polled mailbox, IDQN_ACT_GRAPH=0 launches eagerly instead of replaying a hipGraph
 bool act_no_poll() { static const bool on = getenv("IDQN_ACT_POLL") && atoi(getenv("IDQN_ACT_POLL")) == 0; return on; }
 bool act_use_graph() { static const bool on = !(getenv("IDQN_ACT_GRAPH") && atoi(getenv("IDQN_ACT_GRAPH")) == 0); return on; }
+// the replay-sourced MLP step's two A/B switches: IDQN_FC_REPLAY_STAGE=1 (read once) sends every batch through the staging launch,
+// IDQN_FC_LEARN_STEPS_LOOP=1 (read per call: the bench switches it between its legs) runs an n-step call as n single steps
+bool fc_replay_always_stage() { static const bool on = getenv("IDQN_FC_REPLAY_STAGE") && atoi(getenv("IDQN_FC_REPLAY_STAGE")) != 0; return on; }
+bool fc_steps_force_loop() { const char* e = getenv("IDQN_FC_LEARN_STEPS_LOOP"); return e && atoi(e) != 0; }
 
 int cu_budget() { return 256; }  // CUs a launch plan may fill
 
@@ -428,13 +433,8 @@ struct idqn_handle_s {
     bool fcm_global_ = false;  // the plan is fc_mfma_plan_g: weight operands from global memory
     FcParPlan fcp_plan_;  // LDS plan of k_fc_step_par (floats = 0: does not fit); batches of <= 32 samples run it
     FcParPlan fcs_plan_;  // LDS plan of k_fc_steps_par (fc_steps_kernels.h; floats = 0: idqn_learn_steps_on_replay_fc loops over the single step)
-    // slot staging of idqn_learn_steps_on_replay_fc (host form): a ring of {pinned block, device block, event}; a block is
-    // rewritten only after the event recorded behind the launch that read it has passed
-    int32_t* steps_pin[IDQN_STEPS_STAGING_DEPTH] = {};
-    int32_t* steps_dev[IDQN_STEPS_STAGING_DEPTH] = {};
-    hipEvent_t steps_ev[IDQN_STEPS_STAGING_DEPTH] = {};
-    bool steps_busy[IDQN_STEPS_STAGING_DEPTH] = {};
-    int steps_next = 0;
+    // slot staging of idqn_learn_steps_on_replay_fc (host form) and the uniforms of the prioritized entries (staging_ring.h)
+    StagingRing steps;
     // timeline of a whole step (IDQN_F_PROFILE_ALL): one event after every launch; idqn_profile_table averages per name
     std::vector<hipEvent_t> tl_ev;
     std::vector<const char*> tl_name;
@@ -448,20 +448,15 @@ struct idqn_handle_s {
     // stride gP = P - w0n), 64 floats reserved for the caller (losses), then [K][w0n] Dense_0/kernel gradients.
     // Two contiguous regions = two collectives in the data-parallel step.  fc: w0n = 0, gP = P.
     long gP = 0, g_w0_begin = 0, g_w0_end = 0, g_w0_base = 0;
-    // replay-sourced step (idqn_learn_on_replay): set for the duration of the call, the staging launch gathers from the ring
-    // (slots_dev != nullptr: the slots are read from that device array and `slots` is unused)
-    struct ReplaySrc { const uint8_t* frames; const int32_t* rows; long n_frames, frame_bytes; const int32_t* slots_dev; StageSlots slots; };
-    const ReplaySrc* rp = nullptr;
+    // replay-sourced step (idqn_learn_on_replay): the staging launch gathers from the ring (StepIn, below) into these
     int32_t* rp_action = nullptr;   // [max_batch] scalars of the sampled rows, written by the staging launch
     float* rp_reward = nullptr;
     uint8_t* rp_terminal = nullptr;
     // replay-sourced step of the fc / general-shape cnn handles (idqn_learn_on_replay_fc; replay_src_kernels.h): the staging
-    // launch's stacked minibatches [max_batch][obs], and -- set for the duration of a call whose batch runs k_fc_step_par --
-    // the ring as that kernel's minibatch source (slots_dev != nullptr: read from that device array, `slots` unused)
+    // launch's stacked minibatches [max_batch][obs]
     void *rp_state = nullptr, *rp_next = nullptr;
-    struct FcReplaySrc { const void* frames; const int32_t* rows; long n_frames, frame_bytes; int stack; const int32_t* slots_dev; RpsSlotsPar slots; };
-    const FcReplaySrc* rpf = nullptr;
-    const float* is_weight = nullptr;  // prioritized-replay extension (idqn_set_per_buffers)
+    // prioritized-replay extension: written by idqn_set_per_buffers only, read where a public learner entry fills its StepIn
+    const float* is_weight = nullptr;
     float* td_abs = nullptr;
     bool d0_rows = false;  // the last fused Dense_0 launch (pairs of column tiles) finished dL/da3 itself
     bool wt_ready = false;  // the data-gradient kernels of this step are built (k_td_dh_wt)
@@ -473,6 +468,46 @@ struct idqn_handle_s {
 };
 
 namespace {
+
+// What ONE gradient step is told beside the handle: every learner entry fills one and hands it to learn_step.
+// The minibatch is either five device tensors, or (`frames` set) the replay frame ring with the sampled element slots -- then
+// action / reward / terminal (and, on the MLP staging route, state / next_state) name handle-owned buffers (h->rp_*) that the
+// step's first launch fills.  Only that FIRST launch reads the ring, the rows and the slots (the staging launch of cnn_forward,
+// k_rps_stage, or k_fc_step_par with the ring as its source); everything after it -- on a split step (IDQN_F_STOP_*) the rest
+// that idqn_backward_rest / idqn_finish_step_factored enqueue later included -- reads the handle-owned copies.  So a StepIn is a
+// stack local of the entry, dropped on return, and the later calls need nothing of it.
+struct StepIn {
+    const char* fn = "";  // the entry's name, for messages
+    int batch = 0, mean_divisor = 0;
+    uint32_t flags = 0;
+    const void *state = nullptr, *next_state = nullptr;
+    const int32_t* action = nullptr;
+    const float* reward = nullptr;
+    const uint8_t* terminal = nullptr;
+    // the frame ring as the source (frames != nullptr); exactly one of slots_dev (int32 [batch] on the device) and slots_host
+    // (read before the call returns: the first launch takes them by value, slot_block) is set
+    const void* frames = nullptr;
+    const int32_t* rows = nullptr;
+    long n_frames = 0, frame_bytes = 0;
+    int stack = 0;
+    const int32_t *slots_dev = nullptr, *slots_host = nullptr;
+    const float* tau = nullptr;  // the fractions of a quantile step (selects iqn_learn)
+    // importance weights and |TD| output of THIS step: a public entry copies h->is_weight / h->td_abs, the prioritized driver
+    // names the step's own rows
+    const float* is_weight = nullptr;
+    float* td_abs = nullptr;
+
+    bool stop0() const { return flags & IDQN_F_STOP_AFTER_DENSE0; }
+    bool stopb() const { return flags & IDQN_F_STOP_BEFORE_DENSE0_WGRAD; }
+    bool grads_only() const { return (flags & IDQN_F_GRADS_ONLY) || stop0() || stopb(); }
+    bool profile() const { return flags & IDQN_F_PROFILE; }
+    template <class Slots>  // StageSlots, RpsSlotsPar
+    Slots slot_block() const {
+        Slots s = {};
+        memcpy(s.slot, slots_host, (size_t)batch * 4);
+        return s;
+    }
+};
 
 int alloc_zero(float** p, long n_floats, idqn_handle_s* h, const char* name) {
     IDQN_HIP_CHECK(hipMalloc((void**)p, (size_t)n_floats * 4));
@@ -1009,17 +1044,18 @@ static void fc_step_par_launch(idqn_handle_s* h, hipStream_t q, const FcArgs& a,
     hipLaunchKernelGGL((k_fc_step_par<false, Src>), grid, dim3(FCM_T), lds, q, a, h->fcp_plan_, h->ad, h->online, h->mu, h->nu, adam, src);
 }
 
-int gcnn_learn(idqn_handle_s* h, const uint8_t* st, const uint8_t* st2, const int32_t* action, const float* reward,
-               const uint8_t* terminal, int B, int Bdiv, bool grads_only, bool profile, hipStream_t q) {
+int gcnn_learn(idqn_handle_s* h, const StepIn& in, hipStream_t q) {
     GcnnWs& g = h->gc;
-    const int K = h->cfg.n_heads;
+    const int K = h->cfg.n_heads, B = in.batch;
+    const uint8_t *st = (const uint8_t*)in.state, *st2 = (const uint8_t*)in.next_state;
+    const bool profile = in.profile();
     IDQN_REQUIRE(B <= g.Bmax, "batch %d exceeds the workspace (%d)", B, g.Bmax);
     int rc = gcnn_trunk(h, h->train.wbase, 2 * K, K, B, st, st2, g.act, q);
     if (rc) return rc;
-    FcArgs a = fc_args(h, B, Bdiv, grads_only);
+    FcArgs a = fc_args(h, B, in.mean_divisor, in.grads_only());
     a.s = g.act[2]; a.s2 = g.act[2] + (long)K * B * h->F; a.s_stride = (long)B * h->F; a.din = g.dact[2];
-    a.action = action; a.reward = reward; a.terminal = terminal;
-    a.is_weight = h->is_weight; a.td_abs = h->td_abs;
+    a.action = in.action; a.reward = in.reward; a.terminal = in.terminal;
+    a.is_weight = in.is_weight; a.td_abs = in.td_abs;
     if (profile && h->ev_used + 2 <= (int)h->ev.size()) IDQN_HIP_CHECK(hipEventRecord(h->ev[h->ev_used], q));
     hipLaunchKernelGGL(k_fc_step, dim3(K), dim3(256), 0, q, a);
     if (profile && h->ev_used + 2 <= (int)h->ev.size()) {
@@ -1259,15 +1295,16 @@ void imp_wgrad(idqn_handle_s* h, int s, int conv, int B, const uint8_t* st, cons
     tl_mark(h, q, "k_imp_wreduce");
 }
 
-int impala_learn(idqn_handle_s* h, const uint8_t* st, const uint8_t* st2, const int32_t* action, const float* reward,
-                 const uint8_t* terminal, int B, int Bdiv, bool grads_only, bool profile, hipStream_t q) {
+int impala_learn(idqn_handle_s* h, const StepIn& in, hipStream_t q) {
     ImpalaWs& w = h->imp;
     const ImpActs& A = w.train;
-    const int K = h->cfg.n_heads;
+    const int K = h->cfg.n_heads, B = in.batch;
+    const uint8_t *st = (const uint8_t*)in.state, *st2 = (const uint8_t*)in.next_state;
+    const bool profile = in.profile();
     IDQN_REQUIRE(B <= w.Bmax, "batch %d exceeds the workspace (%d)", B, w.Bmax);
     int rc = impala_trunk(h, h->train.wbase, 2 * K, K, B, st, st2, A, q);
     if (rc) return rc;
-    FcArgs a = fc_args(h, B, Bdiv, grads_only);
+    FcArgs a = fc_args(h, B, in.mean_divisor, in.grads_only());
     a.s = A.x[2][2]; a.s2 = A.x[2][2] + (long)K * B * h->F; a.s_stride = (long)B * h->F; a.din = w.d[2];
     ImpD0Args d0;
     const int D = h->fc.d[1], sblocks = cdiv(B, IMP_D0_SB);
@@ -1279,8 +1316,8 @@ int impala_learn(idqn_handle_s* h, const uint8_t* st, const uint8_t* st2, const 
         tl_mark(h, q, "k_imp_d0_fwd");
         a.net = w.tail; a.s = w.hid; a.s2 = w.hid + (long)K * B * D; a.s_stride = (long)B * D; a.din = w.dhid;
     }
-    a.action = action; a.reward = reward; a.terminal = terminal;
-    a.is_weight = h->is_weight; a.td_abs = h->td_abs;
+    a.action = in.action; a.reward = in.reward; a.terminal = in.terminal;
+    a.is_weight = in.is_weight; a.td_abs = in.td_abs;
     if (profile && h->ev_used + 2 <= (int)h->ev.size()) IDQN_HIP_CHECK(hipEventRecord(h->ev[h->ev_used], q));
     hipLaunchKernelGGL(k_fc_step, dim3(K), dim3(256), 0, q, a);
     tl_mark(h, q, "k_fc_step");
@@ -1675,8 +1712,9 @@ int plan_wgrad(idqn_handle_s* h, int layer, int nb, WgradPlan** out, int n_chunk
 }
 
 // staging launch: pixels -> bf16 plane, conv kernels -> packed planes (forward kernels of every net of the set, and
-// for the training set the data-gradient kernels of the K online nets)
-int planes_stage(idqn_handle_s* h, NetSet& s, const uint8_t* st, const uint8_t* st2, int B, int nb, hipStream_t q) {
+// for the training set the data-gradient kernels of the K online nets).  `ring`: the step input of a replay-sourced training
+// step -- the pixels are gathered from its frame ring and the sampled rows' scalars written to h->rp_action / _reward / _terminal
+int planes_stage(idqn_handle_s* h, NetSet& s, const uint8_t* st, const uint8_t* st2, int B, int nb, hipStream_t q, const StepIn* ring) {
     StageArgs a;
     memset(&a, 0, sizeof(a));
     a.src[0] = st; a.src[1] = st2 ? st2 : st;
@@ -1714,10 +1752,12 @@ int planes_stage(idqn_handle_s* h, NetSet& s, const uint8_t* st, const uint8_t* 
     }
     a.n_jobs = nj;
     if (train) { a.K = h->cfg.n_heads; a.count = h->count; a.bcinv = h->bcinv; a.b1 = h->ad.b1; a.b2 = h->ad.b2; }
-    if (train && h->rp) {
-        a.frames = h->rp->frames; a.rows = h->rp->rows; a.n_frames = h->rp->n_frames; a.frame_bytes = h->rp->frame_bytes;
+    if (train && ring) {
+        a.frames = (const uint8_t*)ring->frames; a.rows = ring->rows; a.n_frames = ring->n_frames; a.frame_bytes = ring->frame_bytes;
         a.act_out = h->rp_action; a.rew_out = h->rp_reward; a.term_out = h->rp_terminal;
-        return convp_launch_stage(a, a.n_prep_blocks + (int)blocks, q, h->rp->slots_dev ? nullptr : &h->rp->slots, h->rp->slots_dev);
+        if (ring->slots_dev) return convp_launch_stage(a, a.n_prep_blocks + (int)blocks, q, nullptr, ring->slots_dev);
+        const StageSlots slots = ring->slot_block<StageSlots>();
+        return convp_launch_stage(a, a.n_prep_blocks + (int)blocks, q, &slots, nullptr);
     }
     if (debug_on("IDQN_STAGE_SKIP_PIXELS")) a.n_prep_blocks = 0;  // timing probe: the launch without its pixel half (wrong results)
     return convp_launch_stage(a, a.n_prep_blocks + (int)blocks, q);
@@ -1886,12 +1926,14 @@ int planes_pair(idqn_handle_s* h, int layer, int nb, hipStream_t q, bool* done) 
 }
 
 // ---- forward of a net set: staging, 3 convs, Dense_0 partials -----------------------------------
-int cnn_forward(idqn_handle_s* h, NetSet& s, const uint8_t* st, const uint8_t* st2, int B, hipStream_t q, bool with_dense0 = true) {
+// (`ring`: planes_stage)
+int cnn_forward(idqn_handle_s* h, NetSet& s, const uint8_t* st, const uint8_t* st2, int B, hipStream_t q, bool with_dense0 = true,
+                const StepIn* ring = nullptr) {
     const int nb = cdiv(B, 32);
     IDQN_REQUIRE(nb <= s.nb_cap, "batch %d exceeds the workspace (%d blocks of 32)", B, s.nb_cap);
     if (h->planes) {
         static const char* nm[3] = {"conv0 fwd", "conv1 fwd", "conv2 fwd"};
-        int rc = planes_stage(h, s, st, st2, B, nb, q);
+        int rc = planes_stage(h, s, st, st2, B, nb, q, ring);
         tl_mark(h, q, "stage (pixels + kernel packing)");
         for (int i = 0; i < 3 && !rc; ++i) { rc = planes_conv(h, s, i, nb, q); tl_mark(h, q, nm[i]); }
         if (rc) return rc;
@@ -2167,9 +2209,9 @@ int launch_dense0_wgrad(idqn_handle_s* h, const float* a3, const float* dh, int 
     return IDQN_OK;
 }
 
-int cnn_backward(idqn_handle_s* h, const int32_t* action, const float* reward, const uint8_t* terminal, int B,
-                 int Bdiv, bool fuse_adam, bool profile, bool stop_after_dense0, bool stop_before_dense0_wgrad,
-                 hipStream_t q) {
+int cnn_backward(idqn_handle_s* h, const StepIn& in, hipStream_t q) {
+    const int B = in.batch, Bdiv = in.mean_divisor;
+    const bool fuse_adam = !in.grads_only(), profile = in.profile(), stop_after_dense0 = in.stop0(), stop_before_dense0_wgrad = in.stopb();
     const int K = h->cfg.n_heads, nb = cdiv(B, 32);
     NetSet& s = h->train;
     const ConvL *c0 = &h->conv[0], *c1 = &h->conv[1], *c2 = &h->conv[2];
@@ -2186,12 +2228,12 @@ int cnn_backward(idqn_handle_s* h, const int32_t* action, const float* reward, c
         const long w0n = h->g_w0_end - h->g_w0_begin;
         ta.gP = h->gP; ta.g_b0_off = h->off_b0 - w0n; ta.g_w1_off = h->off_w1 - w0n; ta.g_b1_off = h->off_b1 - w0n;
     } ta.nb = nb; ta.J = h->J; ta.A = h->cfg.n_actions;
-    ta.B = B; ta.Bdiv = Bdiv; ta.action = action; ta.reward = reward; ta.terminal = terminal; ta.gamma_n = h->gamma_n;
+    ta.B = B; ta.Bdiv = Bdiv; ta.action = in.action; ta.reward = in.reward; ta.terminal = in.terminal; ta.gamma_n = h->gamma_n;
     ta.prof = (h->cprof && h->cprof_role == 9) ? (long long*)h->cprof : nullptr;
     ta.dh = dh_of(h, nb); ta.q_dbg = h->qdbg; ta.grad = h->grad; ta.losses = h->losses;
     ta.count = h->count; ta.bcinv = h->bcinv; ta.b1 = h->ad.b1; ta.b2 = h->ad.b2;
     ta.cum = h->cum; ta.finish_step = fuse_adam ? 1 : 0;
-    ta.is_weight = h->is_weight; ta.td_abs = h->td_abs; ta.bpart = nullptr; ta.bctr = nullptr;
+    ta.is_weight = in.is_weight; ta.td_abs = in.td_abs; ta.bpart = nullptr; ta.bctr = nullptr;
     ta.bcinv_done = h->planes ? 1 : 0;  // (the plane path's staging launch writes the bias corrections)
     h->wt_ready = false;
     if (!h->planes) {  // (the plane path packs the data-gradient kernels in its staging launch)
@@ -2477,11 +2519,7 @@ extern "C" int idqn_destroy(idqn_handle_t h) {
     if (h->act_mail) (void)hipHostFree(h->act_mail);
     if (h->many.mail) (void)hipHostFree(h->many.mail);
     if (h->many.pin) (void)hipHostFree(h->many.pin);
-    for (int i = 0; i < IDQN_STEPS_STAGING_DEPTH; ++i) {
-        if (h->steps_pin[i]) (void)hipHostFree(h->steps_pin[i]);
-        if (h->steps_dev[i]) (void)hipFree(h->steps_dev[i]);
-        if (h->steps_ev[i]) (void)hipEventDestroy(h->steps_ev[i]);
-    }
+    h->steps.release();
     if (h->fact_planes) (void)hipFree(h->fact_planes);
     for (int32_t* p : h->iqn.bwd_items)
         if (p) (void)hipFree(p);
@@ -2510,121 +2548,99 @@ static int capture_exec(idqn_handle_t h, Issue&& issue, hipGraphExec_t* exec) {
     return IDQN_OK;
 }
 
-extern "C" int idqn_learn_on_batch(idqn_handle_t h, const void* state_dev, const void* next_state_dev,
-                                   const int32_t* action_dev, const float* reward_dev, const uint8_t* terminal_dev,
-                                   int32_t batch, int32_t batch_mean_divisor, uint32_t flags, void* stream) {
-    IDQN_REQUIRE(h && state_dev && next_state_dev && action_dev && reward_dev && terminal_dev, "idqn_learn_on_batch: null pointer");
-    IDQN_REQUIRE(batch >= 1 && batch <= h->cfg.max_batch, "idqn_learn_on_batch: batch %d not in [1, %d]", batch, h->cfg.max_batch);
-    IDQN_REQUIRE(batch_mean_divisor >= batch, "idqn_learn_on_batch: mean divisor %d < batch %d", batch_mean_divisor, batch);
-    hipStream_t q = (hipStream_t)stream;
-    const bool stop0 = flags & IDQN_F_STOP_AFTER_DENSE0, stopb = flags & IDQN_F_STOP_BEFORE_DENSE0_WGRAD;
-    const bool grads_only = (flags & IDQN_F_GRADS_ONLY) || stop0 || stopb, profile = flags & IDQN_F_PROFILE;
-    IDQN_REQUIRE(!(stop0 || stopb) || h->cfg.arch == IDQN_ARCH_CNN, "the IDQN_F_STOP_* flags belong to the cnn path");
-    h->pend_B = 0; h->pend_stage = 0;
-    if (const int rc = tl_begin(h, flags, q)) return rc;
-    int rc;
-    if (h->imp.on) {
-        if ((rc = impala_learn(h, (const uint8_t*)state_dev, (const uint8_t*)next_state_dev, action_dev, reward_dev, terminal_dev, batch,
-                               batch_mean_divisor, grads_only, profile, q)))
-            return rc;
-        if (!grads_only && (rc = launch_adam(h, 0, h->L.head_stride, 0, 0, false, q))) return rc;
-        return IDQN_OK;
-    }
-    if (h->gc.on) {
-        IDQN_REQUIRE(!(stop0 || stopb), "the IDQN_F_STOP_* flags belong to the MFMA cnn path");
-        if ((rc = gcnn_learn(h, (const uint8_t*)state_dev, (const uint8_t*)next_state_dev, action_dev, reward_dev, terminal_dev, batch,
-                             batch_mean_divisor, grads_only, profile, q)))
-            return rc;
-        if (!grads_only && (rc = launch_adam(h, 0, h->L.head_stride, 0, 0, false, q))) return rc;
-        return IDQN_OK;
-    }
-    if (h->cfg.arch == IDQN_ARCH_CNN) {
-        auto issue = [&](hipStream_t qs) -> int {
-            int r;
-            if ((r = cnn_forward(h, h->train, (const uint8_t*)state_dev, (const uint8_t*)next_state_dev, batch, qs))) return r;
-            if ((r = cnn_backward(h, action_dev, reward_dev, terminal_dev, batch, batch_mean_divisor, !grads_only, profile, stop0, stopb, qs)))
-                return r;
-            if (!grads_only) {
-                // every leaf except Dense_0/kernel (already updated by the fused weight-gradient kernel)
-                const long w0_b = h->off_w0, w0_e = h->off_b0;
-                if ((r = launch_adam(h, 0, h->L.head_stride, w0_b, w0_e, true, qs))) return r;
-            }
-            return IDQN_OK;
-        };
-        // A whole plain step is 13 launches whose arguments are pointers and sizes only: for a given set of batch buffers it
-        // can be replayed as ONE hipGraph (opt-in).  The first call of a key runs eagerly (it builds the launch plans, which
-        // allocate), the second is captured on the handle's private stream, every call from then on is one graph launch.
-        static const bool step_graph = getenv("IDQN_STEP_GRAPH") && atoi(getenv("IDQN_STEP_GRAPH")) != 0;
-        if (step_graph && flags == 0 && !h->rp) {  // (a replay-sourced step carries its slots as kernel arguments: not replayable)
-            auto key = std::make_tuple(state_dev, next_state_dev, (const void*)action_dev, (const void*)reward_dev,
-                                       (const void*)terminal_dev, (int)batch, (int)batch_mean_divisor,
-                                       (const void*)h->is_weight, (const void*)h->td_abs);
-            // bounded: a caller that hands over allocator-recycled buffers would otherwise instantiate a graph per pointer
-            // tuple that ever recurs; past 32 keys everything is dropped and the cache starts again
-            if (h->step_graphs.size() >= 32 && !h->step_graphs.count(key)) {
-                // the last replay may still be running on the caller's stream: an executable graph is only destroyed idle
-                IDQN_HIP_CHECK(hipStreamSynchronize(q));
-                for (auto& g : h->step_graphs)
-                    if (g.second.second) (void)hipGraphExecDestroy(g.second.second);
-                h->step_graphs.clear();
-            }
-            auto& ent = h->step_graphs[key];
-            if (ent.first++ == 0) return issue(q);
-            if (!ent.second && (rc = capture_exec(h, issue, &ent.second))) {  // nothing of a failed capture is kept
+// The step of the MFMA cnn path (plane conv by default): forward, backward with the fused Dense_0 update, Adam on every other leaf
+static int cnn_learn(idqn_handle_t h, const StepIn& in, hipStream_t q) {
+    auto issue = [&](hipStream_t qs) -> int {
+        int r;
+        if ((r = cnn_forward(h, h->train, (const uint8_t*)in.state, (const uint8_t*)in.next_state, in.batch, qs, true, in.frames ? &in : nullptr)))
+            return r;
+        if ((r = cnn_backward(h, in, qs))) return r;
+        if (!in.grads_only()) {
+            // every leaf except Dense_0/kernel (already updated by the fused weight-gradient kernel)
+            const long w0_b = h->off_w0, w0_e = h->off_b0;
+            if ((r = launch_adam(h, 0, h->L.head_stride, w0_b, w0_e, true, qs))) return r;
+        }
+        return IDQN_OK;  // count += 1 and cum_losses += losses already happened in k_td_dh
+    };
+    // A whole plain step is 13 launches whose arguments are pointers and sizes only: for a given set of batch buffers it
+    // can be replayed as ONE hipGraph (opt-in).  The first call of a key runs eagerly (it builds the launch plans, which
+    // allocate), the second is captured on the handle's private stream, every call from then on is one graph launch.
+    static const bool step_graph = getenv("IDQN_STEP_GRAPH") && atoi(getenv("IDQN_STEP_GRAPH")) != 0;
+    if (step_graph && in.flags == 0 && !in.frames) {  // (a replay-sourced step carries its slots as kernel arguments: not replayable)
+        auto key = std::make_tuple(in.state, in.next_state, (const void*)in.action, (const void*)in.reward, (const void*)in.terminal,
+                                   in.batch, in.mean_divisor, (const void*)in.is_weight, (const void*)in.td_abs);
+        // bounded: a caller that hands over allocator-recycled buffers would otherwise instantiate a graph per pointer
+        // tuple that ever recurs; past 32 keys everything is dropped and the cache starts again
+        if (h->step_graphs.size() >= 32 && !h->step_graphs.count(key)) {
+            // the last replay may still be running on the caller's stream: an executable graph is only destroyed idle
+            IDQN_HIP_CHECK(hipStreamSynchronize(q));
+            for (auto& g : h->step_graphs)
+                if (g.second.second) (void)hipGraphExecDestroy(g.second.second);
+            h->step_graphs.clear();
+        }
+        auto& ent = h->step_graphs[key];
+        if (ent.first++ == 0) return issue(q);
+        if (!ent.second) {
+            if (const int rc = capture_exec(h, issue, &ent.second)) {  // nothing of a failed capture is kept
                 h->step_graphs.erase(key);
                 return rc;
             }
-            IDQN_HIP_CHECK(hipGraphLaunch(ent.second, q));
-            return IDQN_OK;
         }
-        if ((rc = issue(q))) return rc;
-    } else {
-        FcArgs a = fc_args(h, batch, batch_mean_divisor, grads_only);
-        a.s = (const float*)state_dev; a.s2 = (const float*)next_state_dev; a.action = action_dev; a.reward = reward_dev;
-        a.terminal = terminal_dev;
-        a.is_weight = h->is_weight; a.td_abs = h->td_abs;
-        if (profile && h->ev_used + 2 <= (int)h->ev.size()) IDQN_HIP_CHECK(hipEventRecord(h->ev[h->ev_used], q));
-        const FcPlan& fp = h->fc_plan_;
-        const size_t lds = (size_t)fp.floats * 4;
-        const FcMfmaPlan& fm = h->fcm_plan_;
-        const bool par = h->fcp_plan_.floats && batch <= 32;  // one launch: forwards side by side, Adam in the gradient epilogues
-        // h->dominant names the kernel this call launches, template variant included (idqn_profile_read reports it)
-        if (par && h->rpf) {  // the minibatch comes from the replay frame ring (idqn_learn_on_replay_fc): the same single launch
-            h->dominant = "k_fc_step_par<ring>";
-            const idqn_handle_s::FcReplaySrc& r = *h->rpf;
-            if (r.slots_dev) fc_step_par_launch(h, q, a, grads_only, fc_ring_src(r.frames, r.rows, r.n_frames, r.frame_bytes, r.stack, RpsSlotsDev{r.slots_dev}));
-            else fc_step_par_launch(h, q, a, grads_only, fc_ring_src(r.frames, r.rows, r.n_frames, r.frame_bytes, r.stack, r.slots));
-        } else if (par) {
-            h->dominant = "k_fc_step_par";
-            fc_step_par_launch(h, q, a, grads_only, FcBatchSrc{});
-        } else if (fm.floats && h->fcm_global_) {
-            h->dominant = "k_fc_step_mfma<global>";
-            hipLaunchKernelGGL(k_fc_step_mfma<true>, dim3(h->cfg.n_heads), dim3(FCM_T), (size_t)fm.floats * 4, q, a, fm.ldw, fm.drows, fm.w_floats);
-        } else if (fm.floats) {
-            h->dominant = "k_fc_step_mfma<lds>";
-            hipLaunchKernelGGL(k_fc_step_mfma<false>, dim3(h->cfg.n_heads), dim3(FCM_T), (size_t)fm.floats * 4, q, a, fm.ldw, fm.drows, fm.w_floats);
-        } else if (fp.BS == 32) {
-            h->dominant = "k_fc_step_lds<32>";
-            hipLaunchKernelGGL(k_fc_step_lds<32>, dim3(h->cfg.n_heads), dim3(FC_T), lds, q, a, fp.tw, fp.wfl);
-        } else if (fp.BS == 16) {
-            h->dominant = "k_fc_step_lds<16>";
-            hipLaunchKernelGGL(k_fc_step_lds<16>, dim3(h->cfg.n_heads), dim3(FC_T), lds, q, a, fp.tw, fp.wfl);
-        } else if (fp.BS == 8) {
-            h->dominant = "k_fc_step_lds<8>";
-            hipLaunchKernelGGL(k_fc_step_lds<8>, dim3(h->cfg.n_heads), dim3(FC_T), lds, q, a, fp.tw, fp.wfl);
-        } else {
-            h->dominant = "k_fc_step";
-            hipLaunchKernelGGL(k_fc_step, dim3(h->cfg.n_heads), dim3(256), 0, q, a);
-        }
-        if (profile && h->ev_used + 2 <= (int)h->ev.size()) {
-            IDQN_HIP_CHECK(hipEventRecord(h->ev[h->ev_used + 1], q));
-            h->ev_used += 2;
-        }
-        tl_mark(h, q, h->dominant);
-        IDQN_HIP_CHECK(hipGetLastError());
-        if (!grads_only && !par && (rc = launch_adam(h, 0, h->L.head_stride, 0, 0, false, q))) return rc;
+        IDQN_HIP_CHECK(hipGraphLaunch(ent.second, q));
+        return IDQN_OK;
     }
-    return IDQN_OK;  // count += 1 and cum_losses += losses already happened in k_td_dh / k_fc_step (fused path)
+    return issue(q);
+}
+
+// The MLP step: ONE launch of the first kernel of the ladder that serves the net and the batch (+ Adam where the kernel has
+// none of its own).  h->dominant names that kernel, template variant included (idqn_profile_read reports it).
+static int fc_learn(idqn_handle_t h, const StepIn& in, hipStream_t q) {
+    const bool grads_only = in.grads_only(), profile = in.profile();
+    FcArgs a = fc_args(h, in.batch, in.mean_divisor, grads_only);
+    a.s = (const float*)in.state; a.s2 = (const float*)in.next_state; a.action = in.action; a.reward = in.reward;
+    a.terminal = in.terminal;
+    a.is_weight = in.is_weight; a.td_abs = in.td_abs;
+    if (profile && h->ev_used + 2 <= (int)h->ev.size()) IDQN_HIP_CHECK(hipEventRecord(h->ev[h->ev_used], q));
+    const FcPlan& fp = h->fc_plan_;
+    const size_t lds = (size_t)fp.floats * 4;
+    const FcMfmaPlan& fm = h->fcm_plan_;
+    const bool par = h->fcp_plan_.floats && in.batch <= 32;  // one launch: forwards side by side, Adam in the gradient epilogues
+    if (par && in.frames) {  // the minibatch comes from the replay frame ring (learn_on_replay_fc): the same single launch
+        h->dominant = "k_fc_step_par<ring>";
+        if (in.slots_dev)
+            fc_step_par_launch(h, q, a, grads_only, fc_ring_src(in.frames, in.rows, in.n_frames, in.frame_bytes, in.stack, RpsSlotsDev{in.slots_dev}));
+        else
+            fc_step_par_launch(h, q, a, grads_only, fc_ring_src(in.frames, in.rows, in.n_frames, in.frame_bytes, in.stack, in.slot_block<RpsSlotsPar>()));
+    } else if (par) {
+        h->dominant = "k_fc_step_par";
+        fc_step_par_launch(h, q, a, grads_only, FcBatchSrc{});
+    } else if (fm.floats && h->fcm_global_) {
+        h->dominant = "k_fc_step_mfma<global>";
+        hipLaunchKernelGGL(k_fc_step_mfma<true>, dim3(h->cfg.n_heads), dim3(FCM_T), (size_t)fm.floats * 4, q, a, fm.ldw, fm.drows, fm.w_floats);
+    } else if (fm.floats) {
+        h->dominant = "k_fc_step_mfma<lds>";
+        hipLaunchKernelGGL(k_fc_step_mfma<false>, dim3(h->cfg.n_heads), dim3(FCM_T), (size_t)fm.floats * 4, q, a, fm.ldw, fm.drows, fm.w_floats);
+    } else if (fp.BS == 32) {
+        h->dominant = "k_fc_step_lds<32>";
+        hipLaunchKernelGGL(k_fc_step_lds<32>, dim3(h->cfg.n_heads), dim3(FC_T), lds, q, a, fp.tw, fp.wfl);
+    } else if (fp.BS == 16) {
+        h->dominant = "k_fc_step_lds<16>";
+        hipLaunchKernelGGL(k_fc_step_lds<16>, dim3(h->cfg.n_heads), dim3(FC_T), lds, q, a, fp.tw, fp.wfl);
+    } else if (fp.BS == 8) {
+        h->dominant = "k_fc_step_lds<8>";
+        hipLaunchKernelGGL(k_fc_step_lds<8>, dim3(h->cfg.n_heads), dim3(FC_T), lds, q, a, fp.tw, fp.wfl);
+    } else {
+        h->dominant = "k_fc_step";
+        hipLaunchKernelGGL(k_fc_step, dim3(h->cfg.n_heads), dim3(256), 0, q, a);
+    }
+    if (profile && h->ev_used + 2 <= (int)h->ev.size()) {
+        IDQN_HIP_CHECK(hipEventRecord(h->ev[h->ev_used + 1], q));
+        h->ev_used += 2;
+    }
+    tl_mark(h, q, h->dominant);
+    IDQN_HIP_CHECK(hipGetLastError());
+    if (!grads_only && !par) return launch_adam(h, 0, h->L.head_stride, 0, 0, false, q);
+    return IDQN_OK;  // count += 1 and cum_losses += losses already happened in the step kernel (fused path)
 }
 
 // ---- i-IQN heads (extension; iqn_kernels.h, oracle/iqn_ref.py) --------------------------------------------------------
@@ -2687,6 +2703,49 @@ int iqn_heads_forward(idqn_handle_s* h, const float* const* wbase_v, int V, int 
 }
 }  // namespace
 
+static int iqn_learn(idqn_handle_t h, const StepIn& in, hipStream_t q);  // (below, with its public entry)
+
+// ONE gradient step on handle h: what every step does once, then the step of the handle's path (a quantile step, in.tau set,
+// is iqn_learn on its cnn handle).  Every learner entry ends here, its arguments checked under its own name.
+static int learn_step(idqn_handle_t h, const StepIn& in, hipStream_t q) {
+    h->pend_B = 0; h->pend_stage = 0;
+    int rc;
+    if ((rc = tl_begin(h, in.flags, q))) return rc;
+    if (in.tau) return iqn_learn(h, in, q);
+    if (h->imp.on) {
+        rc = impala_learn(h, in, q);
+    } else if (h->gc.on) {
+        IDQN_REQUIRE(!(in.stop0() || in.stopb()), "the IDQN_F_STOP_* flags belong to the MFMA cnn path");
+        rc = gcnn_learn(h, in, q);
+    } else {
+        return h->cfg.arch == IDQN_ARCH_CNN ? cnn_learn(h, in, q) : fc_learn(h, in, q);
+    }
+    if (rc || in.grads_only()) return rc;
+    return launch_adam(h, 0, h->L.head_stride, 0, 0, false, q);
+}
+
+// The five device tensors of a batch entry, and the prioritized-replay buffers the caller set on the handle
+static StepIn batch_step(idqn_handle_t h, const char* fn, const void* state_dev, const void* next_state_dev, const int32_t* action_dev,
+                         const float* reward_dev, const uint8_t* terminal_dev, int32_t batch, int32_t mean_divisor, uint32_t flags) {
+    StepIn in;
+    in.fn = fn; in.batch = batch; in.mean_divisor = mean_divisor; in.flags = flags;
+    in.state = state_dev; in.next_state = next_state_dev; in.action = action_dev; in.reward = reward_dev; in.terminal = terminal_dev;
+    in.is_weight = h->is_weight; in.td_abs = h->td_abs;
+    return in;
+}
+
+extern "C" int idqn_learn_on_batch(idqn_handle_t h, const void* state_dev, const void* next_state_dev,
+                                   const int32_t* action_dev, const float* reward_dev, const uint8_t* terminal_dev,
+                                   int32_t batch, int32_t batch_mean_divisor, uint32_t flags, void* stream) {
+    IDQN_REQUIRE(h && state_dev && next_state_dev && action_dev && reward_dev && terminal_dev, "idqn_learn_on_batch: null pointer");
+    IDQN_REQUIRE(batch >= 1 && batch <= h->cfg.max_batch, "idqn_learn_on_batch: batch %d not in [1, %d]", batch, h->cfg.max_batch);
+    IDQN_REQUIRE(batch_mean_divisor >= batch, "idqn_learn_on_batch: mean divisor %d < batch %d", batch_mean_divisor, batch);
+    IDQN_REQUIRE(!(flags & (IDQN_F_STOP_AFTER_DENSE0 | IDQN_F_STOP_BEFORE_DENSE0_WGRAD)) || h->cfg.arch == IDQN_ARCH_CNN,
+                 "the IDQN_F_STOP_* flags belong to the cnn path");
+    return learn_step(h, batch_step(h, "idqn_learn_on_batch", state_dev, next_state_dev, action_dev, reward_dev, terminal_dev, batch,
+                                    batch_mean_divisor, flags), (hipStream_t)stream);
+}
+
 // Everything learn_on_replay (below) refuses on its own account, before anything is enqueued or allocated (shared with
 // idqn_per_learn_on_replay).
 static int replay_check(idqn_handle_t h, const char* fn, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
@@ -2709,18 +2768,14 @@ static int replay_check(idqn_handle_t h, const char* fn, const uint8_t* frame_ri
 }
 
 // iDQN.update_online_params (idqn.py:65-72) on the HBM frame ring: replay_buffer.py:215-230's sample() fused into the step.
-// Exactly one of slots_host / slots_dev is set.
+// `in` names the ring (ring_step); exactly one of its slots_host / slots_dev is set.
 //
-// The replay source is read by ONE launch: the staging launch of cnn_forward (planes_stage), which writes the bf16 pixel planes
-// and the sampled rows' scalars into buffers the handle owns.  Everything after it -- the TD kernel, and on a split step
-// (IDQN_F_STOP_*) the rest that idqn_backward_rest / idqn_finish_step_factored enqueue later, Conv_0's weight gradient
-// included -- reads those handle-owned copies, never the ring, the rows or the slots.  So the source can stay a stack local
-// that is dropped on return, for split steps too: the later calls have nothing of it left to read.  (The stream order still
-// matters to the CALLER: the ring must not be overwritten before the staging launch has run.)
-static int learn_on_replay(idqn_handle_t h, const char* fn, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
-                           const int32_t* rows_dev, const int32_t* slots_host, const int32_t* slots_dev, int32_t batch, int32_t stack,
-                           const float* tau_dev, int32_t batch_mean_divisor, uint32_t flags, void* stream) {
-    if (const int rc = replay_check(h, fn, frame_ring_dev, n_frames, frame_bytes, rows_dev, slots_host, slots_dev, batch, stack, tau_dev, flags))
+// The ring is read by ONE launch (StepIn): the staging launch of cnn_forward (planes_stage), which writes the bf16 pixel planes
+// and the sampled rows' scalars into buffers the handle owns; the TD kernel and everything later read those.  (The stream order
+// still matters to the CALLER: the ring must not be overwritten before the staging launch has run.)
+static int learn_on_replay(idqn_handle_t h, StepIn in, void* stream) {
+    if (const int rc = replay_check(h, in.fn, (const uint8_t*)in.frames, in.n_frames, in.frame_bytes, in.rows, in.slots_host, in.slots_dev, in.batch,
+                                    in.stack, in.tau, in.flags))
         return rc;
     if (!h->rp_action) {
         const int mb = h->cfg.max_batch;
@@ -2730,35 +2785,40 @@ static int learn_on_replay(idqn_handle_t h, const char* fn, const uint8_t* frame
         IDQN_HIP_CHECK(hipStreamSynchronize(nullptr));  // (the zero-fill runs on the null stream)
         h->rp_action = (int32_t*)f; h->rp_reward = f + mb; h->rp_terminal = (uint8_t*)(f + 2L * mb);
     }
-    idqn_handle_s::ReplaySrc src;
-    src.frames = frame_ring_dev; src.rows = rows_dev; src.n_frames = n_frames; src.frame_bytes = frame_bytes;
-    src.slots_dev = slots_dev;
-    memset(&src.slots, 0, sizeof(src.slots));
-    if (!slots_dev) memcpy(src.slots.slot, slots_host, (size_t)batch * 4);
-    h->rp = &src;
-    // (the state pointers only select the staging path; the replay source replaces them)
-    const int rc = tau_dev ? idqn_iqn_learn_on_batch(h, frame_ring_dev, frame_ring_dev, h->rp_action, h->rp_reward, h->rp_terminal, tau_dev,
-                                                     batch, flags, stream)
-                           : idqn_learn_on_batch(h, frame_ring_dev, frame_ring_dev, h->rp_action, h->rp_reward, h->rp_terminal, batch,
-                                                 batch_mean_divisor, flags, stream);
-    h->rp = nullptr;  // (see above: nothing enqueued later reads the source)
-    return rc;
+    // (reported under the batch entry's name, and behind the first call's allocation, since the step first ran through that entry)
+    IDQN_REQUIRE(in.tau || in.mean_divisor >= in.batch, "idqn_learn_on_batch: mean divisor %d < batch %d", in.mean_divisor, in.batch);
+    // (the state pointers are what the staging launch is told beside the ring; it gathers from the ring)
+    in.state = in.next_state = in.frames;
+    in.action = h->rp_action; in.reward = h->rp_reward; in.terminal = h->rp_terminal;
+    return learn_step(h, in, (hipStream_t)stream);
+}
+
+// The frame ring of a replay entry as a step's input.  `per`: the handle of a public entry, whose prioritized-replay buffers
+// (idqn_set_per_buffers) the step takes; nullptr where the caller names the step's weights / |TD| itself, or has refused them
+static StepIn ring_step(idqn_handle_t per, const char* fn, const void* frame_ring_dev, int64_t n_frames, int64_t frame_bytes, const int32_t* rows_dev,
+                        const int32_t* slots_host, const int32_t* slots_dev, int32_t batch, int32_t stack, int32_t mean_divisor, uint32_t flags) {
+    StepIn in;
+    in.fn = fn; in.batch = batch; in.mean_divisor = mean_divisor; in.flags = flags;
+    in.frames = frame_ring_dev; in.rows = rows_dev; in.n_frames = n_frames; in.frame_bytes = frame_bytes; in.stack = stack;
+    in.slots_host = slots_dev ? nullptr : slots_host; in.slots_dev = slots_dev;
+    if (per) { in.is_weight = per->is_weight; in.td_abs = per->td_abs; }
+    return in;
 }
 
 extern "C" int idqn_learn_on_replay(idqn_handle_t h, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
                                     const int32_t* rows_dev, const int32_t* slots_host, int32_t batch, int32_t stack,
                                     int32_t batch_mean_divisor, uint32_t flags, void* stream) {
     IDQN_REQUIRE(slots_host, "idqn_learn_on_replay: null pointer");
-    return learn_on_replay(h, "idqn_learn_on_replay", frame_ring_dev, n_frames, frame_bytes, rows_dev, slots_host, nullptr, batch, stack,
-                           nullptr, batch_mean_divisor, flags, stream);
+    return learn_on_replay(h, ring_step(h, "idqn_learn_on_replay", frame_ring_dev, n_frames, frame_bytes, rows_dev, slots_host, nullptr, batch, stack,
+                                        batch_mean_divisor, flags), stream);
 }
 
 extern "C" int idqn_learn_on_replay_dev(idqn_handle_t h, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
                                         const int32_t* rows_dev, const int32_t* slots_dev, int32_t batch, int32_t stack,
                                         int32_t batch_mean_divisor, uint32_t flags, void* stream) {
     IDQN_REQUIRE(slots_dev, "idqn_learn_on_replay_dev: null pointer");
-    return learn_on_replay(h, "idqn_learn_on_replay_dev", frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, slots_dev, batch,
-                           stack, nullptr, batch_mean_divisor, flags, stream);
+    return learn_on_replay(h, ring_step(h, "idqn_learn_on_replay_dev", frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, slots_dev, batch,
+                                        stack, batch_mean_divisor, flags), stream);
 }
 
 // Everything learn_on_replay_fc refuses, before anything is enqueued or allocated (shared with idqn_learn_steps_on_replay_fc).
@@ -2797,14 +2857,14 @@ static int replay_fc_check(idqn_handle_t h, const char* fn, const uint8_t* frame
 //     staging launch as well (the A/B of tools/bench_fc_learn_on_replay.py).
 //   * everything else: ONE staging launch (k_rps_stage; per RPS_ARG_SLOTS samples when the slots travel as kernel arguments)
 //     writes the stacked minibatches and the rows' scalars into buffers the handle owns and the plain step runs on those.
-// Either way only that first launch reads the ring, the rows and the slots: the source is a stack local dropped on return.
+// Either way only that first launch reads the ring, the rows and the slots (StepIn).
 // Every refusal comes before anything is enqueued.
-static int learn_on_replay_fc(idqn_handle_t h, const char* fn, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
-                              const int32_t* rows_dev, const int32_t* slots_host, const int32_t* slots_dev, int32_t batch, int32_t stack,
-                              int32_t batch_mean_divisor, uint32_t flags, void* stream) {
+static int learn_on_replay_fc(idqn_handle_t h, StepIn in, void* stream) {
+    const int32_t *slots_host = in.slots_host, *slots_dev = in.slots_dev;
+    const int batch = in.batch;
     long obs_elems;
-    if (const int rc = replay_fc_check(h, fn, frame_ring_dev, n_frames, frame_bytes, rows_dev, slots_host, slots_dev, batch, stack, batch_mean_divisor,
-                                       flags, &obs_elems))
+    if (const int rc = replay_fc_check(h, in.fn, (const uint8_t*)in.frames, in.n_frames, in.frame_bytes, in.rows, slots_host, slots_dev, batch, in.stack,
+                                       in.mean_divisor, in.flags, &obs_elems))
         return rc;
     const bool fc = h->cfg.arch == IDQN_ARCH_FC;
     if (!h->rp_state) {
@@ -2818,23 +2878,12 @@ static int learn_on_replay_fc(idqn_handle_t h, const char* fn, const uint8_t* fr
         h->rp_action = (int32_t*)f; h->rp_reward = f + mb; h->rp_terminal = (uint8_t*)(f + 2L * mb);
         h->rp_state = s; h->rp_next = s2;
     }
-    static const bool always_stage = getenv("IDQN_FC_REPLAY_STAGE") && atoi(getenv("IDQN_FC_REPLAY_STAGE")) != 0;
-    if (fc && h->fcp_plan_.floats && batch <= RPS_PAR_SLOTS && !always_stage) {
-        idqn_handle_s::FcReplaySrc src;
-        src.frames = frame_ring_dev; src.rows = rows_dev; src.n_frames = n_frames; src.frame_bytes = frame_bytes;
-        src.stack = stack; src.slots_dev = slots_dev;
-        memset(&src.slots, 0, sizeof(src.slots));
-        if (!slots_dev) memcpy(src.slots.slot, slots_host, (size_t)batch * 4);
-        h->rpf = &src;
-        // (the batch pointers only pass the null checks: k_fc_step_par reads the ring and the rows instead)
-        const int rc = idqn_learn_on_batch(h, h->rp_state, h->rp_next, h->rp_action, h->rp_reward, h->rp_terminal, batch, batch_mean_divisor,
-                                           flags, stream);
-        h->rpf = nullptr;
-        return rc;
-    }
+    // the step's kernel is told the handle-owned minibatch either way (k_fc_step_par reads the ring and the rows instead)
+    in.state = h->rp_state; in.next_state = h->rp_next; in.action = h->rp_action; in.reward = h->rp_reward; in.terminal = h->rp_terminal;
+    if (fc && h->fcp_plan_.floats && batch <= RPS_PAR_SLOTS && !fc_replay_always_stage()) return learn_step(h, in, (hipStream_t)stream);
     RpsStageArgs a;
-    a.frames = frame_ring_dev; a.rows = rows_dev; a.n_frames = n_frames; a.frame_elems = fc ? frame_bytes / 4 : frame_bytes;
-    a.stack = stack; a.B = batch; a.first = 0;
+    a.frames = (const uint8_t*)in.frames; a.rows = in.rows; a.n_frames = in.n_frames; a.frame_elems = fc ? in.frame_bytes / 4 : in.frame_bytes;
+    a.stack = in.stack; a.B = batch; a.first = 0;
     a.s_out = h->rp_state; a.n_out = h->rp_next; a.a_out = h->rp_action; a.r_out = h->rp_reward; a.t_out = h->rp_terminal;
     hipStream_t q = (hipStream_t)stream;
     const long bytes = obs_elems * (fc ? 4 : 1);
@@ -2856,53 +2905,38 @@ static int learn_on_replay_fc(idqn_handle_t h, const char* fn, const uint8_t* fr
         }
     }
     IDQN_HIP_CHECK(hipGetLastError());
-    return idqn_learn_on_batch(h, h->rp_state, h->rp_next, h->rp_action, h->rp_reward, h->rp_terminal, batch, batch_mean_divisor, flags, stream);
+    in.frames = nullptr;  // staged: the step runs on the handle-owned minibatch
+    return learn_step(h, in, q);
 }
 
 extern "C" int idqn_learn_on_replay_fc(idqn_handle_t h, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
                                        const int32_t* rows_dev, const int32_t* slots_host, int32_t batch, int32_t stack,
                                        int32_t batch_mean_divisor, uint32_t flags, void* stream) {
     IDQN_REQUIRE(slots_host, "idqn_learn_on_replay_fc: null pointer");
-    return learn_on_replay_fc(h, "idqn_learn_on_replay_fc", frame_ring_dev, n_frames, frame_bytes, rows_dev, slots_host, nullptr, batch, stack,
-                              batch_mean_divisor, flags, stream);
+    return learn_on_replay_fc(h, ring_step(h, "idqn_learn_on_replay_fc", frame_ring_dev, n_frames, frame_bytes, rows_dev, slots_host, nullptr, batch,
+                                           stack, batch_mean_divisor, flags), stream);
 }
 
 extern "C" int idqn_learn_on_replay_fc_dev(idqn_handle_t h, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
                                            const int32_t* rows_dev, const int32_t* slots_dev, int32_t batch, int32_t stack,
                                            int32_t batch_mean_divisor, uint32_t flags, void* stream) {
     IDQN_REQUIRE(slots_dev, "idqn_learn_on_replay_fc_dev: null pointer");
-    return learn_on_replay_fc(h, "idqn_learn_on_replay_fc_dev", frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, slots_dev, batch,
-                              stack, batch_mean_divisor, flags, stream);
+    return learn_on_replay_fc(h, ring_step(h, "idqn_learn_on_replay_fc_dev", frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, slots_dev,
+                                           batch, stack, batch_mean_divisor, flags), stream);
 }
 
 // The handle's host-argument staging ring (idqn_learn_steps_on_replay_fc's slots, the uniforms of idqn_per_learn_on_replay and
 // idqn_per_learn_steps_on_replay): `bytes`
 // <= STEPS_BLOCK_BYTES of ordinary host memory are copied into the next pinned block and their upload into the block's device
-// twin, h->steps_dev[*blk], is enqueued on q.  A block is rewritten only after the event steps_stage_guard recorded behind the
-// launch that read it has passed, so back-to-back calls need no synchronisation.
+// twin, h->steps.dev(), is enqueued on q.  The caller records h->steps.guard(q) behind the last launch that reads the twin.
 // A block holds the largest of them: idqn_per_learn_steps_on_replay's IDQN_MAX_STEPS_PER_CALL x PER_STEP_MAX_N float64 uniforms.
 static constexpr size_t STEPS_SLOTS_BYTES = (size_t)IDQN_MAX_STEPS_PER_CALL * RPS_PAR_SLOTS * 4;  // the slots of one idqn_learn_steps_on_replay_fc call
 static constexpr size_t STEPS_BLOCK_BYTES = (size_t)IDQN_MAX_STEPS_PER_CALL * PER_STEP_MAX_N * 8;
 static_assert(STEPS_BLOCK_BYTES >= STEPS_SLOTS_BYTES, "the slots fit a block too");
-static int steps_stage(idqn_handle_t h, const void* host, size_t bytes, hipStream_t q, int* blk_out) {
-    const int blk = h->steps_next;
-    if (!h->steps_pin[blk]) {
-        IDQN_HIP_CHECK(hipHostMalloc((void**)&h->steps_pin[blk], STEPS_BLOCK_BYTES, hipHostMallocDefault));
-        IDQN_HIP_CHECK(hipMalloc((void**)&h->steps_dev[blk], STEPS_BLOCK_BYTES));
-        IDQN_HIP_CHECK(hipEventCreateWithFlags(&h->steps_ev[blk], hipEventDisableTiming));
-    }
-    if (h->steps_busy[blk]) IDQN_HIP_CHECK(hipEventSynchronize(h->steps_ev[blk]));  // the launch that read this block is done
-    h->steps_busy[blk] = false;
-    memcpy(h->steps_pin[blk], host, bytes);
-    IDQN_HIP_CHECK(hipMemcpyAsync(h->steps_dev[blk], h->steps_pin[blk], bytes, hipMemcpyHostToDevice, q));
-    h->steps_next = (blk + 1) % IDQN_STEPS_STAGING_DEPTH;
-    *blk_out = blk;
-    return IDQN_OK;
-}
-static int steps_stage_guard(idqn_handle_t h, int blk, hipStream_t q) {  // behind the last launch that reads block blk
-    IDQN_HIP_CHECK(hipEventRecord(h->steps_ev[blk], q));
-    h->steps_busy[blk] = true;
-    return IDQN_OK;
+static int steps_stage(idqn_handle_t h, const void* host, size_t bytes, hipStream_t q) {
+    if (const int rc = h->steps.acquire(STEPS_BLOCK_BYTES)) return rc;
+    memcpy(h->steps.pin(), host, bytes);
+    return h->steps.upload(bytes, q);
 }
 
 // n_steps consecutive update_online_params on the frame ring as ONE C call (include/idqn_hip.h).  Exactly one of slots_host /
@@ -2927,24 +2961,22 @@ static int learn_steps_on_replay_fc(idqn_handle_t h, const char* fn, const uint8
     if (const int rc = replay_fc_check(h, fn, frame_ring_dev, n_frames, frame_bytes, rows_dev, slots_host, slots_dev, batch, stack, batch_mean_divisor,
                                        flags, &obs_elems))
         return rc;
-    static const bool always_stage = getenv("IDQN_FC_REPLAY_STAGE") && atoi(getenv("IDQN_FC_REPLAY_STAGE")) != 0;
-    const char* force_loop = getenv("IDQN_FC_LEARN_STEPS_LOOP");  // (read per call: the bench switches it between its legs)
-    const bool persistent = h->cfg.arch == IDQN_ARCH_FC && h->fcs_plan_.floats && batch <= RPS_PAR_SLOTS && !always_stage &&
-                            !(force_loop && atoi(force_loop) != 0);
+    const bool persistent = h->cfg.arch == IDQN_ARCH_FC && h->fcs_plan_.floats && batch <= RPS_PAR_SLOTS && !fc_replay_always_stage() &&
+                            !fc_steps_force_loop();
     if (!persistent) {
-        for (int i = 0; i < n_steps; ++i) {
+        for (int i = 0; i < n_steps; ++i) {  // (no weights, no |TD|: refused above)
             const long o = (long)i * batch;
-            if (const int rc = learn_on_replay_fc(h, fn, frame_ring_dev, n_frames, frame_bytes, rows_dev, slots_host ? slots_host + o : nullptr,
-                                                  slots_dev ? slots_dev + o : nullptr, batch, stack, batch_mean_divisor, 0, stream))
+            if (const int rc = learn_on_replay_fc(h, ring_step(nullptr, fn, frame_ring_dev, n_frames, frame_bytes, rows_dev, slots_host ? slots_host + o : nullptr,
+                                                               slots_dev ? slots_dev + o : nullptr, batch, stack, batch_mean_divisor, 0), stream))
                 return rc;
         }
         return IDQN_OK;
     }
     hipStream_t q = (hipStream_t)stream;
-    int blk = -1;
-    if (!slots_dev) {
-        if (const int rc = steps_stage(h, slots_host, (size_t)n_steps * batch * 4, q, &blk)) return rc;
-        slots_dev = h->steps_dev[blk];
+    const bool staged = !slots_dev;
+    if (staged) {
+        if (const int rc = steps_stage(h, slots_host, (size_t)n_steps * batch * 4, q)) return rc;
+        slots_dev = (const int32_t*)h->steps.dev();
     }
     h->pend_B = 0; h->pend_stage = 0;
     h->tl_on = false;
@@ -2954,8 +2986,7 @@ static int learn_steps_on_replay_fc(idqn_handle_t h, const char* fn, const uint8
                        h->online, h->mu, h->nu, (int)n_steps,
                        fc_ring_src(frame_ring_dev, rows_dev, n_frames, frame_bytes, stack, RpsSlotsDev{slots_dev}));
     IDQN_HIP_CHECK(hipGetLastError());
-    if (blk >= 0) return steps_stage_guard(h, blk, q);
-    return IDQN_OK;
+    return staged ? h->steps.guard(q) : IDQN_OK;
 }
 
 extern "C" int idqn_learn_steps_on_replay_fc(idqn_handle_t h, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
@@ -2980,16 +3011,18 @@ extern "C" int idqn_iqn_learn_on_replay(idqn_handle_t h, const uint8_t* frame_ri
                                         const int32_t* rows_dev, const int32_t* slots_host, const float* tau_dev, int32_t batch,
                                         int32_t stack, uint32_t flags, void* stream) {
     IDQN_REQUIRE(slots_host && tau_dev, "idqn_iqn_learn_on_replay: null pointer");
-    return learn_on_replay(h, "idqn_iqn_learn_on_replay", frame_ring_dev, n_frames, frame_bytes, rows_dev, slots_host, nullptr, batch,
-                           stack, tau_dev, batch, flags, stream);
+    StepIn in = ring_step(h, "idqn_iqn_learn_on_replay", frame_ring_dev, n_frames, frame_bytes, rows_dev, slots_host, nullptr, batch, stack, batch, flags);
+    in.tau = tau_dev;
+    return learn_on_replay(h, in, stream);
 }
 
 extern "C" int idqn_iqn_learn_on_replay_dev(idqn_handle_t h, const uint8_t* frame_ring_dev, int64_t n_frames, int64_t frame_bytes,
                                             const int32_t* rows_dev, const int32_t* slots_dev, const float* tau_dev, int32_t batch,
                                             int32_t stack, uint32_t flags, void* stream) {
     IDQN_REQUIRE(slots_dev && tau_dev, "idqn_iqn_learn_on_replay_dev: null pointer");
-    return learn_on_replay(h, "idqn_iqn_learn_on_replay_dev", frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, slots_dev, batch,
-                           stack, tau_dev, batch, flags, stream);
+    StepIn in = ring_step(h, "idqn_iqn_learn_on_replay_dev", frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, slots_dev, batch, stack, batch, flags);
+    in.tau = tau_dev;
+    return learn_on_replay(h, in, stream);
 }
 
 // n_steps consecutive prioritized learner steps on the frame ring, the driver of idqn_per_learn_on_replay (n_steps == 1) and
@@ -3027,36 +3060,31 @@ static int per_learn_on_replay(idqn_handle_t h, const char* fn, const P& per, co
             return rc;
     }
     hipStream_t q = (hipStream_t)stream;
-    int blk = -1, rc;
-    if ((rc = steps_stage(h, per.uniforms_host, (size_t)n_steps * batch * 8, q, &blk))) return rc;
-    const double* u = (const double*)h->steps_dev[blk];
+    int rc;
+    if ((rc = steps_stage(h, per.uniforms_host, (size_t)n_steps * batch * 8, q))) return rc;
+    const double* u = (const double*)h->steps.dev();
     if (marks && (rc = tl_begin(h, flags, q))) return rc;
     if ((rc = per_draw(per.nodes_dev, per.depth, u, batch, per.stratified, per.n_items, per.beta, per.leaves_dev, per.weights_dev, stream)))
         return rc;
     if (marks) tl_mark(h, q, "k_per_draw");
     // the last launch that reads the staged uniforms: k_per_draw of a single step, else the last k_per_turn
-    if (n_steps == 1 && (rc = steps_stage_guard(h, blk, q))) return rc;
+    if (n_steps == 1 && (rc = h->steps.guard(q))) return rc;
     for (int i = 0; i < n_steps; ++i) {
         const long o = (long)i * batch;
         int32_t* leaves = per.leaves_dev + o;
         float* td = per.td_abs_dev + o * K;
         double* pri = per.priorities_dev ? per.priorities_dev + o : nullptr;
-        h->is_weight = per.weights_dev + o; h->td_abs = td;
-        if (quantile || plane)
-            rc = learn_on_replay(h, fn, frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, leaves, batch, stack, tau_dev,
-                                 quantile ? batch : batch_mean_divisor, flags, stream);
-        else
-            rc = learn_on_replay_fc(h, fn, frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, leaves, batch, stack, batch_mean_divisor, flags,
-                                    stream);
-        h->is_weight = nullptr; h->td_abs = nullptr;
-        if (rc) return rc;
+        StepIn in = ring_step(nullptr, fn, frame_ring_dev, n_frames, frame_bytes, rows_dev, nullptr, leaves, batch, stack,
+                              quantile ? batch : batch_mean_divisor, flags);
+        in.tau = tau_dev; in.is_weight = per.weights_dev + o; in.td_abs = td;
+        if ((rc = quantile || plane ? learn_on_replay(h, in, stream) : learn_on_replay_fc(h, in, stream))) return rc;
         if (i + 1 < n_steps) {
             if ((rc = per_turn(per.nodes_dev, per.depth, leaves, td, K, batch, per.reduce_max, per.eps, per.alpha, pri, per.max_priority_dev,
                                per.tree_scratch_dev, u + o + batch, per.stratified, per.n_items, per.beta, leaves + batch,
                                per.weights_dev + o + batch, stream)))
                 return rc;
             if (marks) tl_mark(h, q, "k_per_turn");
-            if (i + 2 == n_steps && (rc = steps_stage_guard(h, blk, q))) return rc;
+            if (i + 2 == n_steps && (rc = h->steps.guard(q))) return rc;
         } else {
             if ((rc = per_write_back(per.nodes_dev, per.depth, leaves, td, K, batch, per.reduce_max, per.eps, per.alpha, pri,
                                      per.max_priority_dev, per.tree_scratch_dev, stream)))
@@ -3103,15 +3131,22 @@ extern "C" int idqn_iqn_learn_on_batch(idqn_handle_t h, const void* state_dev, c
     IDQN_REQUIRE(batch >= 1 && batch <= 256 && batch <= h->cfg.max_batch, "idqn_iqn_learn_on_batch: batch %d not in [1, min(256, %d)]",
                  batch, h->cfg.max_batch);
     IDQN_REQUIRE(!(flags & ~(IDQN_F_PROFILE | IDQN_F_PROFILE_ALL)), "idqn_iqn_learn_on_batch: only the profile flags are supported");
-    hipStream_t q = (hipStream_t)stream;
+    StepIn in = batch_step(h, "idqn_iqn_learn_on_batch", state_dev, next_state_dev, action_dev, reward_dev, terminal_dev, batch, batch, flags);
+    in.tau = tau_dev;
+    return learn_step(h, in, (hipStream_t)stream);
+}
+
+// The quantile step (in.tau): the plane trunk without its Dense_0, the fraction blocks of the i-IQN heads, the conv backward
+static int iqn_learn(idqn_handle_t h, const StepIn& in, hipStream_t q) {
+    const int batch = in.batch;
+    const uint32_t flags = in.flags;
+    const float* tau_dev = in.tau;
     IqnWs& w = h->iqn;
     const int K = h->cfg.n_heads, A = h->cfg.n_actions;
     const int nb = cdiv(batch, 32), NB = w.N * nb;  // blocks per virtual net: fraction q of sample block s is block s N + q
-    h->pend_B = 0; h->pend_stage = 0;
-    if (const int rc = tl_begin(h, flags, q)) return rc;
     int rc;
     // trunk of the 2K nets (online on s, target on s'), then the fraction blocks of the 3K virtual nets
-    if ((rc = cnn_forward(h, h->train, (const uint8_t*)state_dev, (const uint8_t*)next_state_dev, batch, q, false))) return rc;
+    if ((rc = cnn_forward(h, h->train, (const uint8_t*)in.state, (const uint8_t*)in.next_state, batch, q, false, in.frames ? &in : nullptr))) return rc;
     if ((rc = iqn_heads_forward(h, w.wbase_v, w.V, K, h->train.a3, tau_dev, batch, q))) return rc;
     IqnZArgs za;
     za.qpart = w.qpart; za.wbase = w.wbase_v; za.z = w.z; za.b1_off = h->off_b1; za.N = NB; za.NJC = h->J / 32; za.A = A;
@@ -3119,10 +3154,10 @@ extern "C" int idqn_iqn_learn_on_batch(idqn_handle_t h, const void* state_dev, c
     tl_mark(h, q, "iqn quantile values");
     IqnLossArgs la;
     la.z = w.z; la.K = K; la.N = w.N; la.A = A; la.nb = nb; la.lpart = w.lpart;
-    la.B = batch; la.Bdiv = batch; la.action = action_dev; la.reward = reward_dev; la.terminal = terminal_dev; la.tau = tau_dev;
+    la.B = batch; la.Bdiv = batch; la.action = in.action; la.reward = in.reward; la.terminal = in.terminal; la.tau = tau_dev;
     la.gamma_n = h->gamma_n; la.dq = w.dq; la.losses = h->losses; la.count = h->count; la.cum = h->cum; la.finish_step = 1;
     la.dbg = w.dbg; la.gate_err = w.gate + 2L * K * cdiv(h->F, 256);
-    la.is_weight = h->is_weight; la.td_abs = h->td_abs;
+    la.is_weight = in.is_weight; la.td_abs = in.td_abs;
     // (N <= 64: at most 22 KB of dynamic LDS with the priority reduction buffer, inside the default limit)
     const size_t loss_lds = (size_t)(2 * w.N * 32 + 32 * 32 + 8 * 32) * 4;
     if (la.is_weight || la.td_abs) hipLaunchKernelGGL(k_iqn_loss<true>, dim3(K, nb), dim3(256), loss_lds + 8 * 32 * 4, q, la);
@@ -4181,25 +4216,16 @@ extern "C" int idqn_profile_read(idqn_handle_t h, double* mean_ms, int32_t* n_la
 
 // ---- seed groups: S independent fc handles learn and act in one launch (fc_group_kernels.h; include/idqn_hip.h) ---------
 // A group owns no parameters: the members keep their arenas, and every member may still be driven alone between two group
-// calls.  What the group owns: a ring of per-call blocks {FcGroupMember[S], slots} (pinned block -> asynchronous copy ->
-// device block, each guarded by an event that is waited on before the block is rewritten, as idqn_learn_steps_on_replay_fc
-// stages its slots) and ONE acting slot of its own.
+// calls.  What the group owns: a staging ring (staging_ring.h) of per-call blocks {FcGroupMember[S], slots}, as
+// idqn_learn_steps_on_replay_fc stages its slots, and ONE acting slot of its own.
 struct idqn_group_s {
     std::vector<idqn_handle_t> m;
     size_t block_bytes = 0, slots_off = 0, uni_off = 0;
-    uint8_t* pin[IDQN_STEPS_STAGING_DEPTH] = {};
-    uint8_t* dev[IDQN_STEPS_STAGING_DEPTH] = {};
-    hipEvent_t ev[IDQN_STEPS_STAGING_DEPTH] = {};
-    bool busy[IDQN_STEPS_STAGING_DEPTH] = {};
-    int next = 0;
+    StagingRing ring;
     // idqn_group_per_learn_steps_on_replay_fc's blocks are larger (n_steps records per member, n_steps rows of uniforms): a ring
-    // of their own, same depth and event guard, made whole by that entry's first call; the ring above keeps its size and use
+    // of their own; the ring above keeps its size and use
     size_t ps_block_bytes = 0;
-    uint8_t* ps_pin[IDQN_STEPS_STAGING_DEPTH] = {};
-    uint8_t* ps_dev[IDQN_STEPS_STAGING_DEPTH] = {};
-    hipEvent_t ps_ev[IDQN_STEPS_STAGING_DEPTH] = {};
-    bool ps_busy[IDQN_STEPS_STAGING_DEPTH] = {};
-    int ps_next = 0;
+    StagingRing ps_ring;
     ActManySlot many;
     std::vector<void*> owned;
 };
@@ -4246,14 +4272,8 @@ extern "C" int idqn_group_destroy(idqn_group_t G) {
     for (auto& g : G->many.graphs) (void)hipGraphExecDestroy(g.second);
     if (G->many.mail) (void)hipHostFree(G->many.mail);
     if (G->many.pin) (void)hipHostFree(G->many.pin);
-    for (int i = 0; i < IDQN_STEPS_STAGING_DEPTH; ++i) {
-        if (G->pin[i]) (void)hipHostFree(G->pin[i]);
-        if (G->dev[i]) (void)hipFree(G->dev[i]);
-        if (G->ev[i]) (void)hipEventDestroy(G->ev[i]);
-        if (G->ps_pin[i]) (void)hipHostFree(G->ps_pin[i]);
-        if (G->ps_dev[i]) (void)hipFree(G->ps_dev[i]);
-        if (G->ps_ev[i]) (void)hipEventDestroy(G->ps_ev[i]);
-    }
+    G->ring.release();
+    G->ps_ring.release();
     delete G;
     return IDQN_OK;
 }
@@ -4295,34 +4315,25 @@ static void group_fill_member(FcGroupMember& m, idqn_handle_t h, const idqn_grou
 // One launch of grid (K, S): block = {FcGroupMember[S], slots [S][n_steps][batch]}, n_steps == 0: the single step k_fc_group_step
 static int group_launch(idqn_group_t G, const idqn_group_ring_t* rings, const int32_t* slots_host, long member_stride, int n_steps, int32_t batch,
                         int32_t mean_divisor, bool grads_only, hipStream_t q) {
-    const int S = (int)G->m.size(), ns = std::max(n_steps, 1), blk = G->next;
-    if (!G->pin[blk]) {
-        IDQN_HIP_CHECK(hipHostMalloc((void**)&G->pin[blk], G->block_bytes, hipHostMallocDefault));
-        IDQN_HIP_CHECK(hipMalloc((void**)&G->dev[blk], G->block_bytes));
-        IDQN_HIP_CHECK(hipEventCreateWithFlags(&G->ev[blk], hipEventDisableTiming));
-    }
-    if (G->busy[blk]) IDQN_HIP_CHECK(hipEventSynchronize(G->ev[blk]));  // the launch that read this block is done
-    G->busy[blk] = false;
-    FcGroupMember* tab = (FcGroupMember*)G->pin[blk];
-    int32_t* slots_pin = (int32_t*)(G->pin[blk] + G->slots_off);
-    const int32_t* slots_dev = (const int32_t*)(G->dev[blk] + G->slots_off);
+    const int S = (int)G->m.size(), ns = std::max(n_steps, 1);
+    StagingRing& R = G->ring;
+    if (const int rc = R.acquire(G->block_bytes)) return rc;
+    FcGroupMember* tab = (FcGroupMember*)R.pin();
+    int32_t* slots_pin = (int32_t*)(R.pin() + G->slots_off);
+    const int32_t* slots_dev = (const int32_t*)(R.dev() + G->slots_off);
     const long per = (long)ns * batch;
     for (int g = 0; g < S; ++g) {
         const idqn_group_ring_t& r = rings[g];
         memcpy(slots_pin + g * per, slots_host + g * member_stride, (size_t)per * 4);
         group_fill_member(tab[g], G->m[g], r, n_steps != 0, batch, mean_divisor, grads_only, slots_dev + g * per);
     }
-    const size_t bytes = G->slots_off + (size_t)S * per * 4;
-    IDQN_HIP_CHECK(hipMemcpyAsync(G->dev[blk], G->pin[blk], bytes, hipMemcpyHostToDevice, q));
-    G->next = (blk + 1) % IDQN_STEPS_STAGING_DEPTH;
+    if (const int rc = R.upload(G->slots_off + (size_t)S * per * 4, q)) return rc;
     const idqn_handle_t h0 = G->m[0];
     const dim3 grid((unsigned)h0->cfg.n_heads, (unsigned)S);
-    if (n_steps) hipLaunchKernelGGL(k_fc_group_steps, grid, dim3(FCM_T), (size_t)h0->fcs_plan_.floats * 4, q, (const FcGroupMember*)G->dev[blk], n_steps);
-    else hipLaunchKernelGGL(k_fc_group_step, grid, dim3(FCM_T), (size_t)h0->fcp_plan_.floats * 4, q, (const FcGroupMember*)G->dev[blk], grads_only ? 0 : 1);
+    if (n_steps) hipLaunchKernelGGL(k_fc_group_steps, grid, dim3(FCM_T), (size_t)h0->fcs_plan_.floats * 4, q, (const FcGroupMember*)R.dev(), n_steps);
+    else hipLaunchKernelGGL(k_fc_group_step, grid, dim3(FCM_T), (size_t)h0->fcp_plan_.floats * 4, q, (const FcGroupMember*)R.dev(), grads_only ? 0 : 1);
     IDQN_HIP_CHECK(hipGetLastError());
-    IDQN_HIP_CHECK(hipEventRecord(G->ev[blk], q));
-    G->busy[blk] = true;
-    return IDQN_OK;
+    return R.guard(q);
 }
 
 extern "C" int idqn_group_learn_on_replay_fc(idqn_group_t G, const idqn_group_ring_t* rings, const int32_t* slots_host, int32_t batch,
@@ -4359,18 +4370,12 @@ extern "C" int idqn_group_per_learn_on_replay_fc(idqn_group_t G, const idqn_grou
             return rc;
     }
     hipStream_t q = (hipStream_t)stream;
-    const int blk = G->next;
-    if (!G->pin[blk]) {
-        IDQN_HIP_CHECK(hipHostMalloc((void**)&G->pin[blk], G->block_bytes, hipHostMallocDefault));
-        IDQN_HIP_CHECK(hipMalloc((void**)&G->dev[blk], G->block_bytes));
-        IDQN_HIP_CHECK(hipEventCreateWithFlags(&G->ev[blk], hipEventDisableTiming));
-    }
-    if (G->busy[blk]) IDQN_HIP_CHECK(hipEventSynchronize(G->ev[blk]));  // the launches that read this block are done
-    G->busy[blk] = false;
-    FcGroupMember* tab = (FcGroupMember*)G->pin[blk];
-    PerSampler* ptab = (PerSampler*)(G->pin[blk] + G->slots_off);
-    double* uni_pin = (double*)(G->pin[blk] + G->uni_off);
-    const double* uni_dev = (const double*)(G->dev[blk] + G->uni_off);
+    StagingRing& R = G->ring;
+    if (const int rc = R.acquire(G->block_bytes)) return rc;
+    FcGroupMember* tab = (FcGroupMember*)R.pin();
+    PerSampler* ptab = (PerSampler*)(R.pin() + G->slots_off);
+    double* uni_pin = (double*)(R.pin() + G->uni_off);
+    const double* uni_dev = (const double*)(R.dev() + G->uni_off);
     for (int g = 0; g < S; ++g) {
         const idqn_per_step_t& p = per[g];
         memcpy(uni_pin + (size_t)g * batch, p.uniforms_host, (size_t)batch * 8);
@@ -4379,18 +4384,15 @@ extern "C" int idqn_group_per_learn_on_replay_fc(idqn_group_t G, const idqn_grou
         tab[g].a.td_abs = p.td_abs_dev;
         ptab[g] = per_sampler_of(p, uni_dev + (size_t)g * batch, K);
     }
-    IDQN_HIP_CHECK(hipMemcpyAsync(G->dev[blk], G->pin[blk], G->uni_off + (size_t)S * batch * 8, hipMemcpyHostToDevice, q));
-    G->next = (blk + 1) % IDQN_STEPS_STAGING_DEPTH;
+    if (const int rc = R.upload(G->uni_off + (size_t)S * batch * 8, q)) return rc;
     const idqn_handle_t h0 = G->m[0];
-    const PerSampler* ptab_dev = (const PerSampler*)(G->dev[blk] + G->slots_off);
+    const PerSampler* ptab_dev = (const PerSampler*)(R.dev() + G->slots_off);
     hipLaunchKernelGGL(k_per_group_draw, dim3((unsigned)S), dim3(PER_GROUP_DRAW_T), 0, q, ptab_dev, (int)batch);
     hipLaunchKernelGGL(k_fc_group_step, dim3((unsigned)K, (unsigned)S), dim3(FCM_T), (size_t)h0->fcp_plan_.floats * 4, q,
-                       (const FcGroupMember*)G->dev[blk], 1);
+                       (const FcGroupMember*)R.dev(), 1);
     hipLaunchKernelGGL(k_per_group_write_back, dim3((unsigned)S), dim3(ST_THREADS), 0, q, ptab_dev, (int)batch, st_pow2_at_least(batch));
     IDQN_HIP_CHECK(hipGetLastError());
-    IDQN_HIP_CHECK(hipEventRecord(G->ev[blk], q));
-    G->busy[blk] = true;
-    return IDQN_OK;
+    return R.guard(q);
 }
 
 // n_steps prioritized steps of every member as ONE call (include/idqn_hip.h): block = {FcGroupMember[n_steps][S], PerSampler
@@ -4423,17 +4425,10 @@ extern "C" int idqn_group_per_learn_steps_on_replay_fc(idqn_group_t G, const idq
             return rc;
     }
     hipStream_t q = (hipStream_t)stream;
-    if (!G->ps_ev[IDQN_STEPS_STAGING_DEPTH - 1])  // the first call makes the whole ring: nothing is allocated later
-        for (int i = 0; i < IDQN_STEPS_STAGING_DEPTH; ++i) {
-            if (!G->ps_pin[i]) IDQN_HIP_CHECK(hipHostMalloc((void**)&G->ps_pin[i], G->ps_block_bytes, hipHostMallocDefault));
-            if (!G->ps_dev[i]) IDQN_HIP_CHECK(hipMalloc((void**)&G->ps_dev[i], G->ps_block_bytes));
-            if (!G->ps_ev[i]) IDQN_HIP_CHECK(hipEventCreateWithFlags(&G->ps_ev[i], hipEventDisableTiming));
-        }
-    const int blk = G->ps_next;
-    if (G->ps_busy[blk]) IDQN_HIP_CHECK(hipEventSynchronize(G->ps_ev[blk]));  // the launches that read this block are done
-    G->ps_busy[blk] = false;
+    StagingRing& R = G->ps_ring;
+    if (const int rc = R.acquire(G->ps_block_bytes)) return rc;
     const PerGroupStepsBlock lay = per_group_steps_block(sizeof(FcGroupMember), S, n_steps, batch);
-    uint8_t *pin = G->ps_pin[blk], *dev = G->ps_dev[blk];
+    uint8_t *pin = R.pin(), *dev = R.dev();
     FcGroupMember* tab = (FcGroupMember*)pin;
     PerSampler* ptab = (PerSampler*)(pin + lay.samplers_off);
     double* uni_pin = (double*)(pin + lay.uniforms_off);
@@ -4456,8 +4451,7 @@ extern "C" int idqn_group_per_learn_steps_on_replay_fc(idqn_group_t G, const idq
             if (s.priorities) s.priorities += o;
         }
     }
-    IDQN_HIP_CHECK(hipMemcpyAsync(dev, pin, lay.bytes, hipMemcpyHostToDevice, q));
-    G->ps_next = (blk + 1) % IDQN_STEPS_STAGING_DEPTH;
+    if (const int rc = R.upload(lay.bytes, q)) return rc;
     const idqn_handle_t h0 = G->m[0];
     const FcGroupMember* tab_dev = (const FcGroupMember*)dev;
     const PerSampler* ptab_dev = (const PerSampler*)(dev + lay.samplers_off);
@@ -4472,9 +4466,7 @@ extern "C" int idqn_group_per_learn_steps_on_replay_fc(idqn_group_t G, const idq
             hipLaunchKernelGGL(k_per_group_write_back, dim3((unsigned)S), dim3(ST_THREADS), 0, q, ptab_dev + (size_t)i * S, (int)batch, m2);
     }
     IDQN_HIP_CHECK(hipGetLastError());
-    IDQN_HIP_CHECK(hipEventRecord(G->ps_ev[blk], q));
-    G->ps_busy[blk] = true;
-    return IDQN_OK;
+    return R.guard(q);
 }
 
 // n_steps steps of every member: ONE launch of k_fc_group_steps (what the members' own idqn_learn_steps_on_replay_fc would run
@@ -4484,8 +4476,7 @@ extern "C" int idqn_group_learn_steps_on_replay_fc(idqn_group_t G, const idqn_gr
     const char* fn = "idqn_group_learn_steps_on_replay_fc";
     IDQN_REQUIRE(flags == 0, "%s: takes no flags (got 0x%x): split a single step through idqn_group_learn_on_replay_fc", fn, flags);
     if (const int rc = group_learn_check(G, fn, rings, slots_host, n_steps, batch, mean_divisor, flags)) return rc;
-    const char* force_loop = getenv("IDQN_FC_LEARN_STEPS_LOOP");  // (read per call, as the single-handle entry does)
-    if (G->m[0]->fcs_plan_.floats && !(force_loop && atoi(force_loop) != 0))
+    if (G->m[0]->fcs_plan_.floats && !fc_steps_force_loop())
         return group_launch(G, rings, slots_host, (long)n_steps * batch, n_steps, batch, mean_divisor, false, (hipStream_t)stream);
     for (int i = 0; i < n_steps; ++i)
         if (const int rc = group_launch(G, rings, slots_host + (long)i * batch, (long)n_steps * batch, 0, batch, mean_divisor, false, (hipStream_t)stream))
