@@ -460,31 +460,15 @@ def test_factored_step_sums_blocks_of_several_ranks():
     """What N ranks compute, on one GPU: split a 64-sample global batch into two 32-sample shards, run the first
     half of the step on each (mean divisor 64), concatenate the exported factors the way all_gather lays them out
     ([rank][head][block]) and finish from them -- the update must equal the single-device step on the 64 samples."""
-    import torch
-
+    import factored_shapes as FS
     from slimdqn import _hip
 
-    lib = _hip.lib()
     agent, bs, rec, _ = _agent("cnn_atari_a18_b64")
-    batch = bs[0]
     K = agent._K
-    F, J = next(shape for n, _, shape in agent._leaves if n == "Dense_0/kernel")
-    X, Y = F * 32, J * 32
-    a3_all = torch.empty(2 * K * X, dtype=torch.float32, device="cuda")
-    dh_all = torch.empty(2 * K * Y, dtype=torch.float32, device="cuda")
-    small = torch.zeros_like(agent._grad_small)
-    Shard = type(batch)
-    q = _hip.current_stream
-    for r in range(2):
-        shard = Shard(*[np.asarray(f)[32 * r : 32 * (r + 1)] for f in batch])
-        agent._learn(shard, flags=_hip.F_STOP_BEFORE_DENSE0_WGRAD, mean_divisor=64)
-        _hip.check(lib.idqn_export_dense0_factors(agent._handle, _hip.ptr(a3_all[r * K * X :]),
-                                                  _hip.ptr(dh_all[r * K * Y :]), q()), "export")
-        _hip.check(lib.idqn_backward_rest(agent._handle, q()), "rest")
-        small += agent._grad_small  # what the all-reduce of the small-leaf region does
-    agent._grad_small.copy_(small)
-    _hip.check(lib.idqn_finish_step_factored(agent._handle, _hip.ptr(a3_all), _hip.ptr(dh_all), 2, 1, K * X, X, X,
-                                             K * Y, Y, Y, _hip.FACTORED_DENSE0 | _hip.FACTORED_REST, q()), "finish")
+    g = FS.emulate_ranks(agent, bs[0], 2)
+    assert (g.nb_total, g.nb_inner) == (2, 1)
+    _hip.check(_hip.lib().idqn_finish_step_factored(*g.finish_args, _hip.FACTORED_DENSE0 | _hip.FACTORED_REST, _hip.current_stream()),
+               "finish")
     st = rec["steps"][0]
     assert np.abs(agent._losses.cpu().numpy() - np.asarray(st["losses"])).max() <= LOSS_ATOL
     flat = agent._flat(agent._online)
