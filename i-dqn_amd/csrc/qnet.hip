@@ -34,6 +34,7 @@
 #include "impala_kernels.h"
 #include "impala_mx_kernels.h"
 #include "impala_mx_wgrad_kernels.h"
+#include "impala_d0_mx_kernels.h"
 #include "fc_act_many_kernels.h"
 #include "imp_act_many_kernels.h"
 #include "fc_group_kernels.h"
@@ -334,6 +335,7 @@ struct ImpalaWs {
     float* inf_ws = nullptr;
     // a head with a hidden layer: Dense_0 runs on the k_imp_d0_* kernels, k_fc_step on the layers behind it (`tail`)
     bool d0_split = false;
+    bool d0mx = false;  // IDQN_IMP_D0=mfma: that forward runs on k_imp_d0_fwd_mx (the same bytes; imp_d0_forward)
     FcNet tail;
     float* hid = nullptr;   // [2K][Bmax][D]  relu(Dense_0)
     float* dhid = nullptr;  // [K][Bmax][D]   dL/d(pre-activation of Dense_0)
@@ -1160,6 +1162,7 @@ int impala_setup(idqn_handle_s* h) {
     if ((rc = alloc_zero(&h->fc_ws, K * ((long)(n.L + 3) * B * n.dmax + 2 * B), h, "fc_ws"))) return rc;
     if ((rc = alloc_zero(&w.inf_ws, 2L * 32 * n.dmax, h, "imp_infws"))) return rc;
     w.d0_split = n.L >= 2;
+    w.d0mx = w.d0mx && impd0x_applies(1, n.L);  // a head without a hidden layer has no such launch: the mode is a no-op
     if (w.d0_split) {
         FcNet& t = w.tail;
         t.L = n.L - 1;
@@ -1295,6 +1298,21 @@ void imp_wgrad(idqn_handle_s* h, int s, int conv, int B, const uint8_t* st, cons
     tl_mark(h, q, "k_imp_wreduce");
 }
 
+// Dense_0 forward of `nets` nets on d0.B samples each, hid = relu(x W + b): the ONE statement of that launch, for the learner
+// step's 2K nets and for the one net of idqn_q_values / idqn_act_host.  Both kernels give the same bytes.
+int imp_d0_forward(idqn_handle_s* h, const ImpD0Args& d0, int nets, hipStream_t q) {
+    if (h->imp.d0mx) {
+        IDQN_REQUIRE(impd0x_shape_ok(d0.B, d0.F, d0.D, nets), "Dense_0 forward: B = %d, F = %d, D = %d, %d nets", d0.B, d0.F, d0.D, nets);
+        const impd0x_plan_t p = impd0x_plan(d0.B, d0.F, d0.D, nets);
+        hipLaunchKernelGGL(k_imp_d0_fwd_mx, dim3(p.grid_x, p.grid_y, p.grid_z), dim3(256), 0, q, d0);
+        tl_mark(h, q, "k_imp_d0_fwd_mx");
+    } else {
+        hipLaunchKernelGGL(k_imp_d0_fwd, dim3((unsigned)cdiv(d0.D, IMP_D0_OC), (unsigned)cdiv(d0.B, IMP_D0_SB), (unsigned)nets), dim3(256), 0, q, d0);
+        tl_mark(h, q, "k_imp_d0_fwd");
+    }
+    return IDQN_OK;
+}
+
 int impala_learn(idqn_handle_s* h, const StepIn& in, hipStream_t q) {
     ImpalaWs& w = h->imp;
     const ImpActs& A = w.train;
@@ -1312,8 +1330,7 @@ int impala_learn(idqn_handle_s* h, const StepIn& in, hipStream_t q) {
         d0.x = A.x[2][2]; d0.hid = w.hid; d0.dh = w.dhid; d0.din = w.d[2]; d0.wbase = h->train.wbase; d0.grad = h->grad;
         d0.gm = GradMap{h->gP, h->g_w0_begin, h->g_w0_end, h->g_w0_base};
         d0.w_off = h->fc.w_off[0]; d0.b_off = h->fc.b_off[0]; d0.B = B; d0.F = h->F; d0.D = D;
-        hipLaunchKernelGGL(k_imp_d0_fwd, dim3((unsigned)cdiv(D, IMP_D0_OC), (unsigned)sblocks, (unsigned)(2 * K)), dim3(256), 0, q, d0);
-        tl_mark(h, q, "k_imp_d0_fwd");
+        if ((rc = imp_d0_forward(h, d0, 2 * K, q))) return rc;
         a.net = w.tail; a.s = w.hid; a.s2 = w.hid + (long)K * B * D; a.s_stride = (long)B * D; a.din = w.dhid;
     }
     a.action = in.action; a.reward = in.reward; a.terminal = in.terminal;
@@ -2464,8 +2481,11 @@ extern "C" int idqn_create(const idqn_config_t* cfg, float* online_dev, float* t
     IDQN_REQUIRE(cfg->arch != IDQN_ARCH_IMPALA || imx_mode_of(imp_mode) != IMX_MODE_BAD, "IDQN_IMP_CONV must be valu or bf16x3, got '%s'", imp_mode);
     const char* imp_wmode = getenv("IDQN_IMP_WGRAD");  // the same for their weight gradients, independently
     IDQN_REQUIRE(cfg->arch != IDQN_ARCH_IMPALA || imx_mode_of(imp_wmode) != IMX_MODE_BAD, "IDQN_IMP_WGRAD must be valu or bf16x3, got '%s'", imp_wmode);
+    const char* imp_d0mode = getenv("IDQN_IMP_D0");  // the head's Dense_0 forward: k_imp_d0_fwd, or the f32 matrix-core kernel
+    IDQN_REQUIRE(cfg->arch != IDQN_ARCH_IMPALA || impd0_mode_of(imp_d0mode) != IMPD0_MODE_BAD, "IDQN_IMP_D0 must be valu or mfma, got '%s'", imp_d0mode);
     idqn_handle_s* h = new idqn_handle_s();
     h->cfg = *cfg;
+    h->imp.d0mx = cfg->arch == IDQN_ARCH_IMPALA && impd0_mode_of(imp_d0mode) == IMPD0_MODE_MFMA;
     h->imp.mx = cfg->arch == IDQN_ARCH_IMPALA && imx_mode_of(imp_mode) == IMX_MODE_BF16X3;
     h->imp.wmx = cfg->arch == IDQN_ARCH_IMPALA && imx_mode_of(imp_wmode) == IMX_MODE_BF16X3;
     int rc = build_layout(*cfg, h->L);
@@ -3471,7 +3491,7 @@ static int q_values_impl(idqn_handle_t h, int32_t which, int32_t head, const voi
             memset(&d0, 0, sizeof(d0));
             d0.x = h->imp.infer.x[2][2]; d0.hid = h->imp.inf_hid; d0.wbase = wb;
             d0.w_off = h->fc.w_off[0]; d0.b_off = h->fc.b_off[0]; d0.B = n; d0.F = h->F; d0.D = h->fc.d[1];
-            hipLaunchKernelGGL(k_imp_d0_fwd, dim3((unsigned)cdiv(d0.D, IMP_D0_OC), 1, 1), dim3(256), 0, q, d0);
+            if ((rc = imp_d0_forward(h, d0, 1, q))) return rc;
             a.net = h->imp.tail; a.s = h->imp.inf_hid;
         }
         hipLaunchKernelGGL(k_fc_q, dim3(1), dim3(256), 0, q, a);
