@@ -41,7 +41,6 @@
 #include "dp_internal.h"
 #include "per_step_args.h"
 #include "per_group_kernels.h"
-#include "per_group_steps_args.h"
 #include "convp_fwd_phases.h"
 #include "convp_items.h"
 #include "staging_ring.h"
@@ -363,6 +362,13 @@ struct ActManySlot {
     unsigned* ctr = nullptr;      // device side: {sequence number, finished workgroups}
     unsigned expected = 0;        // sequence number the next call waits for
     std::map<std::tuple<int, void*, void*>, hipGraphExec_t> graphs;  // (n, q out, host actions)
+
+    // what act_many_alloc's `owned` does not hold: the graphs and the two host blocks (the destroy functions, device idle)
+    void release() {
+        for (auto& g : graphs) (void)hipGraphExecDestroy(g.second);
+        if (mail) (void)hipHostFree(mail);
+        if (pin) (void)hipHostFree(pin);
+    }
 };
 
 struct idqn_handle_s {
@@ -2532,13 +2538,11 @@ extern "C" int idqn_destroy(idqn_handle_t h) {
         if (e) (void)hipEventDestroy(e);
     for (auto& g : h->act_graphs) (void)hipGraphExecDestroy(g.second);
     for (auto& g : h->iact_graphs) (void)hipGraphExecDestroy(g.second);
-    for (auto& g : h->many.graphs) (void)hipGraphExecDestroy(g.second);
     for (auto& g : h->step_graphs)
         if (g.second.second) (void)hipGraphExecDestroy(g.second.second);
     if (h->act_stream) (void)hipStreamDestroy(h->act_stream);
     if (h->act_mail) (void)hipHostFree(h->act_mail);
-    if (h->many.mail) (void)hipHostFree(h->many.mail);
-    if (h->many.pin) (void)hipHostFree(h->many.pin);
+    h->many.release();
     h->steps.release();
     if (h->fact_planes) (void)hipFree(h->fact_planes);
     for (int32_t* p : h->iqn.bwd_items)
@@ -2787,6 +2791,19 @@ static int replay_check(idqn_handle_t h, const char* fn, const uint8_t* frame_ri
     return IDQN_OK;
 }
 
+// h->rp_action / rp_reward / rp_terminal, the scalars of the sampled rows, on a handle's first replay-sourced call (behind that
+// call's refusals).  One set per handle whichever of the two callers comes first; learn_on_replay_fc's first call waits for the
+// null stream once here and once more behind its own state buffers (a first call only).
+static int ensure_replay_scalars(idqn_handle_t h) {
+    if (h->rp_action) return IDQN_OK;
+    const long mb = h->cfg.max_batch;
+    float* f = nullptr;
+    if (const int rc = alloc_zero(&f, 3L * mb + 64, h, "replay scalars")) return rc;
+    IDQN_HIP_CHECK(hipStreamSynchronize(nullptr));  // (the zero-fill runs on the null stream)
+    h->rp_action = (int32_t*)f; h->rp_reward = f + mb; h->rp_terminal = (uint8_t*)(f + 2L * mb);
+    return IDQN_OK;
+}
+
 // iDQN.update_online_params (idqn.py:65-72) on the HBM frame ring: replay_buffer.py:215-230's sample() fused into the step.
 // `in` names the ring (ring_step); exactly one of its slots_host / slots_dev is set.
 //
@@ -2797,14 +2814,7 @@ static int learn_on_replay(idqn_handle_t h, StepIn in, void* stream) {
     if (const int rc = replay_check(h, in.fn, (const uint8_t*)in.frames, in.n_frames, in.frame_bytes, in.rows, in.slots_host, in.slots_dev, in.batch,
                                     in.stack, in.tau, in.flags))
         return rc;
-    if (!h->rp_action) {
-        const int mb = h->cfg.max_batch;
-        float* f = nullptr;
-        int rc = alloc_zero(&f, 3L * mb + 64, h, "replay scalars");
-        if (rc) return rc;
-        IDQN_HIP_CHECK(hipStreamSynchronize(nullptr));  // (the zero-fill runs on the null stream)
-        h->rp_action = (int32_t*)f; h->rp_reward = f + mb; h->rp_terminal = (uint8_t*)(f + 2L * mb);
-    }
+    if (const int rc = ensure_replay_scalars(h)) return rc;
     // (reported under the batch entry's name, and behind the first call's allocation, since the step first ran through that entry)
     IDQN_REQUIRE(in.tau || in.mean_divisor >= in.batch, "idqn_learn_on_batch: mean divisor %d < batch %d", in.mean_divisor, in.batch);
     // (the state pointers are what the staging launch is told beside the ring; it gathers from the ring)
@@ -2887,15 +2897,14 @@ static int learn_on_replay_fc(idqn_handle_t h, StepIn in, void* stream) {
                                        in.mean_divisor, in.flags, &obs_elems))
         return rc;
     const bool fc = h->cfg.arch == IDQN_ARCH_FC;
+    if (const int rc = ensure_replay_scalars(h)) return rc;
     if (!h->rp_state) {
-        const long mb = h->cfg.max_batch, words = (mb * obs_elems * (fc ? 4 : 1) + 3) / 4;
-        float *f = nullptr, *s = nullptr, *s2 = nullptr;
+        const long words = ((long)h->cfg.max_batch * obs_elems * (fc ? 4 : 1) + 3) / 4;
+        float *s = nullptr, *s2 = nullptr;
         int rc;
-        if ((rc = alloc_zero(&f, 3L * mb + 64, h, "replay scalars"))) return rc;
         if ((rc = alloc_zero(&s, words, h, "replay state"))) return rc;
         if ((rc = alloc_zero(&s2, words, h, "replay next_state"))) return rc;
         IDQN_HIP_CHECK(hipStreamSynchronize(nullptr));  // (the zero-fill runs on the null stream)
-        h->rp_action = (int32_t*)f; h->rp_reward = f + mb; h->rp_terminal = (uint8_t*)(f + 2L * mb);
         h->rp_state = s; h->rp_next = s2;
     }
     // the step's kernel is told the handle-owned minibatch either way (k_fc_step_par reads the ring and the rows instead)
@@ -4236,19 +4245,24 @@ extern "C" int idqn_profile_read(idqn_handle_t h, double* mean_ms, int32_t* n_la
 
 // ---- seed groups: S independent fc handles learn and act in one launch (fc_group_kernels.h; include/idqn_hip.h) ---------
 // A group owns no parameters: the members keep their arenas, and every member may still be driven alone between two group
-// calls.  What the group owns: a staging ring (staging_ring.h) of per-call blocks {FcGroupMember[S], slots}, as
-// idqn_learn_steps_on_replay_fc stages its slots, and ONE acting slot of its own.
+// calls.  What the group owns: ONE staging ring (staging_ring.h) of per-call blocks -- {FcGroupMember[S], slots}, as
+// idqn_learn_steps_on_replay_fc stages its slots, or a prioritized call's records and uniforms (group_per_learn); the four
+// learner entries interleave on it, each block behind its own event -- and ONE acting slot of its own.
 struct idqn_group_s {
     std::vector<idqn_handle_t> m;
-    size_t block_bytes = 0, slots_off = 0, uni_off = 0;
+    size_t block_bytes = 0, slots_off = 0;  // a block holds the largest call of any of the four learner entries
     StagingRing ring;
-    // idqn_group_per_learn_steps_on_replay_fc's blocks are larger (n_steps records per member, n_steps rows of uniforms): a ring
-    // of their own; the ring above keeps its size and use
-    size_t ps_block_bytes = 0;
-    StagingRing ps_ring;
     ActManySlot many;
     std::vector<void*> owned;
 };
+
+// Member c of a group (seed or acting) has the shape of member 0
+static bool same_member_shape(const idqn_config_t& c, const idqn_config_t& c0, bool with_max_batch) {
+    bool same = c.obs_h == c0.obs_h && c.obs_w == c0.obs_w && c.obs_c == c0.obs_c && c.n_features == c0.n_features &&
+                c.n_actions == c0.n_actions && c.n_heads == c0.n_heads && (!with_max_batch || c.max_batch == c0.max_batch);
+    for (int i = 0; same && i < c.n_features; ++i) same = c.features[i] == c0.features[i];
+    return same;
+}
 
 extern "C" int idqn_group_create(const idqn_handle_t* members, int32_t n_members, idqn_group_t* out) {
     IDQN_REQUIRE(members && out, "idqn_group_create: null pointer");
@@ -4261,11 +4275,8 @@ extern "C" int idqn_group_create(const idqn_handle_t* members, int32_t n_members
                      "idqn_group_create: member %d is not an MLP (fc) handle: groups serve fc handles only", g);
         IDQN_REQUIRE(h->fcp_plan_.floats != 0,
                      "idqn_group_create: member %d is outside the one-launch step (layer widths <= 128, heads of <= %d parameters)", g, 512 * FCP_NPT);
-        const idqn_config_t &c = h->cfg, &c0 = members[0]->cfg;
-        bool same = c.obs_h == c0.obs_h && c.obs_w == c0.obs_w && c.obs_c == c0.obs_c && c.n_features == c0.n_features &&
-                    c.n_actions == c0.n_actions && c.n_heads == c0.n_heads && c.max_batch == c0.max_batch;
-        for (int i = 0; same && i < c.n_features; ++i) same = c.features[i] == c0.features[i];
-        IDQN_REQUIRE(same, "idqn_group_create: member %d differs from member 0 in shape (obs, features, n_actions, n_heads, max_batch)", g);
+        IDQN_REQUIRE(same_member_shape(h->cfg, members[0]->cfg, true),
+                     "idqn_group_create: member %d differs from member 0 in shape (obs, features, n_actions, n_heads, max_batch)", g);
         for (int j = 0; j < g; ++j)
             IDQN_REQUIRE(members[j] != h && members[j]->online != h->online,
                          "idqn_group_create: members %d and %d are the same handle or share an arena: one arena would have two writers", j, g);
@@ -4277,10 +4288,9 @@ extern "C" int idqn_group_create(const idqn_handle_t* members, int32_t n_members
     idqn_group_s* G = new idqn_group_s();
     G->m.assign(members, members + n_members);
     G->slots_off = ((size_t)n_members * sizeof(FcGroupMember) + 15) & ~(size_t)15;
-    // the prioritized call (idqn_group_per_learn_on_replay_fc) puts its tree records and uniforms where the slots go
-    G->uni_off = G->slots_off + (((size_t)n_members * sizeof(PerSampler) + 15) & ~(size_t)15);
-    G->block_bytes = std::max(G->slots_off + (size_t)n_members * STEPS_SLOTS_BYTES, G->uni_off + (size_t)n_members * PER_GROUP_MAX_N * 8);
-    G->ps_block_bytes = per_group_steps_block(sizeof(FcGroupMember), n_members, IDQN_MAX_STEPS_PER_CALL, PER_GROUP_MAX_N).bytes;
+    // the larger of the plain layout {FcGroupMember[S], slots} and the prioritized one (per_group_args.h) at its limits
+    G->block_bytes = std::max(G->slots_off + (size_t)n_members * STEPS_SLOTS_BYTES,
+                              per_group_steps_block(sizeof(FcGroupMember), n_members, IDQN_MAX_STEPS_PER_CALL, PER_GROUP_MAX_N).bytes);
     *out = G;
     return IDQN_OK;
 }
@@ -4289,11 +4299,8 @@ extern "C" int idqn_group_destroy(idqn_group_t G) {
     if (!G) return IDQN_OK;
     (void)hipDeviceSynchronize();
     for (void* p : G->owned) (void)hipFree(p);
-    for (auto& g : G->many.graphs) (void)hipGraphExecDestroy(g.second);
-    if (G->many.mail) (void)hipHostFree(G->many.mail);
-    if (G->many.pin) (void)hipHostFree(G->many.pin);
+    G->many.release();
     G->ring.release();
-    G->ps_ring.release();
     delete G;
     return IDQN_OK;
 }
@@ -4362,23 +4369,27 @@ extern "C" int idqn_group_learn_on_replay_fc(idqn_group_t G, const idqn_group_ri
     return group_launch(G, rings, slots_host, batch, 0, batch, mean_divisor, (flags & IDQN_F_GRADS_ONLY) != 0, (hipStream_t)stream);
 }
 
-// The prioritized step of every member as ONE call (include/idqn_hip.h): block = {FcGroupMember[S], PerSampler[S], uniforms
-// [S][batch]} in the group's staging ring -> one copy -> k_per_group_draw (S) -> k_fc_group_step (K, S) on the members' leaves,
-// weights and |TD| (they travel in the table: the members' own h->is_weight / h->td_abs stay unset) -> k_per_group_write_back (S).
-// Every refusal comes before anything is enqueued, allocated or staged.
+// n_steps prioritized steps of every member, the driver of idqn_group_per_learn_on_replay_fc (n_steps == 1) and
+// idqn_group_per_learn_steps_on_replay_fc; P is idqn_per_step_t or idqn_per_steps_t (the same fields; tau_dev is the former's and
+// is refused).  Block = {FcGroupMember[n_steps][S], PerSampler[n_steps][S], uniforms [S][n_steps][batch]} (per_group_args.h) in
+// the group's staging ring -> one copy of the bytes the call fills -> k_per_group_draw (S) on row 0 -> for every step
+// k_fc_group_step (K, S) on that step's records, which carry the members' leaves, weights and |TD| (the members' own
+// h->is_weight / h->td_abs stay unset) -> k_per_group_turn (S) behind every step but the last -> k_per_group_write_back (S):
+// 2 n_steps + 1 launches.  The persistent k_fc_group_steps cannot serve: every step's draw depends on the previous step's |TD|.
+// Every refusal -- the entries' and this one's -- comes before anything is enqueued, allocated or staged.
 static_assert(PER_GROUP_MAX_N == RPS_PAR_SLOTS, "a prioritized group batch is a batch of the one-launch step");
-extern "C" int idqn_group_per_learn_on_replay_fc(idqn_group_t G, const idqn_group_ring_t* rings, const idqn_per_step_t* per, int32_t batch,
-                                                 int32_t mean_divisor, uint32_t flags, void* stream) {
-    const char* fn = "idqn_group_per_learn_on_replay_fc";
-    IDQN_REQUIRE(G && rings && per, "%s: null pointer", fn);
+template <class P>
+static int group_per_learn(idqn_group_t G, const char* fn, const idqn_group_ring_t* rings, const P* per, int32_t n_steps, int32_t batch,
+                           int32_t mean_divisor, uint32_t flags, void* stream) {
     IDQN_REQUIRE(batch >= 1 && batch <= PER_GROUP_MAX_N, "%s: batch %d not in [1, %d]: a group runs the one-launch step", fn, batch, PER_GROUP_MAX_N);
-    IDQN_REQUIRE(flags == 0, "%s: takes no flags (got 0x%x): profile or split a member's step alone", fn, flags);
+    IDQN_REQUIRE(flags == 0, "%s: takes no flags (got 0x%x): profile or split a member's %s alone", fn, flags,
+                 std::is_same<P, idqn_per_steps_t>::value ? "steps" : "step");
     const int S = (int)G->m.size(), K = G->m[0]->cfg.n_heads;
     for (int g = 0; g < S; ++g)
         IDQN_REQUIRE(!G->m[g]->is_weight && !G->m[g]->td_abs,
                      "%s: member %d has prioritized-replay buffers set (idqn_set_per_buffers): the call carries the members' weights and |TD| itself", fn, g);
     int bad_g = -1, bad_j = -1;
-    const char* bad = per_group_args_error(per, S, batch, K, &bad_g, &bad_j);
+    const char* bad = per_group_args_error(per, S, n_steps, batch, K, &bad_g, &bad_j);
     IDQN_REQUIRE(!bad || bad_j < 0, "%s: members %d and %d: %s", fn, bad_j, bad_g, bad ? bad : "");
     IDQN_REQUIRE(!bad, "%s: member %d: %s (depth %d, batch %d, n_items %ld)", fn, bad_g, bad, bad_g >= 0 ? per[bad_g].depth : 0, batch,
                  bad_g >= 0 ? (long)per[bad_g].n_items : 0L);
@@ -4392,61 +4403,6 @@ extern "C" int idqn_group_per_learn_on_replay_fc(idqn_group_t G, const idqn_grou
     hipStream_t q = (hipStream_t)stream;
     StagingRing& R = G->ring;
     if (const int rc = R.acquire(G->block_bytes)) return rc;
-    FcGroupMember* tab = (FcGroupMember*)R.pin();
-    PerSampler* ptab = (PerSampler*)(R.pin() + G->slots_off);
-    double* uni_pin = (double*)(R.pin() + G->uni_off);
-    const double* uni_dev = (const double*)(R.dev() + G->uni_off);
-    for (int g = 0; g < S; ++g) {
-        const idqn_per_step_t& p = per[g];
-        memcpy(uni_pin + (size_t)g * batch, p.uniforms_host, (size_t)batch * 8);
-        group_fill_member(tab[g], G->m[g], rings[g], false, batch, mean_divisor, false, p.leaves_dev);
-        tab[g].a.is_weight = p.weights_dev;
-        tab[g].a.td_abs = p.td_abs_dev;
-        ptab[g] = per_sampler_of(p, uni_dev + (size_t)g * batch, K);
-    }
-    if (const int rc = R.upload(G->uni_off + (size_t)S * batch * 8, q)) return rc;
-    const idqn_handle_t h0 = G->m[0];
-    const PerSampler* ptab_dev = (const PerSampler*)(R.dev() + G->slots_off);
-    hipLaunchKernelGGL(k_per_group_draw, dim3((unsigned)S), dim3(PER_GROUP_DRAW_T), 0, q, ptab_dev, (int)batch);
-    hipLaunchKernelGGL(k_fc_group_step, dim3((unsigned)K, (unsigned)S), dim3(FCM_T), (size_t)h0->fcp_plan_.floats * 4, q,
-                       (const FcGroupMember*)R.dev(), 1);
-    hipLaunchKernelGGL(k_per_group_write_back, dim3((unsigned)S), dim3(ST_THREADS), 0, q, ptab_dev, (int)batch, st_pow2_at_least(batch));
-    IDQN_HIP_CHECK(hipGetLastError());
-    return R.guard(q);
-}
-
-// n_steps prioritized steps of every member as ONE call (include/idqn_hip.h): block = {FcGroupMember[n_steps][S], PerSampler
-// [n_steps][S], uniforms [S][n_steps][batch]} (per_group_steps_args.h) in the entry's own staging ring -> one copy ->
-// k_per_group_draw (S) on row 0 -> for every step k_fc_group_step (K, S) on that step's records -> k_per_group_turn (S) behind
-// every step but the last -> k_per_group_write_back (S): 2 n_steps + 1 launches.  The persistent k_fc_group_steps cannot serve:
-// every step's draw depends on the previous step's |TD|.  At n_steps == 1 this is idqn_group_per_learn_on_replay_fc's sequence.
-// Every refusal comes before anything is enqueued, allocated or staged.
-extern "C" int idqn_group_per_learn_steps_on_replay_fc(idqn_group_t G, const idqn_group_ring_t* rings, const idqn_per_steps_t* per, int32_t n_steps,
-                                                       int32_t batch, int32_t mean_divisor, uint32_t flags, void* stream) {
-    const char* fn = "idqn_group_per_learn_steps_on_replay_fc";
-    IDQN_REQUIRE(G && rings && per, "%s: null pointer", fn);
-    IDQN_REQUIRE(n_steps >= 1 && n_steps <= IDQN_MAX_STEPS_PER_CALL, "%s: n_steps %d not in [1, %d]", fn, n_steps, IDQN_MAX_STEPS_PER_CALL);
-    IDQN_REQUIRE(batch >= 1 && batch <= PER_GROUP_MAX_N, "%s: batch %d not in [1, %d]: a group runs the one-launch step", fn, batch, PER_GROUP_MAX_N);
-    IDQN_REQUIRE(flags == 0, "%s: takes no flags (got 0x%x): profile or split a member's steps alone", fn, flags);
-    const int S = (int)G->m.size(), K = G->m[0]->cfg.n_heads;
-    for (int g = 0; g < S; ++g)
-        IDQN_REQUIRE(!G->m[g]->is_weight && !G->m[g]->td_abs,
-                     "%s: member %d has prioritized-replay buffers set (idqn_set_per_buffers): the call carries the members' weights and |TD| itself", fn, g);
-    int bad_g = -1, bad_j = -1;
-    const char* bad = per_group_steps_args_error(per, S, n_steps, batch, K, &bad_g, &bad_j);
-    IDQN_REQUIRE(!bad || bad_j < 0, "%s: members %d and %d: %s", fn, bad_j, bad_g, bad ? bad : "");
-    IDQN_REQUIRE(!bad, "%s: member %d: %s (depth %d, batch %d, n_items %ld)", fn, bad_g, bad, bad_g >= 0 ? per[bad_g].depth : 0, batch,
-                 bad_g >= 0 ? (long)per[bad_g].n_items : 0L);
-    for (int g = 0; g < S; ++g) {
-        const idqn_group_ring_t& r = rings[g];
-        long obs_elems;
-        if (const int rc = replay_fc_check(G->m[g], fn, (const uint8_t*)r.frames_dev, r.n_frames, r.frame_bytes, r.rows_dev, nullptr, per[g].leaves_dev, batch,
-                                           r.stack, mean_divisor, flags, &obs_elems))
-            return rc;
-    }
-    hipStream_t q = (hipStream_t)stream;
-    StagingRing& R = G->ps_ring;
-    if (const int rc = R.acquire(G->ps_block_bytes)) return rc;
     const PerGroupStepsBlock lay = per_group_steps_block(sizeof(FcGroupMember), S, n_steps, batch);
     uint8_t *pin = R.pin(), *dev = R.dev();
     FcGroupMember* tab = (FcGroupMember*)pin;
@@ -4454,7 +4410,7 @@ extern "C" int idqn_group_per_learn_steps_on_replay_fc(idqn_group_t G, const idq
     double* uni_pin = (double*)(pin + lay.uniforms_off);
     const double* uni_dev = (const double*)(dev + lay.uniforms_off);
     for (int g = 0; g < S; ++g) {
-        const idqn_per_steps_t& p = per[g];
+        const P& p = per[g];
         const size_t rows = (size_t)g * n_steps * batch;  // member g's rows of uniforms
         memcpy(uni_pin + rows, p.uniforms_host, (size_t)n_steps * batch * 8);
         group_fill_member(tab[g], G->m[g], rings[g], false, batch, mean_divisor, false, p.leaves_dev);
@@ -4487,6 +4443,23 @@ extern "C" int idqn_group_per_learn_steps_on_replay_fc(idqn_group_t G, const idq
     }
     IDQN_HIP_CHECK(hipGetLastError());
     return R.guard(q);
+}
+
+// The prioritized step of every member as ONE call (include/idqn_hip.h): the driver at one step.
+extern "C" int idqn_group_per_learn_on_replay_fc(idqn_group_t G, const idqn_group_ring_t* rings, const idqn_per_step_t* per, int32_t batch,
+                                                 int32_t mean_divisor, uint32_t flags, void* stream) {
+    const char* fn = "idqn_group_per_learn_on_replay_fc";
+    IDQN_REQUIRE(G && rings && per, "%s: null pointer", fn);
+    return group_per_learn(G, fn, rings, per, 1, batch, mean_divisor, flags, stream);
+}
+
+// n_steps of them as ONE call (include/idqn_hip.h): the driver, where n_steps single calls make 3 n_steps launches and n_steps uploads.
+extern "C" int idqn_group_per_learn_steps_on_replay_fc(idqn_group_t G, const idqn_group_ring_t* rings, const idqn_per_steps_t* per, int32_t n_steps,
+                                                       int32_t batch, int32_t mean_divisor, uint32_t flags, void* stream) {
+    const char* fn = "idqn_group_per_learn_steps_on_replay_fc";
+    IDQN_REQUIRE(G && rings && per, "%s: null pointer", fn);
+    IDQN_REQUIRE(n_steps >= 1 && n_steps <= IDQN_MAX_STEPS_PER_CALL, "%s: n_steps %d not in [1, %d]", fn, n_steps, IDQN_MAX_STEPS_PER_CALL);
+    return group_per_learn(G, fn, rings, per, n_steps, batch, mean_divisor, flags, stream);
 }
 
 // n_steps steps of every member: ONE launch of k_fc_group_steps (what the members' own idqn_learn_steps_on_replay_fc would run
@@ -4572,11 +4545,7 @@ extern "C" int idqn_act_group_create(const idqn_handle_t* members, int32_t n_mem
         IDQN_REQUIRE(h->cfg.n_actions <= 32, "%s: member %d has A = %d > 32 actions: the acting kernels take A <= 32", fn, g, h->cfg.n_actions);
         IDQN_REQUIRE(!h->gc.on, "%s: member %d is a general-shape cnn handle: outside the single-state MFMA cnn acting path", fn, g);
         if (const int rc = act_many_conv_plans(h, fn)) return rc;
-        const idqn_config_t &c = h->cfg, &c0 = members[0]->cfg;
-        bool same = c.obs_h == c0.obs_h && c.obs_w == c0.obs_w && c.obs_c == c0.obs_c && c.n_features == c0.n_features &&
-                    c.n_actions == c0.n_actions && c.n_heads == c0.n_heads;
-        for (int i = 0; same && i < c.n_features; ++i) same = c.features[i] == c0.features[i];
-        IDQN_REQUIRE(same, "%s: member %d differs from member 0 in shape (obs, features, n_actions, n_heads)", fn, g);
+        IDQN_REQUIRE(same_member_shape(h->cfg, members[0]->cfg, false), "%s: member %d differs from member 0 in shape (obs, features, n_actions, n_heads)", fn, g);
         for (int j = 0; j < g; ++j) IDQN_REQUIRE(members[j] != h, "%s: members %d and %d are the same handle", fn, j, g);
     }
     IDQN_REQUIRE(((size_t)members[0]->cfg.obs_h * members[0]->cfg.obs_w * members[0]->cfg.obs_c) % 4 == 0, "%s: bytes per state must be a multiple of 4", fn);
@@ -4590,9 +4559,7 @@ extern "C" int idqn_act_group_destroy(idqn_act_group_t G) {
     if (!G) return IDQN_OK;
     (void)hipDeviceSynchronize();
     for (void* p : G->owned) (void)hipFree(p);
-    for (auto& g : G->many.graphs) (void)hipGraphExecDestroy(g.second);
-    if (G->many.mail) (void)hipHostFree(G->many.mail);
-    if (G->many.pin) (void)hipHostFree(G->many.pin);
+    G->many.release();
     delete G;
     return IDQN_OK;
 }

@@ -3,7 +3,7 @@
 // upload into the device twin (upload) and, behind the LAST launch that reads the twin (dev()), records the block's event
 // (guard).  A block is rewritten only after that event has passed -- acquire waits for it -- so back-to-back calls need no
 // synchronisation of their own.  Serves the handle's ring (slots of idqn_learn_steps_on_replay_fc, uniforms of the prioritized
-// entries) and the two rings of a seed group.
+// entries) and the one ring of a seed group, on which its four learner entries interleave.
 //
 // Allocation rule, the same for every ring: the first acquire makes the WHOLE ring, every block `block_bytes` large, and nothing
 // is allocated later; when any part of that fails, what it got is freed again and the ring stays empty (a later acquire starts

@@ -450,9 +450,9 @@ int idqn_group_per_learn_on_replay_fc(idqn_group_t group, const idqn_group_ring_
  * idqn_group_per_learn_on_replay_fc make 3 n_steps launches and n_steps uploads and S calls of idqn_per_learn_steps_on_replay
  * S (2 n_steps + 1) launches.  At n_steps = 1 the call enqueues exactly what idqn_group_per_learn_on_replay_fc enqueues.  The
  * persistent k_fc_group_steps cannot serve here: every step's draw depends on the previous step's |TD|, so the sampler has to
- * run between two steps.  The block is larger than the other group entries' and has a staging ring of its own
+ * run between two steps.  The block lies in the group's one staging ring, which every group learner entry shares
  * (IDQN_STEPS_STAGING_DEPTH blocks sized for n_steps = 32, each reused only after the launches that read it have finished;
- * all allocated by the first call of this entry, none later); the other entries' ring and bytes are untouched.
+ * all allocated by the group's first learner call, none later); the bytes a call uploads are its own block's alone.
  * CONTRACT: for every member, online parameters, both moments, count, losses, cum_losses, tree nodes, max_priority_dev and
  * every step's row of leaves, weights, |TD| and priorities after the call equal, byte for byte, n_steps calls of
  * idqn_group_per_learn_on_replay_fc on the rows of the uniforms on the same stream -- hence also

@@ -319,6 +319,58 @@ def test_six_calls_back_to_back_then_a_member_alone():
     group.close(), twin_group.close()
 
 
+def test_the_four_group_learner_entries_share_one_ring():
+    """S = 2, B = 7: eight learner calls back to back, no host synchronisation between them, through the four group learner
+    entries -- the prioritized single call, the plain n-step call (n = 3), the prioritized n-step call (n = 3), the plain single
+    call -- against the same calls on the twins with a ``torch.cuda.synchronize()`` after each.  Eight is twice
+    ``IDQN_STEPS_STAGING_DEPTH``: every block of the group's staging ring is written a second time while earlier calls may still be
+    running.  The second round starts one entry later than the first, so on a ring of four blocks a block's second writer is
+    another entry, with another layout, than its first.  The plain calls take the slots a prioritized draw could have given
+    (any index below the member's item count)."""
+    import torch
+
+    from slimdqn import _hip
+
+    S, B, n, calls = 2, 7, 3, 8
+    assert calls > _hip.STEPS_STAGING_DEPTH
+    assert _hip.STEPS_STAGING_DEPTH == 4, "the schedule below is worked out for a ring of four blocks: two rounds of the four entries"
+    members, twins = _sets(S, B=B)
+    rng = np.random.default_rng(29)
+    rows, twin_rows = [_Rows(lr, n, B) for lr in members], [_Rows(lr, n, B) for lr in twins]
+    group, twin_group = _Group(members), _Group(twins)
+    script = []  # (entry, its uniforms [S] x [steps][B] or slots [S][steps][B]), the same for both sides
+    for c in range(calls):
+        entry = (c + c // _hip.STEPS_STAGING_DEPTH) % 4
+        steps = n if entry in (1, 2) else 1
+        if entry in (0, 2):
+            script.append((entry, _uniforms(rng, S, steps, B)))
+        else:
+            script.append((entry, np.stack([rng.integers(0, len(lr.sampler), (steps, B)) for lr in members]).astype(np.int32)))
+    assert sorted(e for e, _ in script) == [0, 0, 1, 1, 2, 2, 3, 3]
+
+    def run(grp, rws, sync):
+        lib, q = _hip.lib(), _hip.current_stream()
+        for entry, x in script:
+            if entry == 0:
+                grp.singles(x, rws)
+            elif entry == 2:
+                grp.steps(x, rws)
+            elif entry == 1:
+                _hip.check(lib.idqn_group_learn_steps_on_replay_fc(grp.g, grp.rings(), x.ctypes.data, n, B, B, 0, q), "idqn_group_learn_steps_on_replay_fc")
+            else:
+                _hip.check(lib.idqn_group_learn_on_replay_fc(grp.g, grp.rings(), x.ctypes.data, B, B, 0, q), "idqn_group_learn_on_replay_fc")
+            if sync:
+                torch.cuda.synchronize()
+
+    run(group, rows, False)
+    run(twin_group, twin_rows, True)
+    torch.cuda.synchronize()
+    _assert_equal(_snapshot(members, rows), _snapshot(twins, twin_rows), "four entries on one ring")
+    for lr in members:
+        assert (lr.agent._count.cpu().numpy() == 2 * (1 + n + n + 1)).all() and np.isfinite(lr.agent._losses.cpu().numpy()).all()
+    group.close(), twin_group.close()
+
+
 def test_refusals_leave_everything_untouched():
     import torch
 
